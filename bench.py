@@ -10,8 +10,16 @@ GPU count grows (weak scaling, scenarios sharded by global id, no
 communication inside the loop).  The per-step outputs (u_k, x_{k+1}) are
 gathered over RCCL at the end of the timed region (the end-of-batch gather).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full [--no-cpu]]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does what the headline figure needs and no more: set up, W warmup
+steps, the K timed steps, the outputs of the last timed step written under
+--dump-outputs DIR if given, and the result line (its roofline and solver
+entries come from counters of the timed launches themselves, not from runs of
+their own).  --full adds the legs that take runs of their own: the recompute of
+a seeded sample of the record (gather_verify), the disturbed leg and the CPU
+baseline (each still switched off by --verify 0, --no-disturbed, --no-cpu).
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, the script starts the
 N ranks itself (torch.distributed.run as a child process, before any GPU
@@ -20,8 +28,8 @@ call); under a launcher, WORLD_SIZE must equal --gpus or it exits with 2.
 Rank 0 prints ONE JSON line (bench contract).  roofline.achieved uses this
 build's own algorithmic flop count (ntm_mpc/flops.py),
 driven by the kernel's own solver counters accumulated over exactly the K
-timed launches, over the kernel's HIP-event-timed average duration.  A second
-leg ("disturbed") runs the same workload with the scenario generator on
+timed launches, over the kernel's HIP-event-timed average duration.  With --full
+a second leg ("disturbed") runs the same workload with the scenario generator on
 (per-step w disturbance sigma_w = 1e-3 m and +-10% j_BS / w_dep plasma
 scenarios) and reports its rate and warm-start statistics.
 """
@@ -51,11 +59,17 @@ def parse(argv=None):
     ap.add_argument("--batch", type=int, default=100_000, help="scenarios per GPU")
     ap.add_argument("--N", type=int, default=20)
     ap.add_argument("--mode", type=int, default=2)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-disturbed", action="store_true", help="skip the disturbed-loop leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: the gather_verify recompute, the "
+                         "disturbed leg and the CPU baseline (a plain run times the K steps and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs (U, x_pred, x_next, "
+                         "exitflag, inner_iters) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-disturbed", action="store_true", help="--full: skip the disturbed-loop leg")
     ap.add_argument("--sigma-w", type=float, default=1e-3, help="disturbed leg: w disturbance per step [m]")
     ap.add_argument("--spread", type=float, default=0.1, help="disturbed leg: j_BS / w_dep spread over scenarios")
-    ap.add_argument("--verify", type=int, default=64, help="scenarios rank 0 recomputes after the gather")
+    ap.add_argument("--verify", type=int, default=64, help="--full: scenarios rank 0 recomputes after the gather")
     ap.add_argument("--no-stats", action="store_true",
                     help="A/B only: leave the solver counters off in the timed region (roofline then unavailable)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU sample length")
@@ -325,6 +339,32 @@ def _verify_gathered(ctl, cfg, B_total, K, W, g, n_verify, seed=12345):
     return {"scenarios": n, "ids_seed": seed, "bitwise_equal": not bad, "mismatched": bad}
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20      # a dump stays under 64 MB in all
+
+
+def dump_outputs(out, directory, seed=20241220):
+    """--dump-outputs: the last timed step's outputs as a caller of the step entry
+    point receives them (U (N, B), x_pred (2(N+1), B), x_next (2, B), exitflag and
+    inner_iters (B,); scenario = last axis), each written as DIR/<name>.npy in
+    float64.  Outputs beyond the budget are written for a fixed, seeded sample of
+    the scenarios; scenario_ids.npy holds the ids written (ascending), either way."""
+    import numpy as np
+    import torch
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    B = out["exitflag"].shape[-1]
+    per_scenario = 8 * (1 + sum(v.numel() // B for v in out.values()))
+    keep = max(1, DUMP_BUDGET_BYTES // per_scenario)
+    ids = np.arange(B)
+    if B > keep:
+        ids = np.sort(np.random.default_rng(seed).choice(B, size=keep, replace=False))
+    for k, v in out.items():
+        if B > keep:
+            v = v.index_select(-1, torch.as_tensor(ids, device=v.device))
+        np.save(d / f"{k}.npy", np.ascontiguousarray(v.to(torch.float64).cpu().numpy()))
+    np.save(d / "scenario_ids.npy", ids.astype(np.float64))
+
+
 def main():
     args = parse()
     # --gpus N: the driver launches N ranks itself (torch.distributed.run, WORLD_SIZE
@@ -397,8 +437,10 @@ def main():
         elapsed = max(per_rank["elapsed_s"])                  # the max over ranks
     if world == 1:
         g = leg["hist"]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(leg["out"], args.dump_outputs)     # rank 0's shard: global ids 0..B-1
     verify = None
-    if rank == 0 and args.verify > 0:
+    if rank == 0 and args.full and args.verify > 0:
         gd = {k: v.to(f"cuda:{local}") for k, v in g.items()}
         verify = _verify_gathered(ctl, cfg, world * B, K, W, gd, args.verify)
         del gd
@@ -463,7 +505,7 @@ def main():
                      "note": "elapsed_s: each rank's wall time of the K timed steps (barrier + synchronize "
                              "bracketed, gather included); value uses their max"},
     }
-    if not args.no_disturbed:
+    if args.full and not args.no_disturbed:
         gen = ScenarioGen(seed=20241220, first_id=rank * B, k0=0, sigma_w=args.sigma_w, sigma_omega=0.0,
                           jbs_spread=args.spread, wdep_spread=args.spread)
         dl = _run_leg(ctl, cfg, B, K, W, x0, rank, world, gen=gen)
@@ -481,7 +523,7 @@ def main():
             "warm_hit_rate": 1.0 - d["giruns"] / d["qps"], "optimal_frac": d["optimal_frac"],
             "flop_per_step": FL.per_step(N, args.mode, d["qps"], d["tries"], d["giruns"], d["Kgi"], d["qact"],
                                          d["sgen"])}
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         try:
             res["cpu_baseline"] = cpu_baseline(N, args.mode, args.cpu_seconds)
         except Exception as e:  # pragma: no cover

@@ -1,9 +1,9 @@
 # Copy the outputs of one round-end GPU pass (tools/gpu_round.sh + gpu_dist.sh +
-# the N = 50 diag_phases runs + prof_mfma.sh, all under gpurun_out/) into
+# the N = 50 diag_phases runs + prof_mfma.sh, all under ${OUT_DIR:-out}/) into
 # profiles/ under the round's tag:   bash tools/collect_profiles.sh r03
 set -e
 T=${1:?round tag}
-G=gpurun_out
+G=${OUT_DIR:-out}
 P=profiles
 cp $G/bench_cpu.json $P/${T}_bench.json
 cp $G/bench.json $P/${T}_bench_20steps.json

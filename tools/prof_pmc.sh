@@ -1,10 +1,10 @@
 # SQ instruction-mix / wait counters of the step kernel (separate --pmc passes,
 # kernel trace only; B=1e5, one warmup + one timed step), reduced by sq_parse.py.
-# Results: gpurun_out/pmc/
+# Results: ${OUT_DIR:-out}/pmc/
 set -o pipefail
 R=$GRAFT_REPO_ROOT
 TAG=${TAG:-r01}
-OUT=$R/gpurun_out/pmc
+OUT=$R/${OUT_DIR:-out}/pmc
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 A="--steps 1 --warmup 1 --no-cpu --no-disturbed --verify 0"

@@ -4,7 +4,7 @@
 set -o pipefail
 R=$GRAFT_REPO_ROOT
 TAG=${TAG:-r01}
-OUT=$R/gpurun_out/prof_$TAG
+OUT=$R/${OUT_DIR:-out}/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT -o ktrace --output-format csv -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu --no-disturbed --verify 0 > $OUT/bench_under_rocprof.json 2> $OUT/ktrace.err || exit $?
