@@ -2060,6 +2060,20 @@ struct StructRows {
         return gmaxi<P>(bad) == 0;
     }
 
+    // The certificate's primal tolerance on the input bounds.  A bound's slack V_l - lo
+    // is exact (an active bound's is zero), so the runtime-N kernels hold it to
+    // Goldfarb-Idnani's own stopping tolerance: with the 1e-9 of the general rows they
+    // certified a set that left a variable free 2.8e-10 of the largest input outside
+    // its bound, 1.2e-10 umax off the optimum (N = 49 mode 2,
+    // tests/test_gpu_config_space.py).  The compiled horizons keep 1e-9: with 1e-12
+    // the N = 20 far kernel measured 10% slower (6.34 -> 6.99 ms per step-batch, A/B on
+    // one box) and the N = 50 mode-3 closed loops left the oracle's
+    template <class W>
+    __device__ static constexpr double bound_tol() { return W::kNN == 0 ? 1e-12 : 1e-9; }
+    __device__ bool is_bound_row(int id, int N) const {
+        return mode == NTM_MODE_BOX || (id < 6 * N && id % 6 < 2);
+    }
+
     // Most violated inactive row (verify = false), or, with verify = true,
     // whether EVERY row has slack >= -tol * max(vmax, |bc|) (returned in .p).
     // Rows flagged kCandRow (the rows of a warm-start candidate that failed
@@ -2073,8 +2087,8 @@ struct StructRows {
         if (mode == NTM_MODE_NONE) { Pick none; none.p = verify ? 0 : -1; none.s = 0.0; none.bc = 0.0; return none; }
         double bv = kInf, bs = 0.0, bbc = 0.0;
         int bid = 0x7fffffff, bad = 0;
-        auto consider = [&](double s, int id, double bcv) {
-            if (verify) { bad |= s < -1e-9 * fmax(vmax, fabs(bcv)); return; }
+        auto consider = [&](double s, int id, double bcv, double vtol = 1e-9) {
+            if (verify) { bad |= s < -vtol * fmax(vmax, fabs(bcv)); return; }
             const unsigned char fl = w.aflag()[id];
             constexpr unsigned char kOut = (W::kNN > 32 || W::kNN == 0) ? (kActiveRow | kSkipRow) : kActiveRow;
             if (fl & kOut) return;
@@ -2093,8 +2107,8 @@ struct StructRows {
             }
             int idl = (mode == NTM_MODE_BOX) ? l : 6 * l;
             int idh = (mode == NTM_MODE_BOX) ? N + l : 6 * l + 1;
-            consider(Vl - lo, idl, lo);
-            consider(hi - Vl, idh, -hi);
+            consider(Vl - lo, idl, lo, bound_tol<W>());
+            consider(hi - Vl, idh, -hi, bound_tol<W>());
         }
         if (has_rate() && l >= 1 && l < N) {                 // rate rows on lane j
             const double ir = w.idun()[l];
@@ -4847,7 +4861,9 @@ __device__ __forceinline__ int qp_phase(const Prob& pb, const W& w, double x0, d
                         NTM_WSYNC();
                         if (l < cq) w.aflag()[w.act()[l]] = 0;
                         NTM_WSYNC();
-                        if (pk.p < 0 || !(pk.s < -1e-9 * fmax(vmx, fabs(pk.bc)))) {
+                        // (an input bound counts as violated from the certificate's tolerance on)
+                        const double ptol = (pk.p >= 0 && rows.is_bound_row(pk.p, N)) ? rows.template bound_tol<W>() : 1e-9;
+                        if (pk.p < 0 || !(pk.s < -ptol * fmax(vmx, fabs(pk.bc)))) {
                             // the only violated rows left are skipped ones (A + {p} had a
                             // non-finite end point: p nearly depends on A): GI's step for a
                             // dependent row, the dual-only direction of the last skipped row p

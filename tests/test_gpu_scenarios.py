@@ -34,7 +34,7 @@ def dev_gen(g: O.ScenarioGen, **kw):
 def test_step_teacher_forced_with_generator(ctl, N, mode, warm):
     """Each scenario's own plasma in the model and the plant, plus step k's
     disturbance at time index k (gen.k0 = k), identical inputs every step."""
-    _teacher_forced(ctl, N, mode, warm, k_sim=6, gen=GEN)
+    _teacher_forced(ctl, N, mode, warm, k_sim=6 if N < 50 else 4, gen=GEN)
 
 
 def test_step_teacher_forced_with_omega_disturbance(ctl):
