@@ -394,6 +394,24 @@ __device__ __forceinline__ int gmaxi(int v) {
     if constexpr (P >= 64) { int a, b; pair_i<32>(v, a, b); v = max(a, b); }
     return uni<P>(v);
 }
+// Predicate collectives: does any / every lane of the group hold p?  One v_cmp
+// into a lane mask instead of gmaxi's six dependent DPP steps.  P = 64: the
+// wave's ballot, a scalar result (so the branch it feeds is a scalar branch);
+// P < 64: the ballot masked to the lane's own group.  Same contract as the
+// reductions above: group-uniform control flow, all P lanes of the group active
+// (lanes of other groups may be inactive: their ballot bits are masked off).
+template <int P>
+__device__ __forceinline__ unsigned long long group_mask() {
+    if constexpr (P == 64) return ~0ull;
+    else return ((1ull << P) - 1ull) << ((threadIdx.x & 63) & ~(P - 1));
+}
+template <int P>
+__device__ __forceinline__ bool gany(bool p) {
+    if constexpr (P == 64) return __ballot(p) != 0ull;
+    else return (__ballot(p) & group_mask<P>()) != 0ull;
+}
+template <int P>
+__device__ __forceinline__ bool gall(bool p) { return !gany<P>(!p); }
 // broadcast lane `src` of the group (src group-uniform)
 template <int P>
 __device__ __forceinline__ double gbcast(double v, int src) {
@@ -441,10 +459,29 @@ __device__ __forceinline__ void gargmin(double& v, int& id, double& a, double& b
     a = uni<P>(a);
     b = uni<P>(b);
 }
+// the same without payloads (same comparison, same tie rule: smaller id)
+__device__ __forceinline__ void amin_sel(double& v, int& id, double ov, int oid) {
+    if (ov < v || (ov == v && oid < id)) { v = ov; id = oid; }
+}
+template <int S>
+__device__ __forceinline__ void amin_pair(double& v, int& id) {
+    double v0, v1;
+    int i0, i1;
+    pair_d<S>(v, v0, v1);
+    pair_i<S>(id, i0, i1);
+    v = v0; id = i0;
+    amin_sel(v, id, v1, i1);
+}
 template <int P>
 __device__ __forceinline__ void gargmin(double& v, int& id) {
-    double a = 0.0, b = 0.0;
-    gargmin<P>(v, id, a, b);
+    amin_sel(v, id, dpp_d<0xB1>(v), dpp_i<0xB1>(id));
+    amin_sel(v, id, dpp_d<0x4E>(v), dpp_i<0x4E>(id));
+    if constexpr (P >= 8) amin_sel(v, id, dpp_d<0x141>(v), dpp_i<0x141>(id));
+    if constexpr (P >= 16) amin_sel(v, id, dpp_d<0x140>(v), dpp_i<0x140>(id));
+    if constexpr (P >= 32) amin_pair<16>(v, id);
+    if constexpr (P >= 64) amin_pair<32>(v, id);
+    v = uni<P>(v);
+    id = uni<P>(id);
 }
 
 // ---------------------------------------------------------------------------
@@ -1748,7 +1785,7 @@ __device__ __forceinline__ int diag_scale_phase(const Prob& pb, const W& w, int 
             NTM_WSYNC();
         }
         NTM_ACC(ST_SC_ROW, tsc);
-        const int code = fold_const<W>() ? gmaxi<P>(bad ? 2 : infe) : (gmaxi<P>(bad) != 0 ? 2 : 0);
+        const int code = gany<P>(bad != 0) ? 2 : ((fold_const<W>() && gany<P>(infe != 0)) ? 1 : 0);
         NTM_ACC(ST_SC_END, tsc);
         return code;
     }
@@ -1888,7 +1925,7 @@ __device__ __forceinline__ int diag_scale_phase(const Prob& pb, const W& w, int 
         NTM_WSYNC();
     }
     NTM_ACC(ST_SC_ROW, tsc);
-    const int code = fold_const<W>() ? gmaxi<P>(bad ? 2 : infe) : (gmaxi<P>(bad) != 0 ? 2 : 0);
+    const int code = gany<P>(bad != 0) ? 2 : ((fold_const<W>() && gany<P>(infe != 0)) ? 1 : 0);
     NTM_ACC(ST_SC_END, tsc);
     return code;
 }
@@ -1914,7 +1951,7 @@ __device__ __forceinline__ bool full_gram(const Prob& pb, const W& w, int l) {
         bad = scale_gram<P>(w, w.R(), l);
     }
     NTM_WSYNC();
-    return gmaxi<P>(bad) == 0;
+    return !gany<P>(bad != 0);
 }
 
 // kept for the dense-row entry point (ntm_qp_device): G~ = D G D in place,
@@ -1934,7 +1971,7 @@ __device__ __forceinline__ bool scale_phase(const W& w, int l, bool /*with_state
         w.F()[l] = f;
     }
     NTM_WSYNC();
-    return gmaxi<P>(bad) == 0;
+    return !gany<P>(bad != 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -2057,6 +2094,15 @@ struct StructRows {
                 }
             }
         }
+        // (kept as the DPP reduction, with load_candidates' two in ntm_step.h: with all
+        // three as ballots the far N = 20 kernel returned wrong plans for 20 of 64
+        // scenarios, and turning any one of them back gave the parent's results bit for
+        // bit; so did the all-ballot source built without the N = 20 TU's scheduler
+        // flag or with SGPR spills to memory: code generation, not the source, and not
+        // located further.  Once per QP / per step: nothing to gain here.
+        // Any change to these kernels is checked by the byte-equal A/B of the benchmark's
+        // dumped outputs against the parent (profiles/r07_ab/bitwise.txt), not only by
+        // the tolerance tests)
         return gmaxi<P>(bad) == 0;
     }
 
@@ -2143,7 +2189,7 @@ struct StructRows {
         }
         Pick pk;
         if (verify) {
-            pk.p = gmaxi<P>(bad);
+            pk.p = gany<P>(bad != 0) ? 1 : 0;
             pk.s = 0.0;
             pk.bc = 0.0;
             return pk;
@@ -2215,7 +2261,7 @@ struct DenseRows {
         }
         Pick pk;
         if (verify) {
-            pk.p = gmaxi<P>(bad);
+            pk.p = gany<P>(bad != 0) ? 1 : 0;
             pk.s = 0.0;
             pk.bc = 0.0;
             return pk;
@@ -2460,7 +2506,7 @@ __device__ __forceinline__ int gi_solve(const W& w, const Rows rows, bool has_ro
             }
             const double uabs = gmax<P>(l < q ? fabs(u) : 0.0);
             const double umin = -gmax<P>(l < q ? -u : -kInf);
-            okw = !(umin < -1e-9 * fmax(1.0, uabs)) && gmaxi<P>((l < N && !isfinite(v)) ? 1 : 0) == 0;
+            okw = !(umin < -1e-9 * fmax(1.0, uabs)) && !gany<P>(l < N && !isfinite(v));
             if (!okw) {
                 NTM_CNT(CN_WARM_NEG);
                 // the added rows whose multipliers are >= 0: the caller's second warm pass
@@ -2786,7 +2832,8 @@ __device__ __forceinline__ bool polish_phase(const Prob& pb, const W& w, const R
             vfin = fixed ? vb : vl;
         }
     }
-    ok = gmaxi<P>(ok ? 0 : 1) == 0;
+    // ok is group-uniform already: chol_inplace decides on a broadcast pivot, and
+    // the collectives of the solves above ran under it
     if (ok && Gsave) {
         // One step of fixed-precision iterative refinement on the KKT residual with
         // the same factors.  The range-space solve goes through L = chol(G~_FF),
@@ -2841,7 +2888,7 @@ __device__ __forceinline__ bool polish_phase(const Prob& pb, const W& w, const R
         }
         const double dv = bwd_lanes<P>(w.R(), w.ldi(), N, 1, LD, dt, l);
         const double vr = fixed ? vb : vfin + dv;
-        ok = gmaxi<P>((l < N && !isfinite(vr)) ? 1 : 0) == 0;
+        ok = !gany<P>(l < N && !isfinite(vr));
         if (ok) vfin = vr;
     }
     if (ok) {
@@ -2893,8 +2940,9 @@ __device__ __forceinline__ bool polish_phase(const Prob& pb, const W& w, const R
             has = true;
         }
         double mabs = gmax<P>(has ? fabs(mval) : 0.0);
-        double mmin = -gmax<P>(has ? -mval : -kInf);
-        ok = ok && !(mmin < -1e-9 * fmax(1.0, mabs));
+        // the smallest multiplier only feeds this comparison: a predicate per lane
+        // (a NaN multiplier compares false here, as fmax dropped it from the minimum)
+        ok = ok && !gany<P>(has && mval < -1e-9 * fmax(1.0, mabs));
     }
     if (verify_only && !ok) {
         if (l < N) w.V()[l] = Vgi;
@@ -2926,6 +2974,10 @@ __device__ __forceinline__ bool polish_phase(const Prob& pb, const W& w, const R
 // slack on every row, multiplier signs).  Writes w.U()/w.V() on success or
 // when !verify_only (then GI's V is kept); returns success.
 // ---------------------------------------------------------------------------
+// fail_kind / fail_pos (optional): after a FAILED certificate, its kind (1 dual, 2
+// primal, 3 singular, 4 both) and the active-list position of the most negative
+// multiplier (kinds 1, 2, 4).  fail_pos is defined only then: a certified set runs
+// no argmin and leaves 0 there, so a caller must not read it on success.
 // mult_out (optional, LDS): every active row's multiplier (GI form, n'V >= bc rows),
 // by active position, written when the certificate's multipliers are formed.
 // dir_p >= 0 (the certified dual path of qp_phase): no solve at all.  The active
@@ -2956,9 +3008,11 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
         rows.decode(id, N, kind, j);
         if (kind < 2) {                                   // u bound: Lin = -+e_j, b = -umin / umax
             fixj = j;
-            double lv = kind == 0 ? -1.0 : 1.0;
-            ufix = rows.bval(w, id) / lv;
-            nfix = -((lv * w.D()[j]) / w.D()[j]);
+            // lv = -+1: b / lv is -+b exactly, and -((lv D_j) / D_j) is -lv exactly (D_j
+            // is finite and non-zero: a non-finite scale left with NTM_EXIT_NONFINITE)
+            const double bv = rows.bval(w, id);
+            ufix = kind == 0 ? -bv : bv;
+            nfix = kind == 0 ? 1.0 : -1.0;
         } else if (kind >= 4) {                           // rate row: Lin = sg (e_j - e_{j-1})
             isgen = 1;
             srow = 2 * N + j;                             // general-row code >= 2N: rate row j
@@ -3008,8 +3062,7 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
     // two active rows fixing one variable (only a caller-supplied candidate can
     // do that; GI never adds a dependent row) cannot be certified: reject; so is a
     // set holding a constant row
-    const bool collide =
-        gmaxi<P>((l < q && !isgen && (constrow || w.fx()[fixj] != (unsigned char)(l + 1))) ? 1 : 0) != 0;
+    const bool collide = gany<P>(l < q && !isgen && (constrow || w.fx()[fixj] != (unsigned char)(l + 1)));
     const bool fixed = (l < N) && w.fx()[l];
     const double uf = fixed ? w.Uf()[l] : 0.0;
     const double vb = fixed ? uf / w.D()[l] : 0.0;
@@ -3462,7 +3515,7 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
                 acz3 -= et * zt3;
             }
         }
-        ok = gmaxi<P>((l < n && !(isfinite(x) && isfinite(zz) && isfinite(zz2) && isfinite(zz3))) ? 1 : 0) == 0;
+        ok = !gany<P>(l < n && !(isfinite(x) && isfinite(zz) && isfinite(zz2) && isfinite(zz3)));
         // V_0 (pivots from E_p V_p = h, fixed values, 0 on the non-pivot columns) and Z
         const bool hole = fpos == nc || (kCollision && nc2 >= 0 && fpos == nc2) || (kColl3 && nc3 >= 0 && fpos == nc3);
         const int rk = hole ? 0
@@ -4264,7 +4317,7 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
                     const int lr = l + r * P;
                     if (lr >= nF && lr < nt) good = good && isfinite(w.np()[lr - nF] - xr[r]);
                 }
-                good = gmaxi<P>(good ? 0 : 1) == 0;
+                good = !gany<P>(!good);
                 if (good) {
                     vfin = vr;
 #pragma unroll
@@ -4279,14 +4332,22 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
                 continue;
             }
         }
+        // A fixed variable's multiplier res / hv, once.  hv is exactly -+1 for a
+        // variable fixed by an input bound (classification above), so the quotient is
+        // +-res bit for bit; only a single-entry state row (|hv| != 1) needs the IEEE
+        // division: one ballot and a group-uniform branch
+        const double hvl = fixed ? w.hv()[l] : 1.0;
+        double lamf;
+        if (gany<P>(fixed && fabs(hvl) != 1.0)) lamf = res / hvl;
+        else lamf = hvl > 0.0 ? res : -res;
         if (mult_out) {                                    // by active position
             if (l < nS) mult_out[w.sidx()[l]] = w.np()[l];
-            if (fixed) mult_out[w.fx()[l] - 1] = res / w.hv()[l];
+            if (fixed) mult_out[w.fx()[l] - 1] = lamf;
         }
 #ifdef NTM_STAMPS
         if (!dir) {                                        // non-finite multipliers, by re-solve path
-            const int nanm = gmaxi<P>(((l < nS && !isfinite(w.np()[l])) || (fixed && !isfinite(res / w.hv()[l]))) ? 1 : 0);
-            const int nanv = gmaxi<P>((l < N && !isfinite(vfin)) ? 1 : 0);
+            const bool nanm = gany<P>((l < nS && !isfinite(w.np()[l])) || (fixed && !isfinite(lamf)));
+            const bool nanv = gany<P>(l < N && !isfinite(vfin));
             if (nanm) {
                 if (!sq) NTM_CNT(CN_NAN_BORD);
                 else if (xb2 >= 0) NTM_CNT(CN_NAN_COLL2);
@@ -4300,7 +4361,7 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
         }
 #endif
         if (dir) {
-            ok = gmaxi<P>(((l < nS && !isfinite(w.np()[l])) || (fixed && !isfinite(res / w.hv()[l]))) ? 1 : 0) == 0;
+            ok = !gany<P>((l < nS && !isfinite(w.np()[l])) || (fixed && !isfinite(lamf)));
             fk = ok ? 0 : 3;
             break;
         }
@@ -4312,21 +4373,36 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
         if (l < nS) { mval = w.np()[l]; mpos = w.sidx()[l]; has = true; }
         if (!(fabs(mval) < kInf)) mval = -1e300;         // a non-finite multiplier fails the dual check
         if (fixed) {
-            double lam = res / w.hv()[l];
+            double lam = lamf;
             if (!(fabs(lam) < kInf)) lam = -1e300;
             if (!has || lam < mval) { mval = lam; mpos = w.fx()[l] - 1; }
             has = true;
         }
         double mabs = gmax<P>(has ? fabs(mval) : 0.0);
-        double mkey = has ? mval : kInf;
-        gargmin<P>(mkey, mpos);
-        const bool dual_ok = !(mkey < -1e-9 * fmax(1.0, mabs));
+        // The dual test is a predicate over the lanes' own multipliers: the smallest
+        // one is below the threshold iff some lane's is (the key of a lane without a
+        // multiplier was +inf, non-finite ones are -1e300 already).  The argmin's
+        // position is read by the callers only after a failed certificate (the drop
+        // position, or the slot an exchange overwrites), so it runs only then
+        const bool dual_ok = !gany<P>(has && mval < -1e-9 * fmax(1.0, mabs));
         fk = !ok ? (dual_ok ? 2 : 4) : (!dual_ok ? 1 : 0);
-        fpos_out = mpos;
+        if (fail_pos && !(ok && dual_ok)) {
+            double mkey = has ? mval : kInf;
+            gargmin<P>(mkey, mpos);
+            fpos_out = mpos;
+        }
         ok = ok && dual_ok;
         break;
     }
-    ok = gmaxi<P>(ok ? 0 : 1) == 0;
+    // ok needs no further reduction here, at any P: it is the certificate loop's own
+    // condition, and that loop runs collectives (gmax, the check, the ballots), so it
+    // was group-uniform on entry; inside the loop it is only assigned results of
+    // collectives (the primal check's pick, the multipliers' finiteness, dual_ok).
+    // Before the loop, the solves set it from scalars that are bit-identical across
+    // the group: sums out of gsum (det, h11, num, den, the plane systems' terms) and
+    // pivots out of gbcast (dk), besides collide and the substitution's ballot.  The
+    // old reduction was also a safety net at P < 64 against a future per-lane term;
+    // whoever adds one must reduce it where it is formed
     NTM_ACC(ST_P_KKT, tp);
     if (fail_kind) *fail_kind = uni<P>(fk);
     if (fail_pos) *fail_pos = uni<P>(fpos_out);

@@ -69,6 +69,9 @@ __device__ __forceinline__ void load_candidates(const Prob& pb, const W& w, int6
         if (!bad) {
             int lb = 0;
             if (l < q) lb = (c[l] < 0 || c[l] >= nrows) ? 1 : 0;
+            // the DPP reduction on purpose here and below, not a gany ballot: see
+            // StructRows::feasible_const (ntm_device.h) and DESIGN.md §10; a change is
+            // checked by the byte-equal A/B of profiles/r07_ab/bitwise.txt
             bad = gmaxi<P>(lb) != 0;
         }
         if (!bad) {
