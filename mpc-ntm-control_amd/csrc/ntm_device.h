@@ -965,12 +965,161 @@ __device__ __forceinline__ void axpy_sub(double* a, const double* b, double f, i
             if (j0 + u < hi) a[(j0 + u) * sa] = x[u] - f * z[u];
     }
 }
-// Gamma_r v restricted to j <= r/2 (row r of the packed block-lower-triangular Gamma)
-template <int CH, class W>
+// ---------------------------------------------------------------------------
+// Lane-masked accumulation (N = 20, one scenario per wave, row or column =
+// lane).  The triangular passes over the packed Gamma sum N fixed terms per
+// lane and zero the ones outside the lane's row or column with a select (two
+// v_cndmask and a v_cmp per fp64 term).  The lanes a term belongs to are
+// contiguous and known at compile time (lanes >= 2j for the term j of a row
+// pass, lanes <= i for the term i of a column pass), so the one accumulating
+// instruction runs with EXEC narrowed to them instead: a lane that is off keeps
+// its accumulator, which is what y + (+-0) leaves for any y other than -0.0.
+//   Row dots (v_fmac_f64; a row's own terms come first, the masked ones after):
+// the two forms differ on a lane the term does not belong to when x is not
+// finite (NaN from 0 x against y untouched) and when y is -0.0 there (+0.0 from
+// -0.0 + 0 against -0.0); never on a lane the term belongs to.
+//   Column passes (v_add_f64 of a term formed on every lane; the select form adds
+// +0.0, never a product with 0): a column's masked terms come first, onto the
+// +0.0 the sum starts from, so no accumulator is -0.0 where a term is masked
+// and the two forms are identical, whatever the data.
+//   Measured on the far N = 20 kernel at B = 1e5 (A/B on one box, three runs
+// each): the row dots 6.057 -> 5.962 ms per step-batch, the certificate's
+// gradient and the scaling pass's column pass on top 5.949 -> 5.772 ms; the
+// scaling pass's row pass (masked adds of the squares, the last / cnt tracking
+// left select-based) 5.762 -> 5.792 ms: not kept.  qdot_rows' callers take the
+// column from fidx[], not from the lane, so it keeps its selects.
+// One asm block per chunk of five terms: EXEC is saved on entry, every mask is
+// ANDed with the saved value (lanes off on entry stay off), only SALU builds
+// the masks (s_lshl_b64 / s_lshr_b64 from -1), and EXEC is restored before the
+// block ends.  Wait states: a SALU write of EXEC needs none before a VALU (the
+// sequence the compiler emits for every divergent branch), nor does a VALU
+// write of an SGPR pair before the SALU that reads it (v_cmp then s_and); the
+// blocks have no DPP, lane access, v_div_fmas, EXECZ / VCCZ read or memory
+// instruction, the cases the ISA lists for EXEC and VALU-written SGPRs.
+// After a block: the compiler's hazard pass does not see the block's last VALU
+// write, and a DPP read of that VGPR needs two wait states; the restoring
+// s_mov_b64 is one, the s_nop 0 behind it the second, so whatever the scheduler
+// places next (a DPP or lane read of the sum included) is covered.
+// ---------------------------------------------------------------------------
+template <int P, int CH, class W>
+__device__ __forceinline__ constexpr bool lane_masked_ok() {
+    // row r / column l sits on lane r / l: one scenario per wave, 2N <= 64, one trip of `r += P`.
+    // The far build only: its chunks hold five terms, which is what the asm blocks are written
+    // for; the all-LDS builds batch four terms per round trip (ntm_n20near.hip) and run their
+    // scaling pass split over idle lanes
+    return P == 64 && CH == 5 && W::kNN == 20 && W::kFar;
+}
+// EXEC = entry EXEC & (lanes >= s<k>) / (lanes <= 63 - s<k>), s<k> a compile-time shift
+#define NTM_LANES_FROM(k) "s_lshl_b64 %[m], -1, %[s" #k "]\n\ts_and_b64 exec, %[sv], %[m]\n\t"
+#define NTM_LANES_UPTO(k) "s_lshr_b64 %[m], -1, %[s" #k "]\n\ts_and_b64 exec, %[sv], %[m]\n\t"
+#define NTM_SHIFTS_FROM(J0) \
+    [s0] "n"(2 * (J0)), [s1] "n"(2 * (J0) + 2), [s2] "n"(2 * (J0) + 4), [s3] "n"(2 * (J0) + 6), [s4] "n"(2 * (J0) + 8)
+#define NTM_SHIFTS_UPTO(I0) \
+    [s0] "n"(63 - (I0)), [s1] "n"(62 - (I0)), [s2] "n"(61 - (I0)), [s3] "n"(60 - (I0)), [s4] "n"(59 - (I0))
+#define NTM_V5(n, a) [n##0] "v"(a[0]), [n##1] "v"(a[1]), [n##2] "v"(a[2]), [n##3] "v"(a[3]), [n##4] "v"(a[4])
+// y += g[u] x[u] on lanes >= 2 (J0 + u), u = 0..4 in order, one v_fmac_f64 each
+template <int J0>
+__device__ __forceinline__ void fmac5_lanes_from(double& y, const double (&g)[5], const double (&x)[5]) {
+    unsigned long long sv, m;
+#define NTM_TERM(k) NTM_LANES_FROM(k) "v_fmac_f64_e32 %[y], %[g" #k "], %[x" #k "]\n\t"
+    asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_TERM(0) NTM_TERM(1) NTM_TERM(2) NTM_TERM(3) NTM_TERM(4)
+                 "s_mov_b64 exec, %[sv]\n\ts_nop 0"
+                 : [y] "+v"(y), [sv] "=&s"(sv), [m] "=&s"(m)
+                 : NTM_V5(g, g), NTM_V5(x, x), NTM_SHIFTS_FROM(J0)
+                 : "scc");
+#undef NTM_TERM
+}
+// the same for two accumulators that share g and the masks: y1 += g x1, then y2 += g x2, per term
+template <int J0>
+__device__ __forceinline__ void fmac5x2_lanes_from(double& y1, double& y2, const double (&g)[5],
+                                                   const double (&x1)[5], const double (&x2)[5]) {
+    unsigned long long sv, m;
+#define NTM_TERM(k) \
+    NTM_LANES_FROM(k) "v_fmac_f64_e32 %[y1], %[g" #k "], %[a" #k "]\n\tv_fmac_f64_e32 %[y2], %[g" #k "], %[b" #k "]\n\t"
+    asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_TERM(0) NTM_TERM(1) NTM_TERM(2) NTM_TERM(3) NTM_TERM(4)
+                 "s_mov_b64 exec, %[sv]\n\ts_nop 0"
+                 : [y1] "+v"(y1), [y2] "+v"(y2), [sv] "=&s"(sv), [m] "=&s"(m)
+                 : NTM_V5(g, g), NTM_V5(a, x1), NTM_V5(b, x2), NTM_SHIFTS_FROM(J0)
+                 : "scc");
+#undef NTM_TERM
+}
+// s += t[u] on lanes <= I0 + u (column pass), one v_add_f64 each
+template <int I0>
+__device__ __forceinline__ void fadd5_lanes_upto(double& s, const double (&t)[5]) {
+    unsigned long long sv, m;
+#define NTM_TERM(k) NTM_LANES_UPTO(k) "v_add_f64 %[y], %[y], %[t" #k "]\n\t"
+    asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_TERM(0) NTM_TERM(1) NTM_TERM(2) NTM_TERM(3) NTM_TERM(4)
+                 "s_mov_b64 exec, %[sv]\n\ts_nop 0"
+                 : [y] "+v"(s), [sv] "=&s"(sv), [m] "=&s"(m)
+                 : NTM_V5(t, t), NTM_SHIFTS_UPTO(I0)
+                 : "scc");
+#undef NTM_TERM
+}
+// The scaling pass's column terms on lanes <= I0 + u: s += t[u], fs += tf[u], and the
+// lanes on which g0[u] or g1[u] is an infinity or a NaN ORed into the lane mask nf
+// (v_cmp_class under the narrowed EXEC writes zeros for the lanes that are off)
+template <int I0>
+__device__ __forceinline__ void fadd5x2_class_lanes_upto(double& s, double& fs, unsigned long long& nf,
+                                                         const double (&t)[5], const double (&tf)[5],
+                                                         const double (&g0)[5], const double (&g1)[5]) {
+    unsigned long long sv, m, c;
+    const int cls = 0x207;                                // signalling / quiet NaN, -inf, +inf
+#define NTM_TERM(k)                                                                                       \
+    NTM_LANES_UPTO(k) "v_cmp_class_f64_e64 %[c], %[p" #k "], %[cls]\n\ts_or_b64 %[nf], %[nf], %[c]\n\t" \
+                      "v_cmp_class_f64_e64 %[c], %[q" #k "], %[cls]\n\ts_or_b64 %[nf], %[nf], %[c]\n\t" \
+                      "v_add_f64 %[y], %[y], %[t" #k "]\n\tv_add_f64 %[z], %[z], %[u" #k "]\n\t"
+    asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_TERM(0) NTM_TERM(1) NTM_TERM(2) NTM_TERM(3) NTM_TERM(4)
+                 "s_mov_b64 exec, %[sv]\n\ts_nop 0"
+                 : [y] "+v"(s), [z] "+v"(fs), [nf] "+s"(nf), [sv] "=&s"(sv), [m] "=&s"(m), [c] "=&s"(c)
+                 : NTM_V5(t, t), NTM_V5(u, tf), NTM_V5(p, g0), NTM_V5(q, g1), [cls] "s"(cls), NTM_SHIFTS_UPTO(I0)
+                 : "scc");
+#undef NTM_TERM
+}
+#undef NTM_LANES_FROM
+#undef NTM_LANES_UPTO
+#undef NTM_SHIFTS_FROM
+#undef NTM_SHIFTS_UPTO
+#undef NTM_V5
+// chunk J0 / 5 of row `lane`'s dot(s): the batched loads at compile-time offsets, then the masked terms
+template <int J0, class W>
+__device__ __forceinline__ void gamma_row_chunk_lanes(const W& w, const double* gr, const double* v, double& y) {
+    double g[5], x[5];
+#pragma unroll
+    for (int u = 0; u < 5; ++u) {
+        g[u] = gr[w.gidx(0, J0 + u)];
+        x[u] = v[J0 + u];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    fmac5_lanes_from<J0>(y, g, x);
+}
+template <int J0, class W>
+__device__ __forceinline__ void gamma_row_chunk2_lanes(const W& w, const double* gr, const double* v1,
+                                                       const double* v2, double& y1, double& y2) {
+    double g[5], x1[5], x2[5];
+#pragma unroll
+    for (int u = 0; u < 5; ++u) {
+        g[u] = gr[w.gidx(0, J0 + u)];
+        x1[u] = v1[J0 + u];
+        x2[u] = v2[J0 + u];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    fmac5x2_lanes_from<J0>(y1, y2, g, x1, x2);
+}
+
+// Gamma_r v restricted to j <= r/2 (row r of the packed block-lower-triangular Gamma).
+// P = 64 is passed where the caller's row is its lane (`for (r = l; r < 2N; r += P)`):
+// the N = 20 far kernel then masks the terms by lane (lane_masked_ok)
+template <int CH, int P = 0, class W>
 __device__ __forceinline__ double gamma_row_dot(const W& w, int r, const double* v) {
-    const int n = w.n(), jm = r >> 1;
     const double* gr = w.Gt() + r;                        // gt(r, j) = gr[gidx(0, j)]
     double y = 0.0;
+    if constexpr (lane_masked_ok<P, CH, W>()) {
+        gamma_row_chunk_lanes<0>(w, gr, v, y);
+        gamma_row_chunk_lanes<5>(w, gr, v, y);
+        gamma_row_chunk_lanes<10>(w, gr, v, y);
+        gamma_row_chunk_lanes<15>(w, gr, v, y);
+    } else {
+    const int n = w.n(), jm = r >> 1;
     NTM_CHUNK_PRAGMA
     for (int j0 = 0; j0 < n; j0 += CH) {
         double g[CH], x[CH];
@@ -988,17 +1137,24 @@ __device__ __forceinline__ double gamma_row_dot(const W& w, int r, const double*
             y += (j <= jm ? g[u] : 0.0) * x[u];
         }
     }
+    }
     return y;
 }
 
 // Gamma_r v1 and Gamma_r v2 in one pass over row r (its loads shared)
-template <int CH, class W>
+template <int CH, int P = 0, class W>
 __device__ __forceinline__ void gamma_row_dot2(const W& w, int r, const double* v1, const double* v2, double& y1,
                                                double& y2) {
-    const int n = w.n(), jm = r >> 1;
     const double* gr = w.Gt() + r;
     y1 = 0.0;
     y2 = 0.0;
+    if constexpr (lane_masked_ok<P, CH, W>()) {
+        gamma_row_chunk2_lanes<0>(w, gr, v1, v2, y1, y2);
+        gamma_row_chunk2_lanes<5>(w, gr, v1, v2, y1, y2);
+        gamma_row_chunk2_lanes<10>(w, gr, v1, v2, y1, y2);
+        gamma_row_chunk2_lanes<15>(w, gr, v1, v2, y1, y2);
+    } else {
+    const int n = w.n(), jm = r >> 1;
     NTM_CHUNK_PRAGMA
     for (int j0 = 0; j0 < n; j0 += CH) {
         double g[CH], x1[CH], x2[CH];
@@ -1017,6 +1173,7 @@ __device__ __forceinline__ void gamma_row_dot2(const W& w, int r, const double* 
             y1 += gm * x1[u];
             y2 += gm * x2[u];
         }
+    }
     }
 }
 
@@ -1462,6 +1619,39 @@ __device__ __forceinline__ double dot_rows2(const double* a, const double* c, in
     }
     return s;
 }
+// chunk I0 / 5 of column `lane`'s sum: the batched loads at compile-time offsets, the
+// terms formed on every lane, then added on the lanes <= i
+template <int I0>
+__device__ __forceinline__ void dot_rows2_chunk_lanes(const double* a, const double* c, double& s) {
+    double a0[5], a1[5], c0[5], c1[5], t[5];
+#pragma unroll
+    for (int u = 0; u < 5; ++u) {
+        const int i = I0 + u;
+        a0[u] = a[2 * i];
+        a1[u] = a[2 * i + 1];
+        c0[u] = c[2 * i];
+        c1[u] = c[2 * i + 1];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < 5; ++u) t[u] = a0[u] * c0[u] + a1[u] * c1[u];
+    fadd5_lanes_upto<I0>(s, t);
+}
+// dot_rows2 with imin = the caller's lane (column l on lane l < N): the N = 20 far
+// kernel masks the terms by lane (lane_masked_ok)
+template <int CH, int P, class W>
+__device__ __forceinline__ double dot_rows2(const W&, const double* a, const double* c, int n, int imin) {
+    if constexpr (lane_masked_ok<P, CH, W>()) {
+        double s = 0.0;
+        dot_rows2_chunk_lanes<0>(a, c, s);
+        dot_rows2_chunk_lanes<5>(a, c, s);
+        dot_rows2_chunk_lanes<10>(a, c, s);
+        dot_rows2_chunk_lanes<15>(a, c, s);
+        return s;
+    } else {
+        return dot_rows2<CH>(a, c, n, imin);
+    }
+}
 
 // ---------------------------------------------------------------------------
 // Gram of Gamma columns on the matrix cores (long horizons): for the columns
@@ -1641,6 +1831,32 @@ __device__ __forceinline__ int scale_gram(const W& w, double* G, int l) {
 // while config 2 (0.201 -> 0.199 ms) and config 5 (74.2 -> 73.7 ms) gained.
 template <class W>
 __device__ __forceinline__ constexpr bool fold_const() { return !(W::kFar && W::kNN == 20); }
+// Lane-masked chunk of the scaling pass's column pass (lane_masked_ok: column l on lane l),
+// stages I0..I0+4 of column `lane`: the terms of G_ll and F_l formed on every lane, added
+// on the lanes <= i, the non-finite Gamma entries of those lanes into nf
+template <int I0, class OM>
+__device__ __forceinline__ void scale_col_chunk_lanes(const OM& qw, const double* cj, const double* om, double& s,
+                                                      double& fs, unsigned long long& nf) {
+    double ga[5], gb[5], ea[5], eb[5], t[5], tf[5];
+#pragma unroll
+    for (int u = 0; u < 5; ++u) {
+        const int i = I0 + u;
+        ga[u] = cj[2 * i];
+        gb[u] = cj[2 * i + 1];
+        ea[u] = om[2 * i];
+        eb[u] = om[2 * i + 1];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < 5; ++u) {
+        const double g0 = ga[u], g1 = gb[u];
+        const double o0 = qw.o0(g0, g1);
+        const double o1 = qw.o1(g0, g1);
+        t[u] = g0 * o0 + g1 * o1;
+        tf[u] = g0 * ea[u] + g1 * eb[u];
+    }
+    fadd5x2_class_lanes_upto<I0>(s, fs, nf, t, tf, ga, gb);
+}
 template <int P, class W>
 __device__ __forceinline__ int diag_scale_phase(const Prob& pb, const W& w, int l, bool with_state_rows,
                                                 double x0 = 0.0, double x1 = 0.0, const ColSums* cs = nullptr) {
@@ -1799,6 +2015,13 @@ __device__ __forceinline__ int diag_scale_phase(const Prob& pb, const W& w, int 
             s = cs->s;
             fs = cs->f;
             bad |= cs->bad;
+        } else if constexpr (lane_masked_ok<P, CH, W>()) {   // terms i < l masked by lane
+            unsigned long long nf = 0ull;
+            scale_col_chunk_lanes<0>(qw, cj, om, s, fs, nf);
+            scale_col_chunk_lanes<5>(qw, cj, om, s, fs, nf);
+            scale_col_chunk_lanes<10>(qw, cj, om, s, fs, nf);
+            scale_col_chunk_lanes<15>(qw, cj, om, s, fs, nf);
+            bad |= (int)((nf >> l) & 1ull);
         } else {
         NTM_CHUNK_PRAGMA
         for (int i0 = 0; i0 < N; i0 += CH) {     // fixed trip count, terms i < l masked; batched loads
@@ -2176,7 +2399,7 @@ struct StructRows {
                         // fixed trip count, entries j > jmax masked.  The packed reads stay
                         // inside Gt: gidx(0, j) + r = j(2N-j-1) + r < N(N+1)
                         (void)gr;
-                        xh = gamma_row_dot<NTM_CH>(w, r, w.U());
+                        xh = gamma_row_dot<NTM_CH, P>(w, r, w.U());
                     }
                     const double er = w.e()[r];
                     xh += er;
@@ -3102,7 +3325,7 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
         }
     } else if constexpr (!kLateY) {
         for (int r = l; r < 2 * N && !dir; r += P) {
-            const double y = gamma_row_dot<NTM_CH>(w, r, w.dr());
+            const double y = gamma_row_dot<NTM_CH, P>(w, r, w.dr());
             w.Phi()[r] = y;
             w.xp()[r] = allfixed ? y : y + w.e()[r] - ((r & 1) ? pb.r[1] : pb.r[0]);
         }
@@ -3543,10 +3766,10 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
             NTM_WSYNC();
             for (int r = l; r < 2 * N; r += P) {
                 double ya, yb;
-                gamma_row_dot2<NTM_CH>(w, r, w.U(), w.d(), ya, yb);
+                gamma_row_dot2<NTM_CH, P>(w, r, w.U(), w.d(), ya, yb);
                 w.xp()[r] = ya;
                 w.Phi()[r] = yb;
-                y2s[r] = gamma_row_dot<NTM_CH>(w, r, w.dr());
+                y2s[r] = gamma_row_dot<NTM_CH, P>(w, r, w.dr());
             }
             NTM_WSYNC();
             double g1 = 0.0, g2 = 0.0, h11 = 0.0, h12 = 0.0, h22 = 0.0;
@@ -3697,7 +3920,7 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
             } else {
                 for (int r = l; r < 2 * N; r += P) {
                     double ya, yb;
-                    gamma_row_dot2<NTM_CH>(w, r, w.U(), w.d(), ya, yb);
+                    gamma_row_dot2<NTM_CH, P>(w, r, w.U(), w.d(), ya, yb);
                     w.xp()[r] = ya;
                     w.Phi()[r] = yb;                             // scratch (hs_of is done with it)
                 }
@@ -4035,7 +4258,7 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
                 gamma_rows_split<NTM_CH, 1>(w, {w.U()}, y, l);
                 if (l < 2 * N) w.xp()[l] = y[0];
             } else {
-                for (int r = l; r < 2 * N; r += P) w.xp()[r] = gamma_row_dot<NTM_CH>(w, r, w.U());
+                for (int r = l; r < 2 * N; r += P) w.xp()[r] = gamma_row_dot<NTM_CH, P>(w, r, w.U());
             }
             NTM_WSYNC();
         }
@@ -4083,7 +4306,7 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
         if constexpr (kSplitC) g2c = gamma_col_split<NTM_CH>(w, omy, l);
         if (l < N) {
             const double* cl = w.Gt() + w.gidx(2 * l, l) - 2 * l;
-            const double g2 = kSplitC ? g2c : dot_rows2<NTM_CH>(cl, omy, N, l);      // terms i < l masked
+            const double g2 = kSplitC ? g2c : dot_rows2<NTM_CH, P>(w, cl, omy, N, l);   // terms i < l masked
             double gu = 2 * g2;
             if constexpr (ru_on<W>()) gu = gu + 2 * pb.Ru * w.U()[l];  // + 2 Ru U_l
             res = w.D()[l] * gu + w.F()[l];
