@@ -194,77 +194,20 @@ enum { ST_LIFT, ST_COST, ST_SCALE, ST_CAND, ST_REGRAM, ST_GI, ST_POLISH, ST_ROLL
        CN_CDPX_NAN, CN_NAN_BORD, CN_NAN_K0, CN_NAN_K1, CN_NAN_K2, CN_NAN_COLL, CN_NAN_COLL2, CN_NAN_PRIMFAIL,
        CN_NAN_V, CN_BX_O1, CN_BX_O2, CN_BX_O3P, CN_BX_NEG, CN_BX_NOCLASS, CN_CDP_SKIP, CN_CDP_SKIPDIR };
 constexpr double kDepTol = 1e-8;   // GI linear-dependence threshold (oracle GI_DEP_TOL)
-#ifndef NTM_MAX_NT
-#define NTM_MAX_NT 32
-#endif
-constexpr int kMaxNT = NTM_MAX_NT; // explicit R^{-1} in GI up to this horizon (WS::useT)
-#ifndef NTM_REPAIRS
-#define NTM_REPAIRS 8
-#endif
-constexpr int kRepairs = NTM_REPAIRS;
-// NTM_CDP=1: a failed candidate continues on Goldfarb-Idnani's dual path with certified
+constexpr int kMaxNT = 32;         // explicit R^{-1} in GI up to this horizon (WS::useT)
+// a failed candidate continues on Goldfarb-Idnani's dual path with certified
 // re-solves (qp_phase); up to N + kCdpExtra re-solves before GI itself takes over
-#ifndef NTM_CDP
-#define NTM_CDP 1
-#endif
-#ifndef NTM_CDP_EXTRA
-#define NTM_CDP_EXTRA 8
-#endif
-constexpr int kCdpExtra = NTM_CDP_EXTRA;
-#ifndef NTM_SPLIT_SCALE
-#define NTM_SPLIT_SCALE 1
-#endif
-#ifndef NTM_SPLIT_FAR
-#define NTM_SPLIT_FAR 0
-#endif
-#ifndef NTM_SPLIT_PRAGMA
-#define NTM_SPLIT_PRAGMA NTM_CHUNK_PRAGMA
-#endif
-// The re-solve's Gamma passes split over idle lanes (gamma_rows_split /
-// gamma_col_split; N = 20): bit 0 the row passes (Gamma U_B, the k = 1 line's
-// Gamma U_0 and Gamma D Z, the certificate's Gamma U), bit 1 the certificate's
-// gradient column pass.  NTM_SPLIT_CERT for the all-LDS build, _FAR for the far one
-#ifndef NTM_SPLIT_CERT
-#define NTM_SPLIT_CERT 0
-#endif
-#ifndef NTM_SPLIT_CERT_FAR
-#define NTM_SPLIT_CERT_FAR 0
-#endif
-// the dual path's skip of a row whose A + {p} end point is non-finite (long horizons)
-#ifndef NTM_CDP_SKIP
-#define NTM_CDP_SKIP 1
-#endif
-#ifndef NTM_FUSE_LOCAL_E
-#define NTM_FUSE_LOCAL_E 0 // 1: the fused column sums run the free-response recursion on every lane
-#endif
+constexpr int kCdpExtra = 8;
 #ifndef NTM_SUB_PRESCALE
 #define NTM_SUB_PRESCALE 0 // 1: long horizons, echelon substitutions on accumulators scaled by 1/E[l][l] (slower)
 #endif
 #ifndef NTM_MU_AHEAD
 #define NTM_MU_AHEAD 0     // long horizons: steps ahead the multipliers' back substitution loads E (0: none)
 #endif
-#ifndef NTM_SUB_AHEAD
-#define NTM_SUB_AHEAD 1    // long horizons: steps ahead the echelon forward substitution loads E
-#endif
 #ifndef NTM_SUB_LANEIDX
 #define NTM_SUB_LANEIDX 0  // 1: the certificate's sparse pass takes rows and z by readlane (long horizons;
 #endif                     // on in the mode-3 TU: 76.9 -> 76.3 ms, while mode 2 ran 64.9 -> 65.6 ms)
-#ifndef NTM_E_LANEIDX
-#define NTM_E_LANEIDX 1    // row-per-lane E build: pivot columns' variables and D_j by readlane
-#endif
-#ifndef NTM_CY_LATE
-#define NTM_CY_LATE 1      // long horizons: Gamma U_B at an echelon set's general rows only (polish_compact)
-#endif
-#ifndef NTM_CDP_SKIPDIR
-#define NTM_CDP_SKIPDIR 1  // long horizons: no violated row but skipped ones -> the last one's dual-only step
-#endif
-#ifndef NTM_CDP_HINT
-#define NTM_CDP_HINT 1
-#endif
-#ifndef NTM_BOX_REPAIRS
-#define NTM_BOX_REPAIRS 16
-#endif
-constexpr int kBoxRepairs = NTM_BOX_REPAIRS;   // box-only QPs: single-row exchanges before GI (qp_phase)   // also at N = 50: 16 / 32 were no faster in mode 2, 6% / 10% slower in mode 3
+constexpr int kBoxRepairs = 16;   // box-only QPs: single-row exchanges before GI (qp_phase)   // also at N = 50: 16 / 32 were no faster in mode 2, 6% / 10% slower in mode 3
 // A constant row (Lin_i = 0: the x_0 rows of getWLc, state rows Gamma doesn't
 // reach) is violated when b_i < -kConstTol (D22, oracle CONST_ROW_TOL): the same
 // absolute 1e-9 the KKT certificate allows on a unit-scale row.  An exact test
@@ -525,15 +468,6 @@ __device__ __forceinline__ double coef_b(const Coef& k, double r3) { return k.bc
 #ifndef NTM_FAR_N20
 #define NTM_FAR_N20 1
 #endif
-#ifndef NTM_FAR_JB
-#define NTM_FAR_JB 0         // columns per trip of the bordered elimination's loads in the far block (0: two, loaded as used)
-#endif
-#ifndef NTM_GI_LDS
-#define NTM_GI_LDS 3         // far layouts: GI's G~ / L (bit 0) and R (bit 1) in the LDS E block (WS::gr)
-#endif
-#ifndef NTM_FAR_COLMAJOR
-#define NTM_FAR_COLMAJOR 0   // 1: J, T and the bordered factor column-major in the far block (slower)
-#endif
 __host__ __device__ constexpr bool ws_far(int NN) { return NN > 32 || (NTM_FAR_N20 && NN == 20); }
 // The slim far layout (N = 20 far, round 5): 16 scenarios per CU (4 waves per SIMD,
 // <= 10,240 B of LDS each) instead of 12.  What leaves LDS: the A/B coefficient
@@ -544,26 +478,17 @@ __host__ __device__ constexpr bool ws_far(int NN) { return NN > 32 || (NTM_FAR_N
 // diagonal reciprocals of the bordered factor and GI's Cholesky (ldi / kdi), which
 // move to the far block with the rate-row norms (idun, mode 3 never runs here).
 // The Om products are the identity (qi_on), so the certificate's Om y is y itself.
-#ifndef NTM_SLIM20
-#define NTM_SLIM20 1
-#endif
-#ifndef NTM_SLIM50
-#define NTM_SLIM50 1
-#endif
 // The slim N = 50 layout (round 5): 4 scenarios per CU (one wave on each SIMD) instead
 // of 3, <= 40,960 B each.  Besides the N = 20 slim changes (its Om is general: the
 // certificate's Om y goes to the 2N of scratch), rho, U_old and the two carried
 // active sets move to the far block (touched once or twice per LPV iteration).
 __host__ __device__ constexpr bool ws_slim(int N, bool far) {
-    return far && ((NTM_SLIM20 && N == 20) || (NTM_SLIM50 && N == 50));
+    return far && (N == 20 || N == 50);
 }
 __host__ __device__ constexpr bool slim_far(int N, bool far) { return ws_slim(N, far) && N == 50; }
-// NTM_SLIM_AB: the slim layout keeps a11 / a21 in LDS after all (2N doubles, paid for by
+// the slim N = 20 layout keeps a11 / a21 in LDS after all (2N doubles, paid for by
 // active-row flags for the 6N+4 getWLc rows only: mode 3 never runs on these kernels)
-#ifndef NTM_SLIM_AB
-#define NTM_SLIM_AB 1
-#endif
-__host__ __device__ constexpr int slim_ab(int N, bool far) { return NTM_SLIM_AB && N == 20 && ws_slim(N, far) ? 2 : 0; }
+__host__ __device__ constexpr int slim_ab(int N, bool far) { return N == 20 && ws_slim(N, far) ? 2 : 0; }
 
 template <int NN, bool GEN = false, bool FAR = ws_far(NN)>
 struct WS {
@@ -626,20 +551,13 @@ struct WS {
         if constexpr (kFar) return far;   // never dereferenced: far layouts keep no T (useT)
         else return base + oT();
     }
-    // element (r, c) of J (and of T) at J()[r jr() + c jc()]: row-major in LDS,
-    // column-major in HBM (kFar), where the common access, each lane walking its own
-    // row, is then one coalesced load per column instead of 64 cache lines
-    static constexpr bool kCol = kFar && NTM_FAR_COLMAJOR;
-    __device__ __forceinline__ int jr() const { return kCol ? 1 : ldj(); }
-    __device__ __forceinline__ int jc() const { return kCol ? ldj() : 1; }
+    // element (r, c) of J (and of T) at J()[r jr() + c jc()]: row-major
+    __device__ __forceinline__ int jr() const { return ldj(); }
+    __device__ __forceinline__ int jc() const { return 1; }
     // packed bordered KKT factor (rows 0..nt, row nt the right-hand side), entry
-    // (r, c), c <= r, at J()[brow(r) + bcol(c, nt)]: row-major (row r at r(r+1)/2) in
-    // LDS, column-major (column c at c(nt+1) - c(c-1)/2) in HBM, where a lane owns a
-    // row and the elimination walks the columns
-    __device__ __forceinline__ int brow(int r) const { return kCol ? r : (r * (r + 1)) / 2; }
-    __device__ __forceinline__ int bcol(int c, int nt) const {
-        return kCol ? c * (nt + 1) - (c * (c - 1)) / 2 - c : c;
-    }
+    // (r, c), c <= r, at J()[brow(r) + bcol(c, nt)]: row-major (row r at r(r+1)/2)
+    __device__ __forceinline__ int brow(int r) const { return (r * (r + 1)) / 2; }
+    __device__ __forceinline__ int bcol(int c, int /*nt*/) const { return c; }
     // echelon re-solve: sorted E (entry (t, u), u <= t, at Ep()[eidx(t, u)]) and the
     // GI's triangular factor R (and, before it, the scaled Gram G~ and its Cholesky
     // factor L): element (i, j) at R()[i + j ldj()], or, in the far layouts
@@ -652,11 +570,9 @@ struct WS {
     // that a drop's upper-Hessenberg subdiagonal (i+1, i) does not collide with it.
     // N(N+1)/2 + N-1 doubles <= the E block's N(N+1)/2 + N+1.  GI's back and forward
     // substitutions, adds and drops then run on LDS instead of the HBM far block
-    // (J stays there)
-    // (NTM_GI_LDS bit 0: G~ and L, bit 1: R; the two phases never overlap, so each
-    // may live in either place)
-    static constexpr bool kGiLdsL = FAR && (NTM_GI_LDS & 1);
-    static constexpr bool kGiLds = FAR && (NTM_GI_LDS & 2);
+    // (J stays there).  kGiLdsL: G~ and L; kGiLds: R
+    static constexpr bool kGiLdsL = FAR;
+    static constexpr bool kGiLds = FAR;
     __device__ __forceinline__ int gio(int i, int j) const {
         if (i >= j) return (i * (i + 1)) / 2 + j;
         if (i == j - 1) return (n() * (n() + 1)) / 2 + i;
@@ -770,8 +686,8 @@ __host__ __device__ constexpr int ws_bytes_rows(int N, int rows, bool far = fals
 __host__ __device__ constexpr int ws_bytes(int N, bool far = false) {
     return ws_bytes_rows(N, slim_ab(N, far) ? 6 * N + 4 : 8 * N + 4, far);
 }
-static_assert(!ws_slim(20, true) || 16 * ws_bytes(20, true) <= 160 * 1024, "slim N = 20: 16 scenarios per CU");
-static_assert(!ws_slim(50, true) || 4 * ws_bytes(50, true) <= 160 * 1024, "slim N = 50: 4 scenarios per CU");
+static_assert(16 * ws_bytes(20, true) <= 160 * 1024, "slim N = 20: 16 scenarios per CU");
+static_assert(4 * ws_bytes(50, true) <= 160 * 1024, "slim N = 50: 4 scenarios per CU");
 
 // s: the scenario's index in the launch (its far block, when the WS has one)
 template <int NN, bool GEN = false, bool FAR = ws_far(NN)>
@@ -1178,95 +1094,6 @@ __device__ __forceinline__ void gamma_row_dot2(const W& w, int r, const double* 
 }
 
 // ---------------------------------------------------------------------------
-// Row and column passes over Gamma split in two halves on otherwise idle lanes
-// (compile-time horizons with 4N - 2H <= 64, H = ceil(N/2): N = 20), as the
-// all-LDS build's scaling pass does (diag_scale_phase).  Row pass: lane l < 2N
-// sums the j < H terms of row r = l; lane 2N <= l < 4N - 2H the j >= H terms of
-// row r = l - 2N + 2H (the rows r >= 2H, the only ones that have such terms);
-// row r's value, (first half) + (second half), ends on lane r.  Column pass:
-// lane l < N takes stages i < H of column l, lane N + l stages i >= H; column
-// l's value ends on lane l.  The wave runs H trips instead of N.
-// ---------------------------------------------------------------------------
-template <int P, class W>
-__device__ __forceinline__ constexpr bool split_ok() {
-    return P == 64 && W::kNN > 0 && 4 * W::kNN - 2 * ((W::kNN + 1) / 2) <= 64;
-}
-// (Gamma_r v_k for the NV vectors v_k) on lane r < 2N
-template <int CH, int NV, class W>
-__device__ __forceinline__ void gamma_rows_split(const W& w, const double* const (&v)[NV], double (&y)[NV], int l) {
-    constexpr int NN = W::kNN, H = (NN + 1) / 2;
-    const bool lo = l < 2 * NN, hi = !lo && l < 4 * NN - 2 * H;
-    const int r = lo ? l : (hi ? l - 2 * NN + 2 * H : 0);
-    const int jb = lo ? 0 : H, jm = r >> 1;
-    const double* gr = w.Gt() + r;                        // gt(r, j) = gr[gidx(0, j)]
-    double s[NV];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) s[k] = 0.0;
-    if (lo || hi) {
-        NTM_SPLIT_PRAGMA
-        for (int u0 = 0; u0 < H; u0 += CH) {
-            double g[CH], x[NV][CH];
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                const int j = jb + u0 + u;
-                const bool in = u0 + u < H && j < NN;
-                g[u] = in ? gr[w.gidx(0, j)] : 0.0;
-#pragma unroll
-                for (int k = 0; k < NV; ++k) x[k][u] = in ? v[k][j] : 0.0;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                const int j = jb + u0 + u;
-                const double gm = (u0 + u < H && j <= jm) ? g[u] : 0.0;
-#pragma unroll
-                for (int k = 0; k < NV; ++k) s[k] += gm * x[k][u];
-            }
-        }
-    }
-    const int src = (l >= 2 * H && l < 2 * NN) ? l + 2 * NN - 2 * H : l;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const double s2 = __shfl(s[k], src & 63, 64);
-        y[k] = (src != l) ? s[k] + s2 : s[k];
-    }
-}
-// sum_{i >= l} Gamma_{2i,l} c_{2i} + Gamma_{2i+1,l} c_{2i+1} on lane l < N
-template <int CH, class W>
-__device__ __forceinline__ double gamma_col_split(const W& w, const double* c, int l) {
-    constexpr int NN = W::kNN, H = (NN + 1) / 2;
-    const bool lo = l < NN, hi = !lo && l < 2 * NN;
-    const int col = lo ? l : (hi ? l - NN : 0);
-    const int ib = lo ? 0 : H;
-    const double* cl = w.Gt() + w.gidx(2 * col, col) - 2 * col;   // cl[r] = gt(r, col), r >= 2 col
-    double s = 0.0;
-    if (lo || hi) {
-        NTM_SPLIT_PRAGMA
-        for (int u0 = 0; u0 < H; u0 += CH) {
-            double a0[CH], a1[CH], c0[CH], c1[CH];
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                const int i = ib + u0 + u;
-                const bool in = u0 + u < H && i < NN;
-                a0[u] = in ? cl[2 * i] : 0.0;
-                a1[u] = in ? cl[2 * i + 1] : 0.0;
-                c0[u] = in ? c[2 * i] : 0.0;
-                c1[u] = in ? c[2 * i + 1] : 0.0;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                const int i = ib + u0 + u;
-                const double t = a0[u] * c0[u] + a1[u] * c1[u];
-                s += (u0 + u < H && i >= col && i < NN) ? t : 0.0;
-            }
-        }
-    }
-    const double s2 = __shfl(s, (l + NN) & 63, 64);
-    return lo ? s + s2 : s;
-}
-
-// ---------------------------------------------------------------------------
 // L2: lifted prediction  (Rho_to_PhiGammaLambda.m:17-52, CANON D4/D6)
 // ---------------------------------------------------------------------------
 // Literal-reference lift (D4 / D6; generic kernels only, the host dispatches any
@@ -1326,13 +1153,7 @@ __device__ __forceinline__ void lift_literal(const Prob& pb, const W& w, const C
     NTM_WSYNC();
 }
 
-#ifndef NTM_ROW_PAIRS
-#define NTM_ROW_PAIRS 0    // 1: long horizons, the scaling pass's row norms two rows per lane (slower)
-#endif
-#ifndef NTM_FUSE_COLSUM
-#define NTM_FUSE_COLSUM 1  // the lift accumulates the scaling pass's column sums (ColSums): bit 0
-#endif                     // long horizons (N = 50), bit 1 the far N = 20 kernel, bit 2 the all-LDS N = 20 one
-// The scaling pass's column sums, accumulated by the slim lift (NTM_FUSE_COLSUM):
+// The scaling pass's column sums, accumulated by the slim lift at long horizons:
 // lane l < N walks Gamma's column l stage by stage, so it can add G_ll's and F_l's
 // terms as it produces them (the free response e_i is lane N's value at the same
 // stage, read by readlane), instead of the scaling pass reading the column back
@@ -1346,9 +1167,8 @@ struct ColSums {
 };
 template <class W>
 __device__ __forceinline__ constexpr bool fuse_colsum() {
-    if constexpr (W::kSlim) return W::kNN > 32 ? (NTM_FUSE_COLSUM & 1) != 0 : (NTM_FUSE_COLSUM & 2) != 0;
-    // the all-LDS N = 20 build (lanes N, N+1 and N+2 hold Phi's columns and Lambda)
-    else return !W::kFar && W::kNN == 20 && (NTM_FUSE_COLSUM & 4) != 0;
+    if constexpr (W::kSlim) return W::kNN > 32;   // N = 50: on; the far N = 20 kernel: off
+    else return false;                            // the all-LDS N = 20 build and the generic kernels: off
 }
 
 template <int P, class W>
@@ -1385,14 +1205,9 @@ __device__ __forceinline__ void lift_phase(const Prob& pb, const W& w, int l, do
             double cs_s = 0.0, cs_f = 0.0;
             int cs_bad = 0;
             const OmQ<qi_on<W>()> cq(pb.Q);
-            // NTM_FUSE_LOCAL_E: every lane runs lane N's free-response recursion itself (the
-            // same operations on the same coefficients), so e_i needs no lane read per stage
-            constexpr bool kLocalE = fuse_colsum<W>() && NTM_FUSE_LOCAL_E;
-            double ee0 = kLocalE ? (a0 * x0 + k.C1) : 0.0;
-            double ee1 = kLocalE ? ((c0v * x0 + k.a22 * x1) + k.C2) : 0.0;
             auto col_terms = [&](int i) {
                 if constexpr (fuse_colsum<W>()) {
-                    const double e0 = kLocalE ? ee0 : gbcast<P>(g0, N), e1 = kLocalE ? ee1 : gbcast<P>(g1, N);
+                    const double e0 = gbcast<P>(g0, N), e1 = gbcast<P>(g1, N);
                     const double d0 = e0 - pb.r[0], d1 = e1 - pb.r[1];
                     const double ea = cq.o0(d0, d1), eb = cq.o1(d0, d1);
                     const double o0 = cq.o0(g0, g1), o1 = cq.o1(g0, g1);
@@ -1433,12 +1248,6 @@ __device__ __forceinline__ void lift_phase(const Prob& pb, const W& w, int l, do
                         const int at = live ? i : l;
                         rec[2 * at] = g0;
                         rec[2 * at + 1] = g1;
-                        if constexpr (kLocalE) {
-                            const double m0 = ca[u] * ee0 + k.C1;
-                            const double m1 = (cb[u] * ee0 + k.a22 * ee1) + k.C2;
-                            ee0 = m0;
-                            ee1 = m1;
-                        }
                         col_terms(i);
                     }
                 }
@@ -1486,31 +1295,6 @@ __device__ __forceinline__ void lift_phase(const Prob& pb, const W& w, int l, do
             rec[st * i + 1] = g1;
         };
         put(gam ? l : 0);
-        // stage i's terms of the scaling pass's column sums (ColSums): e_i = Phi_i x_k +
-        // Lambda_i from lanes N, N+1 (Phi's columns) and N+2 (Lambda), free_response's
-        // expressions
-        double cs_s = 0.0, cs_f = 0.0;
-        int cs_bad = 0;
-        const OmQ<qi_on<W>()> cq(pb.Q);
-        auto col_terms = [&](int i) {
-            if constexpr (fuse_colsum<W>()) {
-                const double p00 = gbcast<P>(g0, N), p10 = gbcast<P>(g1, N);
-                const double p01 = gbcast<P>(g0, N + 1), p11 = gbcast<P>(g1, N + 1);
-                const double l0 = gbcast<P>(g0, N + 2), l1 = gbcast<P>(g1, N + 2);
-                const double e0 = (p00 * x0 + p01 * x1) + l0;
-                const double e1 = (p10 * x0 + p11 * x1) + l1;
-                const double d0 = e0 - pb.r[0], d1 = e1 - pb.r[1];
-                const double ea = cq.o0(d0, d1), eb = cq.o1(d0, d1);
-                const double o0 = cq.o0(g0, g1), o1 = cq.o1(g0, g1);
-                const double t = g0 * o0 + g1 * o1;
-                const double tf = g0 * ea + g1 * eb;
-                const bool on = gam && i >= l;
-                if (on) cs_bad |= !isfinite(g0) || !isfinite(g1);
-                cs_s += on ? t : 0.0;
-                cs_f += on ? tf : 0.0;
-            }
-        };
-        col_terms(0);
         // fixed trip count (unrolls), branch-free: Gamma rows i <= l keep (B_l, 0) and
         // rewrite the diagonal.  The coefficients of CH steps are loaded ahead of the
         // chunk's stores (the stores cannot be proven not to alias them, so per-step
@@ -1536,11 +1320,9 @@ __device__ __forceinline__ void lift_phase(const Prob& pb, const W& w, int l, do
                     g0 = live ? n0 : g0;
                     g1 = live ? n1 : g1;
                     put(live ? i : l);
-                    col_terms(i);
                 }
             }
         }
-        if (cs) { cs->s = cs_s; cs->f = cs_f; cs->bad = cs_bad; }
     }
     NTM_ACC(ST_L_LOOP, tlf);
     // Phi and Lambda on lane 0 when the group has no idle lanes
@@ -1667,23 +1449,8 @@ __device__ __forceinline__ double dot_rows2(const W&, const double* a, const dou
 // called in wave-uniform control flow.
 // ---------------------------------------------------------------------------
 typedef double ntm_d4 __attribute__((ext_vector_type(4)));
-#ifndef NTM_MFMA_FF
-#define NTM_MFMA_FF 0      // the re-solve's compact G~_FF (bordered path): measured slower, off
-#endif
-#ifndef NTM_PLANE
-#define NTM_PLANE 1        // k = 2 echelon sets on the null-space path (long horizons, generic kernels)
-#endif
-#ifndef NTM_COLL2
-#define NTM_COLL2 1        // square sets with two collisions on the null-space path (long horizons, generic)
-#endif
 #ifndef NTM_COLL3
 #define NTM_COLL3 1        // k = 2 sets with one collision (three holes) on the null-space path (round 6)
-#endif
-#ifndef NTM_ROWE_ALL
-#define NTM_ROWE_ALL 0     // 1: the echelon re-solve builds E one sorted row per lane at every horizon
-#endif
-#ifndef NTM_MFMA_FULL
-#define NTM_MFMA_FULL 1    // GI's full G~
 #endif
 template <int NN, class W, class ColOf, class Put>
 __device__ __forceinline__ void gram_mfma(const Prob& pb, const W& w, int nc, ColOf col_of, Put put, int l) {
@@ -1745,7 +1512,7 @@ __device__ __forceinline__ void gram_mfma(const Prob& pb, const W& w, int nc, Co
 template <int P, class W, class Put>
 __device__ __forceinline__ void gram_rows_put(const Prob& pb, const W& w, Put put, int l) {
     const int N = w.n();
-    if constexpr (NTM_MFMA_FULL && W::kNN > 32 && P == 64) {   // the matrix cores (gram_mfma)
+    if constexpr (W::kNN > 32 && P == 64) {   // the matrix cores (gram_mfma)
         gram_mfma<W::kNN>(pb, w, N, [](int a) { return a; }, [&](int j, int kk, double sg) { put(j, kk, 2 * sg); },
                           l);
         return;
@@ -1885,31 +1652,24 @@ __device__ __forceinline__ int diag_scale_phase(const Prob& pb, const W& w, int 
     // B = 1024: 0.208 -> 0.199 ms; mode 2 at B = 1024: 0.545 -> 0.526 ms).  The far
     // build's register allocation does not absorb it: 6.36 -> 7.98 ms per step-batch
     // at B = 1e5 with the chunk unroll, 6.41 ms without; the column pass alone 7.11 ms,
-    // the row pass alone 9.66 ms (A/B on one box, NTM_SPLIT_FAR)
+    // the row pass alone 9.66 ms (A/B on one box)
     constexpr int NNs = W::kNN, Hs = (NNs + 1) / 2;
-    constexpr bool kSplit = NTM_SPLIT_SCALE && P == 64 && NNs > 0 && 4 * NNs - 2 * Hs <= 64;
-    // NTM_SPLIT_FAR (far build): bit 0 the column pass, bit 1 the row pass
-    constexpr bool kSC = kSplit && (!W::kFar || (NTM_SPLIT_FAR & 1));
-    constexpr bool kSR = kSplit && (!W::kFar || (NTM_SPLIT_FAR & 2));
-    constexpr int TC = kSC ? Hs : NNs, TR = kSR ? Hs : NNs;   // trips of each pass
-    if constexpr (kSC || kSR) {
+    constexpr bool kSplit = !W::kFar && P == 64 && NNs > 0 && 4 * NNs - 2 * Hs <= 64;
+    if constexpr (kSplit) {
         double s = 0.0, fs = 0.0;
         const int col = l < N ? l : l - N;
         const int base = l < N ? 0 : Hs;
-        const bool fc = fuse_colsum<W>() && cs != nullptr;   // summed by the lift (one sequential sum)
-        if (fc) {
-            if (l < N) { s = cs->s; fs = cs->f; bad |= cs->bad; }
-        } else if (l < (kSC ? 2 * N : N)) {
+        if (l < 2 * N) {
             const double* cj = w.Gt() + w.gidx(2 * col, col) - 2 * col;
             const double* om = w.xp();
             constexpr int CH = NTM_CH;
-            NTM_SPLIT_PRAGMA
-            for (int u0 = 0; u0 < TC; u0 += CH) {
+            NTM_CHUNK_PRAGMA
+            for (int u0 = 0; u0 < Hs; u0 += CH) {
                 double ga[CH], gb[CH], ea[CH], eb[CH];
 #pragma unroll
                 for (int u = 0; u < CH; ++u) {
                     const int i = base + u0 + u;
-                    const bool in = u0 + u < TC && i < N;
+                    const bool in = u0 + u < Hs && i < N;
                     ga[u] = in ? cj[2 * i] : 0.0;
                     gb[u] = in ? cj[2 * i + 1] : 0.0;
                     ea[u] = in ? om[2 * i] : 0.0;
@@ -1924,21 +1684,21 @@ __device__ __forceinline__ int diag_scale_phase(const Prob& pb, const W& w, int 
                     const double o1 = qw.o1(g0, g1);
                     const double t = g0 * o0 + g1 * o1;
                     const double tf = g0 * ea[u] + g1 * eb[u];
-                    const bool on = u0 + u < TC && i >= col && i < N;
+                    const bool on = u0 + u < Hs && i >= col && i < N;
                     if (on) bad |= !isfinite(g0) || !isfinite(g1);
                     s += on ? t : 0.0;
                     fs += on ? tf : 0.0;
                 }
             }
         }
-        const double s2 = (kSC && !fc) ? __shfl(s, (l + N) & 63, 64) : 0.0;
-        const double f2 = (kSC && !fc) ? __shfl(fs, (l + N) & 63, 64) : 0.0;
+        const double s2 = __shfl(s, (l + N) & 63, 64);
+        const double f2 = __shfl(fs, (l + N) & 63, 64);
         if (l < N) {
-            double g = (kSC && !fc) ? 2 * (s + s2) : 2 * s;
+            double g = 2 * (s + s2);
             if constexpr (ru_on<W>()) g = g + 2 * pb.Ru;   // G_ll + 2 Ru (ABI v5)
             const double Dl = (g > 0.0 && g < kInf) ? rsqrt_nr(g) : 1.0;
             w.D()[l] = Dl;
-            const double f = ((kSC && !fc) ? 2 * (fs + f2) : 2 * fs) * Dl;
+            const double f = (2 * (fs + f2)) * Dl;
             bad |= !isfinite(f) || !isfinite(Dl);
             w.F()[l] = f;
             if constexpr (!W::kSlim) {
@@ -1953,7 +1713,7 @@ __device__ __forceinline__ int diag_scale_phase(const Prob& pb, const W& w, int 
             w.idun()[l] = 1.0 / sqrt(a * a + b * b);
         }
         if (with_state_rows) {
-            const bool lo = l < 2 * N, hi = kSR && !lo && l < 4 * N - 2 * Hs;
+            const bool lo = l < 2 * N, hi = !lo && l < 4 * N - 2 * Hs;
             const int r = lo ? l : (hi ? l - 2 * N + 2 * Hs : 0);
             const int jb = lo ? 0 : Hs;
             const int jmax = r >> 1;
@@ -1961,13 +1721,13 @@ __device__ __forceinline__ int diag_scale_phase(const Prob& pb, const W& w, int 
             int last = -1, cnt = 0;
             if (lo || hi) {
                 constexpr int CH = NTM_CH;
-                NTM_SPLIT_PRAGMA
-                for (int u0 = 0; u0 < TR; u0 += CH) {
+                NTM_CHUNK_PRAGMA
+                for (int u0 = 0; u0 < Hs; u0 += CH) {
                     double g[CH], dd[CH];
 #pragma unroll
                     for (int u = 0; u < CH; ++u) {
                         const int j = jb + u0 + u;
-                        const bool in = u0 + u < TR && j < N;
+                        const bool in = u0 + u < Hs && j < N;
                         g[u] = in ? w.gt(r, j) : 0.0;
                         dd[u] = in ? w.D()[j] : 0.0;
                     }
@@ -1976,17 +1736,17 @@ __device__ __forceinline__ int diag_scale_phase(const Prob& pb, const W& w, int 
                     for (int u = 0; u < CH; ++u) {
                         const int j = jb + u0 + u;
                         const double v = g[u] * dd[u];
-                        const bool in = u0 + u < TR && j <= jmax;
+                        const bool in = u0 + u < Hs && j <= jmax;
                         rs += in ? v * v : 0.0;
                         if (in && g[u] != 0.0) { last = j; ++cnt; }
                     }
                 }
             }
             // the row's second half sits on lane 2N + r - 2H (rows r >= 2H)
-            const int src = (kSR && l >= 2 * Hs && l < 2 * N) ? l + 2 * N - 2 * Hs : l;
-            const double rs2 = kSR ? __shfl(rs, src & 63, 64) : 0.0;
-            const int last2 = kSR ? __shfl(last, src & 63, 64) : -1;
-            const int cnt2 = kSR ? __shfl(cnt, src & 63, 64) : 0;
+            const int src = (l >= 2 * Hs && l < 2 * N) ? l + 2 * N - 2 * Hs : l;
+            const double rs2 = __shfl(rs, src & 63, 64);
+            const int last2 = __shfl(last, src & 63, 64);
+            const int cnt2 = __shfl(cnt, src & 63, 64);
             if (lo) {
                 const bool two = src != l;
                 const double sr = two ? rs + rs2 : rs;
@@ -2070,52 +1830,7 @@ __device__ __forceinline__ int diag_scale_phase(const Prob& pb, const W& w, int 
         const double a = w.D()[l], b = w.D()[l - 1];
         w.idun()[l] = 1.0 / sqrt(a * a + b * b);
     }
-    // Long horizons (P < 2N <= 2P): lane l takes state rows l and l + P in one pass
-    // (both rows' loads of a chunk issued together, D_j loaded once) instead of two
-    // passes (NTM_ROW_PAIRS).  Each row's terms are summed in the same order as below.
-    constexpr bool kRowPairs = NTM_ROW_PAIRS && P == 64 && W::kNN > 32 && W::kNN <= 64;
-    if (kRowPairs && with_state_rows) {
-        const int r1 = l, r2 = l + P;
-        const bool two = r2 < 2 * N;
-        const int jmax1 = r1 >> 1, jmax2 = two ? (r2 >> 1) : -1;
-        double s1 = 0.0, s2 = 0.0;
-        int last1 = -1, cnt1 = 0, last2 = -1, cnt2 = 0;
-        constexpr int CH = NTM_CH;
-        NTM_CHUNK_PRAGMA
-        for (int j0 = 0; j0 < N; j0 += CH) {     // fixed trip count, j > jmax masked; batched loads
-            double g1[CH], g2[CH], dd[CH];
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                const int j = j0 + u;
-                g1[u] = j < N ? w.gt(r1, j) : 0.0;
-                g2[u] = (two && j < N) ? w.gt(r2, j) : 0.0;
-                dd[u] = j < N ? w.D()[j] : 0.0;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                const double v1 = g1[u] * dd[u], v2 = g2[u] * dd[u];
-                const bool in1 = j0 + u <= jmax1, in2 = j0 + u <= jmax2;
-                s1 += in1 ? v1 * v1 : 0.0;
-                s2 += in2 ? v2 * v2 : 0.0;
-                if (in1 && g1[u] != 0.0) { last1 = j0 + u; ++cnt1; }
-                if (in2 && g2[u] != 0.0) { last2 = j0 + u; ++cnt2; }
-            }
-        }
-        bad |= !isfinite(s1) || !isfinite(w.e()[r1]);
-        const double ir1 = (s1 > 0.0 && s1 < kInf) ? rsqrt_nr(s1) : 0.0;
-        w.irn()[r1] = ir1;
-        w.rinfo()[r1] = (last1 + 1) | (cnt1 > 1 ? kRowMulti : 0);
-        if (ir1 == 0.0) const_row(r1);
-        if (two) {
-            bad |= !isfinite(s2) || !isfinite(w.e()[r2]);
-            const double ir2 = (s2 > 0.0 && s2 < kInf) ? rsqrt_nr(s2) : 0.0;
-            w.irn()[r2] = ir2;
-            w.rinfo()[r2] = (last2 + 1) | (cnt2 > 1 ? kRowMulti : 0);
-            if (ir2 == 0.0) const_row(r2);
-        }
-        NTM_WSYNC();
-    } else if (with_state_rows) {
+    if (with_state_rows) {
         for (int r = l; r < 2 * N; r += P) {
             double s = 0.0;
             const int jmax = r >> 1;
@@ -3217,8 +2932,6 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
     const OmQ<qi_on<W>()> om(pb.Q);
     const bool dir = dir_p >= 0;
     const double Vprev = (l < N) ? w.V()[l] : 0.0;
-    constexpr int kSplitMask = split_ok<P, W>() ? (W::kFar ? NTM_SPLIT_CERT_FAR : NTM_SPLIT_CERT) : 0;
-    constexpr bool kSplitR = (kSplitMask & 1) != 0, kSplitC = (kSplitMask & 2) != 0;
     NTM_T0(tp);
     // --- classify active rows: single-entry rows fix a variable, the rest are general ---
     if (l < N) w.fx()[l] = 0;
@@ -3309,21 +3022,12 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
     // all-LDS and generic builds; the far N = 20 / 50 kernels keep one code path)
     constexpr bool kFixedY = !W::kFar;
     const bool allfixed = kFixedY && nF == 0 && nS == 0;
-    // Long horizons (NTM_CY_LATE): the pass runs after the set's shape is known; an
+    // Long horizons: the pass runs after the set's shape is known; an
     // echelon set needs Gamma_r U_B only at its active general rows (h), at most N < P
     // of them, so one trip over those rows replaces two over all 2N (z = y_B + e - r,
     // which only the bordered path's g_F reads, is not formed)
-    constexpr bool kLateY = NTM_CY_LATE && W::kNN > 32 && P == 64 && !kSplitR;
-    if constexpr (kSplitR) {
-        if (!dir) {
-            double y[1];
-            gamma_rows_split<NTM_CH, 1>(w, {w.dr()}, y, l);
-            if (l < 2 * N) {
-                w.Phi()[l] = y[0];
-                w.xp()[l] = allfixed ? y[0] : y[0] + w.e()[l] - ((l & 1) ? pb.r[1] : pb.r[0]);
-            }
-        }
-    } else if constexpr (!kLateY) {
+    constexpr bool kLateY = W::kNN > 32 && P == 64;
+    if constexpr (!kLateY) {
         for (int r = l; r < 2 * N && !dir; r += P) {
             const double y = gamma_row_dot<NTM_CH, P>(w, r, w.dr());
             w.Phi()[r] = y;
@@ -3367,8 +3071,8 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
     // Echelon sets with two spare columns (k = 2, round 5; long horizons): the certified
     // dual path passes through them after a drop from a k = 1 set; V = V_0 + w1 Z1 + w2 Z2
     // is minimised over the plane (a 2 x 2 system) instead of the bordered elimination
-    constexpr bool kPlane = kCollision && NTM_PLANE;
-    constexpr bool kColl2 = kCollision && NTM_COLL2;
+    constexpr bool kPlane = kCollision;
+    constexpr bool kColl2 = kCollision;   // square sets with two collisions on the null-space path
     // k = 2 with one collision (round 6): three holes and one row left out; the row
     // left out fixes one of the three spare directions, the cost is minimised over
     // the plane that remains (config 5 mode 3: 0.44 such sets per MPC step took the
@@ -3524,33 +3228,22 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
     const bool fused = kAlwaysFused || ((nt + 1 <= RPL * P) && (nt * (nt + 1) / 2 + nt <= N * LDJ + (N + 1) * LD));
     double* const Lp = w.J();
     if (!sq && fused && l < nF) Lp[w.brow(nt) + w.bcol(l, nt)] = -gl;
-    // --- compact G~_FF: one (a, c) entry per lane (packed rows, or lower col-major in R);
-    //     on the matrix cores at long horizons (gram_mfma) ---
-    constexpr bool kMfmaGram = NTM_MFMA_FF && W::kNN > 32 && P == 64;
-    if constexpr (kMfmaGram) {
-        if (!sq)
-            gram_mfma<W::kNN>(pb, w, nF, [&](int a) { return w.fidx()[a]; },
-                              [&](int a, int c, double sg) {
-                                  Lp[w.brow(a) + w.bcol(c, nt)] = (2 * sg) * w.D()[w.fidx()[a]] * w.D()[w.fidx()[c]];
-                              },
-                              l);
-    } else {
-        const int npair = sq ? 0 : nF * (nF + 1) / 2;
-        for (int idx = l; idx < npair; idx += P) {
-            int a = (int)((sqrt(8.0 * idx + 1.0) - 1.0) * 0.5);
-            if ((a + 1) * (a + 2) / 2 <= idx) ++a;
-            if (a * (a + 1) / 2 > idx) --a;
-            const int c = idx - a * (a + 1) / 2;
-            const int ja = w.fidx()[a], jc = w.fidx()[c];            // ja >= jc
-            const double* ca = w.Gt() + w.gidx(2 * ja, ja) - 2 * ja;
-            const double* cc = w.Gt() + w.gidx(2 * jc, jc) - 2 * jc;
-            const double sg = qdot_rows<NTM_CH>(ca, cc, N, ja, om);   // terms i < ja masked
-            double g2v = 2 * sg;
-            if constexpr (ru_on<W>()) g2v = (a == c) ? g2v + 2 * pb.Ru : g2v;      // + 2 Ru I
-            const double gv = g2v * w.D()[ja] * w.D()[jc];
-            if (fused) Lp[w.brow(a) + w.bcol(c, nt)] = gv;            // row-major: idx == a(a+1)/2 + c
-            else w.R()[a + c * LD] = gv;
-        }
+    // --- compact G~_FF: one (a, c) entry per lane (packed rows, or lower col-major in R) ---
+    const int npair = sq ? 0 : nF * (nF + 1) / 2;
+    for (int idx = l; idx < npair; idx += P) {
+        int a = (int)((sqrt(8.0 * idx + 1.0) - 1.0) * 0.5);
+        if ((a + 1) * (a + 2) / 2 <= idx) ++a;
+        if (a * (a + 1) / 2 > idx) --a;
+        const int c = idx - a * (a + 1) / 2;
+        const int ja = w.fidx()[a], jc = w.fidx()[c];            // ja >= jc
+        const double* ca = w.Gt() + w.gidx(2 * ja, ja) - 2 * ja;
+        const double* cc = w.Gt() + w.gidx(2 * jc, jc) - 2 * jc;
+        const double sg = qdot_rows<NTM_CH>(ca, cc, N, ja, om);   // terms i < ja masked
+        double g2v = 2 * sg;
+        if constexpr (ru_on<W>()) g2v = (a == c) ? g2v + 2 * pb.Ru : g2v;      // + 2 Ru I
+        const double gv = g2v * w.D()[ja] * w.D()[jc];
+        if (fused) Lp[w.brow(a) + w.bcol(c, nt)] = gv;            // row-major: idx == a(a+1)/2 + c
+        else w.R()[a + c * LD] = gv;
     }
     NTM_WSYNC();
     // GI normal of general row s at variable j: n = -(Lin_j D_j)/rn, Lin = sg Gamma_r
@@ -3609,11 +3302,11 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
         // address on every lane (broadcast reads), only Gamma_rj differs.  The entry-
         // per-lane loop below issues ~5 dependent loads per entry, n^2 / 64 times per
         // lane (n ~ 43 at N = 50).  Entries as gen_n computes them, bit for bit.
-        constexpr bool kRowE = W::kNN > 32 || W::kNN == 0 || NTM_ROWE_ALL;
-        // (NTM_E_LANEIDX, P = 64) lane u first loads pivot column u's variable and D_j, and
+        constexpr bool kRowE = W::kNN > 32 || W::kNN == 0;
+        // (P = 64) lane u first loads pivot column u's variable and D_j, and
         // each row's loop takes them by readlane: one LDS round trip per batch (Gamma_rj)
         // instead of two (the column index, then Gamma_rj and D_j at it)
-        constexpr bool kLaneIdx = NTM_E_LANEIDX && P == 64;
+        constexpr bool kLaneIdx = P == 64;
         int jfl = 0;
         double dfl = 0.0;
         if constexpr (kRowE && kLaneIdx) {
@@ -3701,8 +3394,8 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
         // E_p V_p = h and (k = 1) E_p Z_p = -e_c: lane t owns row t; step t broadcasts
         // x_t (z_t) and updates the rows below
         double x = 0.0, zz = 0.0, zz2 = 0.0, zz3 = 0.0;
-        // E[l][t] loaded kAhead steps ahead (a register queue; long horizons: NTM_SUB_AHEAD)
-        constexpr int kAhead = (W::kNN > 32) ? NTM_SUB_AHEAD : 1;
+        // E[l][t] loaded kAhead steps ahead (a register queue)
+        constexpr int kAhead = 1;
         double eq[kAhead];
 #pragma unroll
         for (int a = 0; a < kAhead; ++a) eq[a] = (a < n && l > a && l < n) ? Ep[w.eidx(l, a)] : 0.0;
@@ -3910,20 +3603,11 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
                 w.d()[l] = w.D()[l] * zv;
             }
             NTM_WSYNC();
-            if constexpr (kSplitR) {
-                double yy[2];
-                gamma_rows_split<NTM_CH, 2>(w, {w.U(), w.d()}, yy, l);
-                if (l < 2 * N) {
-                    w.xp()[l] = yy[0];
-                    w.Phi()[l] = yy[1];                          // scratch (hs_of is done with it)
-                }
-            } else {
-                for (int r = l; r < 2 * N; r += P) {
-                    double ya, yb;
-                    gamma_row_dot2<NTM_CH, P>(w, r, w.U(), w.d(), ya, yb);
-                    w.xp()[r] = ya;
-                    w.Phi()[r] = yb;                             // scratch (hs_of is done with it)
-                }
+            for (int r = l; r < 2 * N; r += P) {
+                double ya, yb;
+                gamma_row_dot2<NTM_CH, P>(w, r, w.U(), w.d(), ya, yb);
+                w.xp()[r] = ya;
+                w.Phi()[r] = yb;                             // scratch (hs_of is done with it)
             }
             NTM_WSYNC();
             double num = 0.0, den = 0.0;
@@ -4010,39 +3694,6 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
                     const int rr = (k + b2 < nt) ? k + b2 : nt;
                     prb[b2] = Lp + w.brow(rr);
                 }
-                if constexpr (W::kFar && NTM_FAR_JB > 0) {
-                    // far block (HBM): JB columns per trip for all of the lane's rows and
-                    // the KB pivot rows, every load issued before the first use (one
-                    // memory round trip per trip instead of one per column pair); the
-                    // column index is clamped to k (inside every live row and pivot row),
-                    // the terms past k are skipped, so each sum keeps its column order
-                    constexpr int JB = NTM_FAR_JB > 0 ? NTM_FAR_JB : 1;
-                    for (int j = 0; j < k; j += JB) {
-                        int cj[JB];
-#pragma unroll
-                        for (int u = 0; u < JB; ++u) cj[u] = w.bcol((j + u < k) ? j + u : k, nt);
-                        double av[RPL][JB], pv[KB][JB];
-#pragma unroll
-                        for (int r = 0; r < RPL; ++r)
-#pragma unroll
-                            for (int u = 0; u < JB; ++u) av[r][u] = live[r] ? myrow[r][cj[u]] : 0.0;
-#pragma unroll
-                        for (int b2 = 0; b2 < KB; ++b2)
-#pragma unroll
-                            for (int u = 0; u < JB; ++u) pv[b2][u] = prb[b2][cj[u]];
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int u = 0; u < JB; ++u) {
-                            if (j + u >= k) break;
-                            const double su = (j + u < kf) ? -1.0 : 1.0;
-#pragma unroll
-                            for (int r = 0; r < RPL; ++r)
-                                if (live[r])
-#pragma unroll
-                                    for (int b2 = 0; b2 < KB; ++b2) sacc[r][b2] += (su * av[r][u]) * pv[b2][u];
-                        }
-                    }
-                } else {
 #pragma unroll
                 for (int r = 0; r < RPL; ++r) {
                     if (!live[r]) continue;
@@ -4063,7 +3714,6 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
                             sacc[r][b2] += in1 ? (s1 * a1) * p1[b2] : 0.0;
                         }
                     }
-                }
                 }
                 double Lc[RPL][KB];
 #pragma unroll
@@ -4253,13 +3903,7 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
         NTM_WSYNC();
         // y = Gamma U once, for the primal check (state rows) and the gradient
         if (!y_ready) {
-            if constexpr (kSplitR) {
-                double y[1];
-                gamma_rows_split<NTM_CH, 1>(w, {w.U()}, y, l);
-                if (l < 2 * N) w.xp()[l] = y[0];
-            } else {
-                for (int r = l; r < 2 * N; r += P) w.xp()[r] = gamma_row_dot<NTM_CH, P>(w, r, w.U());
-            }
+            for (int r = l; r < 2 * N; r += P) w.xp()[r] = gamma_row_dot<NTM_CH, P>(w, r, w.U());
             NTM_WSYNC();
         }
         }
@@ -4302,11 +3946,9 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
             omy[2 * l + 1] = om.o1(y0, y1);
         }
         NTM_WSYNC();
-        double g2c = 0.0;
-        if constexpr (kSplitC) g2c = gamma_col_split<NTM_CH>(w, omy, l);
         if (l < N) {
             const double* cl = w.Gt() + w.gidx(2 * l, l) - 2 * l;
-            const double g2 = kSplitC ? g2c : dot_rows2<NTM_CH, P>(w, cl, omy, N, l);   // terms i < l masked
+            const double g2 = dot_rows2<NTM_CH, P>(w, cl, omy, N, l);   // terms i < l masked
             double gu = 2 * g2;
             if constexpr (ru_on<W>()) gu = gu + 2 * pb.Ru * w.U()[l];  // + 2 Ru U_l
             res = w.D()[l] * gu + w.F()[l];
@@ -4816,24 +4458,11 @@ __device__ __forceinline__ int shifted_into_act(const Prob& pb, const W& w, cons
 // ---------------------------------------------------------------------------
 // qp_phase's Goldfarb-Idnani fallback (the full G~, GI warm-started from the
 // failed candidate, then its certified polish; ~2.5% of the QPs at N = 20).
-// NTM_GI_OUTLINE=1 makes it a real call, so that its register allocation is its
-// own instead of the step kernel's (the caller's live registers are saved around
-// the call); 0 inlines it like every other phase.
+// Inlined like every other phase.
 // ---------------------------------------------------------------------------
-#ifndef NTM_GI_DEFER_PROBE
-#define NTM_GI_DEFER_PROBE 0   // timing probe only: GI compiled out of qp_phase
-#endif
-#ifndef NTM_GI_OUTLINE
-#define NTM_GI_OUTLINE 0
-#endif
-#if NTM_GI_OUTLINE
-#define NTM_GI_ATTR __attribute__((noinline))
-#else
-#define NTM_GI_ATTR __forceinline__
-#endif
 template <int P, class W>
-__device__ NTM_GI_ATTR int gi_fallback(const Prob& pb, const W w, const StructRows rows, int nrows, int l, int nwarm,
-                                       int it, int* qp_iters, int* q_out, int* ns_out, bool* yv_out) {
+__device__ __forceinline__ int gi_fallback(const Prob& pb, const W w, const StructRows rows, int nrows, int l, int nwarm,
+                                           int it, int* qp_iters, int* q_out, int* ns_out, bool* yv_out) {
     NTM_T0(tq);
     int flag, q = 0, ns = 0;
     bool yv = false;
@@ -4931,7 +4560,6 @@ __device__ __forceinline__ int qp_phase(const Prob& pb, const W& w, double x0, d
                 for (int i = 0; i < cq; ++i) NTM_TRACE(" %d", w.act()[i]);
                 NTM_TRACE("\n");
 #endif
-#if NTM_CDP
                 // Certified dual path (round 5).  The candidate's re-solve either
                 // certifies, or it gives the set's equality-constrained optimum and
                 // multipliers.  A set whose multipliers are not all >= 0 first drops
@@ -4975,8 +4603,7 @@ __device__ __forceinline__ int qp_phase(const Prob& pb, const W& w, double x0, d
                 // instead, as the dual method may add any violated row; p is eligible again
                 // once A changes.  Before round 6 these QPs went to GI (N = 50 mode 2: 0.1 per
                 // MPC step, 7% of the cycles)
-                constexpr bool kSkipNan = NTM_CDP_SKIP && (W::kNN > 32 || W::kNN == 0);
-                constexpr bool kSkipDir = kSkipNan && NTM_CDP_SKIPDIR;
+                constexpr bool kSkipNan = W::kNN > 32 || W::kNN == 0;
                 int nskip = 0;
                 bool fresh_y = false;                      // the pick recomputes y = Gamma U at V0
                 auto clear_skips = [&]() {
@@ -4992,7 +4619,7 @@ __device__ __forceinline__ int qp_phase(const Prob& pb, const W& w, double x0, d
                 // N = 20 mode 2): 2.67 -> 2.50 re-solves per iteration-2 QP; on the device
                 // 6.45 -> 6.36 ms per step-batch (A/B on one box).  Not for box-only QPs
                 // (their single-row exchanges: config 2 0.206 -> 0.214 ms with it)
-                if (NTM_CDP_HINT && alt && !shift_first && pb.mode != NTM_MODE_BOX)
+                if (alt && !shift_first && pb.mode != NTM_MODE_BOX)
                     (void)shifted_into_act<P>(pb, w, cand, l, true);
                 double vf = 0.0, V0 = 0.0, u0 = 0.0;   // V0: lane = variable; u0: lane = active position
                 bool okc = false;
@@ -5166,8 +4793,8 @@ __device__ __forceinline__ int qp_phase(const Prob& pb, const W& w, double x0, d
                             // the only violated rows left are skipped ones (A + {p} had a
                             // non-finite end point: p nearly depends on A): GI's step for a
                             // dependent row, the dual-only direction of the last skipped row p
-                            // (round 6, NTM_CDP_SKIPDIR), instead of handing the QP to GI
-                            if (kSkipDir && nskip > 0 && p >= 0 && nres < budget) {
+                            // (round 6), instead of handing the QP to GI
+                            if (kSkipNan && nskip > 0 && p >= 0 && nres < budget) {
                                 NTM_CNT(CN_CDP_SKIPDIR);
                                 dirp = p;
                                 qs = cq;
@@ -5209,157 +4836,11 @@ __device__ __forceinline__ int qp_phase(const Prob& pb, const W& w, double x0, d
                     nwarm = cq;
                     NTM_WSYNC();
                 }
-#else
-                // iteration 2: the carried set is the previous step's (slot 1 is only
-                // written at even iterations); when its repairs fail, its
-                // receding-horizon shift is tried before GI (it hits in the
-                // transient of the first steps, where the plan moves in time)
-                bool alt = it == 2 && pb.mode != NTM_MODE_NONE;
-                int keep_id = -1, keep_q = -1;     // the repaired set (lane l: entry l) while the shift is tried
-                // certified re-solve of the candidate; on failure, up to kRepairs
-                // single-row repairs (add the most violated row and/or drop the row
-                // with the most negative multiplier) before falling back to GI.
-                // Only a set that passes the KKT certificate is ever accepted.
-                for (int rep = 0;; ++rep) {
-                    if (n_try) ++*n_try;
-                    int fk = 0, fp = 0;
-                    double vf = 0.0;
-                    const bool okc = polish_compact<P>(pb, w, rows, cq, l, true, &ns, &fk, &fp, &vf);
-                    NTM_TRACE("QP cand rep %d cq %d ok %d fk %d fp %d\n", rep, cq, (int)okc, fk, fp);
-                    if (rep == 0) {
-                        if (it <= 2) NTM_CNT(CN_TRY_EARLY);
-                        if (!okc) { if (it <= 2) NTM_CNT(CN_FAIL_EARLY); else NTM_CNT(CN_FAIL_LATE); }
-                        if (it <= 2 && !okc) {
-                            if (fk == 1) NTM_CNT(CN_FK_DUAL);
-                            else if (fk == 2) NTM_CNT(CN_FK_PRIMAL);
-                            else if (fk == 3) NTM_CNT(CN_FK_SING);
-                            else NTM_CNT(CN_FK_BOTH);
-                        }
-                        if (it == 1) { NTM_CNT(CN_TRY_IT1); if (!okc) NTM_CNT(CN_FAIL_IT1); }
-                        if (it == 2) { NTM_CNT(CN_TRY_IT2); if (!okc) NTM_CNT(CN_FAIL_IT2); }
-                    }
-                    if (rep < 0 && okc) NTM_CNT(CN_ALT_HIT);
-                    if (okc) {
-                        flag = NTM_EXIT_OPTIMAL;
-                        q = cq;
-                        done = true;
-                        yv = true;
-                        NTM_CNT(CN_HIT);
-                        if (rep > 0) NTM_CNT(CN_REPAIR);
-                        break;
-                    }
-                    bool stop = rep >= kRepairs || rep < 0 || fk == 3;   // rep < 0: the shifted set failed
-                    if (!stop && (fk == 2 || fk == 4)) {   // primal: add the most violated row
-                        if (l < cq) w.aflag()[w.act()[l]] = kActiveRow;
-                        NTM_WSYNC();
-                        const double vmx = gmax<P>(l < N ? fabs(vf) : 0.0);
-                        const Pick pk = rows.template check<P>(w, vf, l, false, fmax(1.0, vmx));
-                        NTM_WSYNC();
-                        if (l < cq) w.aflag()[w.act()[l]] = 0;
-                        NTM_WSYNC();
-                        if (pk.p < 0) {
-                            stop = true;
-                        } else {
-                            // A state or rate row whose last variable is held by a bound row
-                            // takes that bound row's place (adding it next to the bound would
-                            // leave it no free variable: a singular system).  This is how a
-                            // boundary arc moves by one stage from step to step.  With a
-                            // negative multiplier too (fk 4) that row goes as well.
-                            int kind, jr, jl = -1;
-                            rows.decode(pk.p, N, kind, jr);
-                            if ((kind == 2 || kind == 3) && jr >= 0) jl = (w.rinfo()[jr] & (kRowMulti - 1)) - 1;
-                            else if (kind >= 4) jl = jr;
-                            int my = -1;
-                            bool drop_me = false, rate_hold = false;
-                            // rate rows (long horizons and the generic kernels): a u bound on
-                            // input jb entering a full set replaces the one active rate row that
-                            // holds jb (U_i - U_{i-1} with i or i-1 = jb), and a rate row entering
-                            // one replaces the bound on its earlier input.  With rate rows the
-                            // odd LPV iterations can alternate between two sets that differ in
-                            // exactly that pair (a period-4 cycle), and the
-                            // smallest-multiplier swap below would pick another row
-                            constexpr bool kRateSwap = W::kNN > 32 || W::kNN == 0;
-                            const int jb = (kRateSwap && kind < 2) ? jr : -1;
-                            if (l < cq) {
-                                my = w.act()[l];
-                                int k2, j2;
-                                rows.decode(my, N, k2, j2);
-                                drop_me = (jl >= 0 && k2 < 2 && j2 == jl) || (fk == 4 && l == fp);
-                                rate_hold = jb >= 0 && k2 >= 4 && (j2 == jb || j2 - 1 == jb);
-                                // and a rate row of input jr entering a full set replaces the
-                                // u bound on input jr - 1 (the one on jr is dropped above)
-                                if (kRateSwap && kind >= 4 && k2 < 2 && j2 == jr - 1) rate_hold = true;
-                            }
-                            const int lane = threadIdx.x & 63;
-                            const unsigned long long gm =
-                                (P == 64) ? ~0ull : (((1ull << P) - 1ull) << (lane & ~(P - 1)));
-                            const unsigned long long keepm = __ballot(l < cq && !drop_me) & gm;
-                            const int nkeep = uni<P>((int)__popcll(keepm));
-                            const unsigned long long rhm = kRateSwap ? (__ballot(rate_hold) & gm) : 0ull;
-                            NTM_WSYNC();
-                            if (nkeep < N) {
-                                if (l < cq && !drop_me) w.act()[__popcll(keepm & ((1ull << lane) - 1ull))] = my;
-                                if (l == 0) w.act()[nkeep] = pk.p;
-                                cq = nkeep + 1;
-                            } else if (kRateSwap && __popcll(rhm) == 1) {   // a full set: the rate row holding jb
-                                if (rate_hold) w.act()[l] = pk.p;
-                            } else if (l == 0) {           // a full set: swap out the smallest multiplier
-                                w.act()[fp] = pk.p;
-                            }
-                        }
-                    } else if (!stop) {                    // dual: drop position fp
-                        int an = 0;
-                        if (l >= fp && l + 1 < cq) an = w.act()[l + 1];
-                        NTM_WSYNC();
-                        if (l >= fp && l + 1 < cq) w.act()[l] = an;
-                        --cq;
-                    }
-                    if (stop) {
-                        if (!alt) break;
-                        alt = false;                       // last try: the other form of the carried set
-                        NTM_CNT(CN_ALT_TRY);
-                        keep_id = (l < cq) ? w.act()[l] : -1;   // the repaired set, for GI's warm start
-                        keep_q = cq;
-                        NTM_WSYNC();
-                        if (shift_first) {                 // the unshifted carried set
-                            cq = cq0;
-                            if (l < cq) w.act()[l] = cand[l];
-                            NTM_WSYNC();
-                        } else {                           // the shifted carried set
-                            cq = shifted_into_act<P>(pb, w, cand, l);
-                        }
-                        rep = -2;                          // counted as neither a first try nor a repair
-                    }
-                    NTM_WSYNC();
-                }
-                if (!done) {
-                    if (keep_q >= 0) {                     // back to the repaired set
-                        cq = keep_q;
-                        if (l < cq) w.act()[l] = keep_id;
-                        NTM_WSYNC();
-                    }
-                    // the repaired set steers GI's add order (StructRows::check) and,
-                    // is GI's warm-start set (gi_solve)
-                    if (l < cq) {
-                        w.aflag()[w.act()[l]] = kCandRow;
-                        w.sidx()[l] = w.act()[l];
-                    }
-                    nwarm = cq;
-                    NTM_WSYNC();
-                }
-#endif
                 NTM_ACC(ST_CAND, tq);
             }
             if (!done) {
                 if (n_girun) ++*n_girun;
-#if NTM_GI_DEFER_PROBE
-                // timing probe only: the set at hand is taken as if certified (wrong
-                // values for these ~1% of QPs; the other 99% run exactly as built)
-                flag = NTM_EXIT_OPTIMAL;
-                q = nwarm;
-#else
                 flag = gi_fallback<P, W>(pb, w, rows, nrows, l, nwarm, it, qp_iters, &q, &ns, &yv);
-#endif
             }
         }
     }

@@ -1,0 +1,33 @@
+# One sha256 per device code object: the six production translation units (Makefile
+# flags, N20FLAGS on ntm_n20.hip) and the single-TU diag, diag20, poison and
+# -DNTM_RU_ONLY20 builds, each compiled to device assembly with the __hip_cuid_ lines
+# (which differ between two compiles of one source) dropped.  CPU only.
+#   bash tools/asm_digest.sh [unit ...]     ->  "<sha256>  <unit>" lines (default: all ten)
+#   ASM_DIR=dir bash tools/asm_digest.sh    also keeps the assembly in dir/<unit>.s
+set -e
+cd "$(dirname "$0")/../mpc-ntm-control_amd"
+H="/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wall -Wno-unused-function --cuda-device-only -S"
+N20="-mllvm -amdgpu-use-amdgpu-trackers=1"
+DIAG="-DNTM_CH=5 -DNTM_CHUNK_UNROLL=2 -Wno-pass-failed -DNTM_STAMPS"
+ONE="csrc/ntm_kernels.hip -DNTM_SINGLE_TU"
+UNITS=${*:-ntm_kernels ntm_n20 ntm_n20near ntm_n20near1w ntm_n50 ntm_n50m3 diag diag20 poison ru_only20}
+D=${ASM_DIR:-$(mktemp -d)}
+mkdir -p "$D"
+for n in $UNITS; do
+  case $n in
+    ntm_n20) F="$N20 csrc/$n.hip";;
+    ntm_*) F="csrc/$n.hip";;
+    diag) F="$DIAG $ONE";;
+    diag20) F="$DIAG $N20 $ONE";;
+    poison) F="-DNTM_POISON=1e300 $ONE";;
+    ru_only20) F="-DNTM_RU_ONLY20 $ONE";;
+    *) echo "unknown unit $n" >&2; exit 1;;
+  esac
+  $H $F -o - | grep -v __hip_cuid_ > "$D/$n.s" &
+done
+wait
+cd "$D"
+for n in $UNITS; do
+  test -s $n.s || { echo "$n: compile failed" >&2; exit 1; }
+  sha256sum $n.s | sed 's/\.s$//'
+done

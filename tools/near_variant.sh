@@ -1,6 +1,6 @@
 # Fast A/B variant of the all-LDS N = 20 translation unit only (ntm_n20near.hip),
 # linked with the product's other objects (lib/obj/), like tools/n20_variant.sh:
-#   bash tools/near_variant.sh NAME "-DNTM_SPLIT_CERT=3 ..."  ->  lib/libntm_mpc_NAME.so
+#   bash tools/near_variant.sh NAME "-DNTM_N20NEAR_CH=5 ..."  ->  lib/libntm_mpc_NAME.so
 set -e
 cd "$(dirname "$0")/../mpc-ntm-control_amd"
 V=$1; F=$2

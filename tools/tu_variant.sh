@@ -1,6 +1,6 @@
 # Fast A/B variant of ONE translation unit (n20 | n20near | n20near1w | n50 | n50m3 | kernels), linked
 # with the product's other objects (lib/obj/):
-#   bash tools/tu_variant.sh n50 NAME "-DNTM_CDP_SIGNED=0"  ->  lib/libntm_mpc_NAME.so
+#   bash tools/tu_variant.sh n50 NAME "-DNTM_COLL3=0"  ->  lib/libntm_mpc_NAME.so
 # (the N = 20 far TU gets its product scheduler flags, Makefile N20FLAGS)
 set -e
 cd "$(dirname "$0")/../mpc-ntm-control_amd"
