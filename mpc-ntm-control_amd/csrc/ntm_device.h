@@ -991,6 +991,91 @@ __device__ __forceinline__ void fadd5x2_class_lanes_upto(double& s, double& fs, 
                  : "scc");
 #undef NTM_TERM
 }
+// ---------------------------------------------------------------------------
+// Lane-masked lift recursion (the slim far N = 20 lift: Gamma's column l on lane
+// l < N, the free response on lane N).  At stage i the lanes that advance are
+// known at compile time: columns 0..i-1 (their diagonal lies above row i) and
+// lane N, the mask ((1 << i) - 1) | (1 << N).  The select form computes the next
+// 2-vector on every lane, selects it or the old one, selects the store index
+// (i, or the lane's own diagonal again) and builds the address: a v_cmp, five
+// v_cndmask, a v_mov and a v_lshl_add per stage around four fp64 instructions,
+// the selects on the chain to the next stage.  Here the four instructions and the
+// pair store run with EXEC narrowed to that mask: a lane that is off keeps g0 /
+// g1 and stores nothing, where the select form re-stored the same bits to the
+// same place, so registers and LDS hold the same bits whatever the data.
+//   The arithmetic is the select form's as the production build compiles it, which
+// is not one form: the compiler contracts (a21 g0 + a22 g1) + c1 from either
+// product, and it does so by the stage's place in its chunk of five.  First and
+// last stage of a chunk (form A): t = g0 a21; t = fma(a22, g1, t); g0 = fma(g0,
+// a11, c0).  The three between (form B): t = a22 g1; t = fma(a21, g0, t); g0 =
+// fma(a11, g0, c0).  Both end g1 = c1 + t.  The two round differently, so each
+// stage keeps the form, and the operand order, it had.
+//   One asm block per chunk.  EXEC is saved on entry, every mask is a literal ANDed
+// with the saved value (lanes off on entry stay off), EXEC is restored before the
+// block ends.  a22 is wave-uniform in every kernel (an SGPR pair, src0 of the
+// v_fmac / v_mul); c0 / c1 differ between the Gamma lanes and lane N: VGPRs.
+//   The stores are in the block (ds_write2_b64 at rec + 16 i: immediate offsets),
+// so the block clobbers memory and the compiler's wait counts do not include them.
+// LDS operations of one wave complete in order, so a compiler wait for a load
+// issued before or after such a store only waits longer, never too little; the
+// last chunk ends with s_waitcnt lgkmcnt(0), so nothing uncounted is in flight
+// past the lift.  Wait states: a SALU write of EXEC needs none before a VALU or
+// an LDS instruction (s_and_saveexec followed by a ds_write is what the compiler
+// emits for a predicated store), nor does a VALU write of a VGPR before the LDS
+// store that reads it as data (the interlock the compiler's own v_add, ds_write2
+// pairs rely on).  A store's data registers are next written by the following
+// stage's v_fma / v_add, three or more instructions behind it (s_and, v_mul,
+// v_fmac), or behind the restoring s_mov, the s_nop and the next block's s_mov /
+// s_and: the ISA asks for wait states there only after a vector-memory store of
+// more than 64 bits (one or two), LDS stores are not in that list, and the
+// compiler itself rewrites a ds_write2's data one instruction later.  After the
+// block: the last VALU write (g1) is followed by the store, the restoring s_mov
+// and an s_nop 0, more than the two wait states a DPP or lane read of it needs.
+//   Measured on the far N = 20 kernel at B = 1e5 (A/B on one box, three runs
+// each): 5.804 -> 5.602 ms per step-batch, outputs byte-equal; VALU instructions
+// per wave-step 25,977 -> 24,475, the fp64 ones unchanged.
+// ---------------------------------------------------------------------------
+#define NTM_LIFT_MASK(k) "s_and_b64 exec, %[sv], %[m" #k "]\n\t"
+#define NTM_LIFT_PUT(k) "ds_write2_b64 %[rec], %[g0], %[g1] offset0:%[o" #k "] offset1:%[p" #k "]\n\t"
+#define NTM_LIFT_A(k)                                                                                    \
+    NTM_LIFT_MASK(k) "v_mul_f64 %[t], %[g0], %[b" #k "]\n\tv_fmac_f64_e32 %[t], %[a22], %[g1]\n\t"       \
+                     "v_fma_f64 %[g0], %[g0], %[a" #k "], %[c0]\n\tv_add_f64 %[g1], %[c1], %[t]\n\t" NTM_LIFT_PUT(k)
+#define NTM_LIFT_B(k)                                                                                    \
+    NTM_LIFT_MASK(k) "v_mul_f64 %[t], %[a22], %[g1]\n\tv_fmac_f64_e32 %[t], %[b" #k "], %[g0]\n\t"       \
+                     "v_fma_f64 %[g0], %[a" #k "], %[g0], %[c0]\n\tv_add_f64 %[g1], %[c1], %[t]\n\t" NTM_LIFT_PUT(k)
+#define NTM_LIFT_N(k, I0) \
+    [m##k] "n"(((1 << ((I0) + k)) - 1) | (1 << 20)), [o##k] "n"(2 * ((I0) + k)), [p##k] "n"(2 * ((I0) + k) + 1)
+// stages I0 .. I0 + NS - 1 (NS = 5, or 4 in the last chunk, which also drains the stores) of
+// g <- A_i g + c on the lanes < i and lane 20, each stage's pair stored at rec + 16 i bytes
+// (rec: the lane's LDS byte address).  ca / cb: a11 / a21 of the chunk's stages
+template <int I0, int NS>
+__device__ __forceinline__ void lift_chunk_lanes(double& g0, double& g1, const double (&ca)[5], const double (&cb)[5],
+                                                 double a22, double c0, double c1, unsigned rec) {
+    static_assert(I0 >= 1 && (NS == 4 || NS == 5) && I0 + NS <= 20, "stages 1..19 of the N = 20 lift");
+    unsigned long long sv;
+    double t;
+    if constexpr (NS == 5) {
+        asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_LIFT_A(0) NTM_LIFT_B(1) NTM_LIFT_B(2) NTM_LIFT_B(3) NTM_LIFT_A(4)
+                     "s_mov_b64 exec, %[sv]\n\ts_nop 0"
+                     : [g0] "+v"(g0), [g1] "+v"(g1), [t] "=&v"(t), [sv] "=&s"(sv)
+                     : NTM_V5(a, ca), NTM_V5(b, cb), [a22] "s"(a22), [c0] "v"(c0), [c1] "v"(c1), [rec] "v"(rec),
+                       NTM_LIFT_N(0, I0), NTM_LIFT_N(1, I0), NTM_LIFT_N(2, I0), NTM_LIFT_N(3, I0), NTM_LIFT_N(4, I0)
+                     : "scc", "memory");
+    } else {
+        asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_LIFT_A(0) NTM_LIFT_B(1) NTM_LIFT_B(2) NTM_LIFT_B(3)
+                     "s_mov_b64 exec, %[sv]\n\ts_waitcnt lgkmcnt(0)"
+                     : [g0] "+v"(g0), [g1] "+v"(g1), [t] "=&v"(t), [sv] "=&s"(sv)
+                     : [a0] "v"(ca[0]), [a1] "v"(ca[1]), [a2] "v"(ca[2]), [a3] "v"(ca[3]), [b0] "v"(cb[0]),
+                       [b1] "v"(cb[1]), [b2] "v"(cb[2]), [b3] "v"(cb[3]), [a22] "s"(a22), [c0] "v"(c0), [c1] "v"(c1),
+                       [rec] "v"(rec), NTM_LIFT_N(0, I0), NTM_LIFT_N(1, I0), NTM_LIFT_N(2, I0), NTM_LIFT_N(3, I0)
+                     : "scc", "memory");
+    }
+}
+#undef NTM_LIFT_MASK
+#undef NTM_LIFT_PUT
+#undef NTM_LIFT_A
+#undef NTM_LIFT_B
+#undef NTM_LIFT_N
 #undef NTM_LANES_FROM
 #undef NTM_LANES_UPTO
 #undef NTM_SHIFTS_FROM
@@ -1170,6 +1255,26 @@ __device__ __forceinline__ constexpr bool fuse_colsum() {
     if constexpr (W::kSlim) return W::kNN > 32;   // N = 50: on; the far N = 20 kernel: off
     else return false;                            // the all-LDS N = 20 build and the generic kernels: off
 }
+// The slim far N = 20 lift runs its recursion lane-masked (lift_chunk_lanes): column l on
+// lane l, a11 / a21 in LDS, chunks of five stages, no column sums riding on the loop
+template <int P, int CH, class W>
+__device__ __forceinline__ constexpr bool lift_lanes_ok() {
+    if constexpr (W::kSlim) return lane_masked_ok<P, CH, W>() && W::kAB != 0 && !fuse_colsum<W>();
+    else return false;
+}
+// chunk I0 of the lane-masked lift: the a11 / a21 loads batched at compile-time offsets, then the stages
+template <int I0, int NS, class W>
+__device__ __forceinline__ void lift_chunk_at(const W& w, double& g0, double& g1, double a22, double c0, double c1,
+                                              unsigned rec) {
+    double ca[5], cb[5];
+#pragma unroll
+    for (int u = 0; u < 5; ++u) {
+        ca[u] = u < NS ? w.a11()[I0 + u] : 0.0;
+        cb[u] = u < NS ? w.a21()[I0 + u] : 0.0;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    lift_chunk_lanes<I0, NS>(g0, g1, ca, cb, a22, c0, c1, rec);
+}
 
 template <int P, class W>
 __device__ __forceinline__ void lift_phase(const Prob& pb, const W& w, int l, double x0 = 0.0, double x1 = 0.0,
@@ -1221,6 +1326,14 @@ __device__ __forceinline__ void lift_phase(const Prob& pb, const W& w, int l, do
             };
             col_terms(0);
             constexpr int CH = NTM_CH;
+            if constexpr (lift_lanes_ok<P, CH, W>()) {
+                // stages 1..19 under EXEC narrowed to the lanes that advance (lift_chunk_lanes)
+                const unsigned at = (unsigned)(uintptr_t)(__attribute__((address_space(3))) double*)rec;
+                lift_chunk_at<1, 5>(w, g0, g1, k.a22, c0, c1, at);
+                lift_chunk_at<6, 5>(w, g0, g1, k.a22, c0, c1, at);
+                lift_chunk_at<11, 5>(w, g0, g1, k.a22, c0, c1, at);
+                lift_chunk_at<16, 4>(w, g0, g1, k.a22, c0, c1, at);
+            } else {
             NTM_CHUNK_PRAGMA
             for (int i0 = 1; i0 < N; i0 += CH) {
                 double ca[CH], cb[CH];
@@ -1251,6 +1364,7 @@ __device__ __forceinline__ void lift_phase(const Prob& pb, const W& w, int l, do
                         col_terms(i);
                     }
                 }
+            }
             }
             if (cs) { cs->s = cs_s; cs->f = cs_f; cs->bad = cs_bad; }
         }
