@@ -1081,6 +1081,238 @@ __device__ __forceinline__ void lift_chunk_lanes(double& g0, double& g1, const d
 #undef NTM_SHIFTS_FROM
 #undef NTM_SHIFTS_UPTO
 #undef NTM_V5
+// ---------------------------------------------------------------------------
+// Lane-masked triangular substitutions of the echelon re-solve (the slim far
+// N = 20 kernels: the sorted E packed in LDS, row t at Ep + t(t+1)/2, n <= 20
+// rows, one scenario per wave).  Forward (E V = h, and E Z = -e_c with it when
+// k = 1): lane l owns row l, step t forms x_t = acc_t / E_tt on lane t, takes it
+// by two v_readlane_b32 and subtracts E_lt x_t on the rows below.  Backward (E'
+// mu = grad): lane l owns column l, the steps descend from u = n - 1 and update
+// the columns l < u.  The loop form does every step on every lane: a select
+// captures x on the lane l == t (a v_cmp, two v_mov, two v_cndmask per right-hand
+// side), the element load sits under a saved EXEC with a branch and its wait
+// directly in front of the fma, the address is rebuilt per step.  Here the steps
+// are unrolled over the compile-time t in batches of five: a batch's five
+// elements are loaded first (ds_read_b64 at immediate offsets from one per-lane
+// address, each under EXEC = the lanes that will use it: t < l < n forward, l < u
+// backward, so nothing past a row's diagonal is read), waited for once, and
+// the five chain steps follow without an LDS wait.  Per step and right-hand
+// side: one v_mul_f64 (acc sq_id, written straight into x under EXEC = lanes t <=
+// l < n: lane t's x is final after step t because the later steps exclude it, so
+// there is no select), the two v_readlane_b32 (the compiler's, between two
+// statements: v_readlane ignores EXEC, and a statement cannot name the halves of
+// a 64-bit operand), one v_fma_f64 under EXEC = lanes t < l < n.
+//   Bit-equality with the loop form, whatever the data: a lane l <= t there goes
+// on computing acc -= 0 x_t after its x was captured, and a lane >= n does so from
+// the start; neither acc is read again, by the loop or behind it.  x (zz, mu) of a
+// lane < n is the same product acc sq_id of the same chain (v_mul_f64 with sq_id as
+// src0; v_fma_f64 with the negated element as src0, the broadcast as src1: the
+// operands, and so the NaN a non-finite step propagates, as the loop form was
+// compiled); lanes >= n and lanes off on entry keep what they held (0.0 in the
+// kernel).  A step t >= n inside a batch runs with an empty EXEC (the masks are ANDed
+// with the lanes < n); backward a step u >= n would pass `lanes <= u`, so each
+// step's masks are ANDed with a gate that is the entry EXEC if u < n and 0 if not
+// (SALU, only in the batch the chain enters through).
+//   The masks are 32-bit literals with bit 31 clear (n <= 20), ANDed with the
+// entry EXEC, which every statement restores before it ends.  Wait states: a
+// SALU write of EXEC needs none before a VALU or an LDS instruction; v_mul_f64's
+// result is read by v_readlane_b32 (one wait state): the restoring s_mov_b64
+// stands between them in every statement.  The v_readlane's SGPR result feeds the
+// v_fma_f64 as a source: a VALU read of an SGPR that a VALU wrote needs two wait
+// states, and the compiler does not look into a statement for them, so each
+// step's s_and_b64 is followed by an s_nop 0 (the v_readlane_b32 may be the last
+// thing ahead of the statement).  The loads and their s_waitcnt lgkmcnt(0) are in
+// one statement, so no loaded register is visible to the compiler before it landed.
+//   Measured on the far N = 20 kernel at B = 1e5 (A/B on one box, three runs
+// each): the forward substitution 5.592 -> 5.495 ms per step-batch, the backward
+// one on top 5.490 -> 5.405 ms, outputs byte-equal; VALU instructions per wave-
+// step 24,475 -> 23,419.
+// ---------------------------------------------------------------------------
+template <int P, int CH, class W>
+__device__ __forceinline__ constexpr bool esub_lanes_ok() {
+    if constexpr (W::kSlim) return lane_masked_ok<P, CH, W>();
+    else return false;
+}
+struct LaneExec {
+    unsigned long long sv;                                // EXEC on entry
+    unsigned long long mb;                                // its lanes below n
+};
+__device__ __forceinline__ LaneExec esub_enter(int n) {   // n wave-uniform, 0..20
+    LaneExec x;
+    const unsigned long long low = (1ull << n) - 1ull;
+    asm volatile("s_mov_b64 %[sv], exec\n\ts_and_b64 %[mb], exec, %[lo]"
+                 : [sv] "=&s"(x.sv), [mb] "=&s"(x.mb)
+                 : [lo] "s"(low)
+                 : "scc");
+    return x;
+}
+constexpr unsigned esub_ge(int t) { return 0xFFFFFu & ~((1u << t) - 1u); }   // lanes t..19
+constexpr unsigned esub_gt(int t) { return 0xFFFFFu & ~((2u << t) - 1u); }   // lanes t+1..19
+constexpr unsigned esub_le(int u) { return (2u << u) - 1u; }                 // lanes 0..u
+constexpr unsigned esub_lt(int u) { return (1u << u) - 1u; }                 // lanes 0..u-1
+#define NTM_ESUB_LD(k) "s_and_b64 exec, %[mk], %[m" #k "]\n\tds_read_b64 %[e" #k "], %[at] offset:%[o" #k "]\n\t"
+// forward batch T0..T0+4: the five loads E[l][T0 + k] (lanes > T0 + k below n), step T0's product(s), one wait
+template <int T0, bool TWO>
+__device__ __forceinline__ void fsub_open(double (&e)[5], double acc, double& x, double acz, double& zz, double sq,
+                                          unsigned row, const LaneExec& c) {
+    static_assert(T0 >= 0 && T0 + 5 <= 20, "steps 0..19");
+    if constexpr (TWO) {
+        asm volatile(NTM_ESUB_LD(0) NTM_ESUB_LD(1) NTM_ESUB_LD(2) NTM_ESUB_LD(3) NTM_ESUB_LD(4)
+                     "s_and_b64 exec, %[mk], %[ge]\n\tv_mul_f64 %[x], %[sq], %[acc]\n\tv_mul_f64 %[z], %[sq], %[acz]\n\t"
+                     "s_waitcnt lgkmcnt(0)\n\ts_mov_b64 exec, %[sv]"
+                     : [e0] "=&v"(e[0]), [e1] "=&v"(e[1]), [e2] "=&v"(e[2]), [e3] "=&v"(e[3]), [e4] "=&v"(e[4]),
+                       [x] "+v"(x), [z] "+v"(zz)
+                     : [acc] "v"(acc), [acz] "v"(acz), [sq] "v"(sq), [at] "v"(row), [mk] "s"(c.mb), [sv] "s"(c.sv),
+                       [ge] "n"(esub_ge(T0)), [m0] "n"(esub_gt(T0)), [m1] "n"(esub_gt(T0 + 1)), [m2] "n"(esub_gt(T0 + 2)),
+                       [m3] "n"(esub_gt(T0 + 3)), [m4] "n"(esub_gt(T0 + 4)), [o0] "n"(8 * T0), [o1] "n"(8 * (T0 + 1)),
+                       [o2] "n"(8 * (T0 + 2)), [o3] "n"(8 * (T0 + 3)), [o4] "n"(8 * (T0 + 4))
+                     : "scc", "memory");
+    } else {
+        asm volatile(NTM_ESUB_LD(0) NTM_ESUB_LD(1) NTM_ESUB_LD(2) NTM_ESUB_LD(3) NTM_ESUB_LD(4)
+                     "s_and_b64 exec, %[mk], %[ge]\n\tv_mul_f64 %[x], %[sq], %[acc]\n\t"
+                     "s_waitcnt lgkmcnt(0)\n\ts_mov_b64 exec, %[sv]"
+                     : [e0] "=&v"(e[0]), [e1] "=&v"(e[1]), [e2] "=&v"(e[2]), [e3] "=&v"(e[3]), [e4] "=&v"(e[4]),
+                       [x] "+v"(x)
+                     : [acc] "v"(acc), [sq] "v"(sq), [at] "v"(row), [mk] "s"(c.mb), [sv] "s"(c.sv),
+                       [ge] "n"(esub_ge(T0)), [m0] "n"(esub_gt(T0)), [m1] "n"(esub_gt(T0 + 1)), [m2] "n"(esub_gt(T0 + 2)),
+                       [m3] "n"(esub_gt(T0 + 3)), [m4] "n"(esub_gt(T0 + 4)), [o0] "n"(8 * T0), [o1] "n"(8 * (T0 + 1)),
+                       [o2] "n"(8 * (T0 + 2)), [o3] "n"(8 * (T0 + 3)), [o4] "n"(8 * (T0 + 4))
+                     : "scc", "memory");
+    }
+}
+// forward step T: acc -= E[l][T] x_T on lanes > T, then (NEXT) step T + 1's product(s) on lanes >= T + 1,
+// the same lanes: one mask
+template <int T, bool TWO, bool NEXT>
+__device__ __forceinline__ void fsub_step(double et, double& acc, double& x, double& acz, double& zz, double sq,
+                                          const LaneExec& c) {
+    const double xt = gbcast<64>(x, T);
+    if constexpr (TWO) {
+        const double zt = gbcast<64>(zz, T);
+        if constexpr (NEXT)
+            asm volatile("s_and_b64 exec, %[mk], %[gt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
+                         "v_fma_f64 %[acz], -%[e], %[zt], %[acz]\n\t"
+                         "v_mul_f64 %[x], %[sq], %[acc]\n\tv_mul_f64 %[z], %[sq], %[acz]\n\ts_mov_b64 exec, %[sv]"
+                         : [acc] "+v"(acc), [acz] "+v"(acz), [x] "+v"(x), [z] "+v"(zz)
+                         : [e] "v"(et), [xt] "s"(xt), [zt] "s"(zt), [sq] "v"(sq), [mk] "s"(c.mb), [sv] "s"(c.sv),
+                           [gt] "n"(esub_gt(T))
+                         : "scc");
+        else if constexpr (esub_gt(T) != 0)
+            asm volatile("s_and_b64 exec, %[mk], %[gt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
+                         "v_fma_f64 %[acz], -%[e], %[zt], %[acz]\n\ts_mov_b64 exec, %[sv]"
+                         : [acc] "+v"(acc), [acz] "+v"(acz)
+                         : [e] "v"(et), [xt] "s"(xt), [zt] "s"(zt), [mk] "s"(c.mb), [sv] "s"(c.sv), [gt] "n"(esub_gt(T))
+                         : "scc");
+    } else {
+        if constexpr (NEXT)
+            asm volatile("s_and_b64 exec, %[mk], %[gt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
+                         "v_mul_f64 %[x], %[sq], %[acc]\n\ts_mov_b64 exec, %[sv]"
+                         : [acc] "+v"(acc), [x] "+v"(x)
+                         : [e] "v"(et), [xt] "s"(xt), [sq] "v"(sq), [mk] "s"(c.mb), [sv] "s"(c.sv),
+                           [gt] "n"(esub_gt(T))
+                         : "scc");
+        else if constexpr (esub_gt(T) != 0)
+            asm volatile("s_and_b64 exec, %[mk], %[gt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
+                         "s_mov_b64 exec, %[sv]"
+                         : [acc] "+v"(acc)
+                         : [e] "v"(et), [xt] "s"(xt), [mk] "s"(c.mb), [sv] "s"(c.sv), [gt] "n"(esub_gt(T))
+                         : "scc");
+    }
+}
+template <int T0, bool TWO>
+__device__ __forceinline__ void fsub_batch(double& acc, double& x, double& acz, double& zz, double sq, unsigned row,
+                                           const LaneExec& c) {
+    double e[5];
+    fsub_open<T0, TWO>(e, acc, x, acz, zz, sq, row, c);
+    fsub_step<T0, TWO, true>(e[0], acc, x, acz, zz, sq, c);
+    fsub_step<T0 + 1, TWO, true>(e[1], acc, x, acz, zz, sq, c);
+    fsub_step<T0 + 2, TWO, true>(e[2], acc, x, acz, zz, sq, c);
+    fsub_step<T0 + 3, TWO, true>(e[3], acc, x, acz, zz, sq, c);
+    fsub_step<T0 + 4, TWO, false>(e[4], acc, x, acz, zz, sq, c);
+}
+// E x = acc (TWO: and E zz = acz) for the lanes < n of the entry EXEC; row: the LDS byte address of
+// the lane's row of the packed E, sq: 1 / E[l][l].  n wave-uniform; the chain leaves at a batch boundary
+template <bool TWO>
+__device__ __forceinline__ void fsub_lanes(int n, double& acc, double& x, double& acz, double& zz, double sq,
+                                           unsigned row) {
+    const LaneExec c = esub_enter(n);
+    if (n > 0) fsub_batch<0, TWO>(acc, x, acz, zz, sq, row, c);
+    if (n > 5) fsub_batch<5, TWO>(acc, x, acz, zz, sq, row, c);
+    if (n > 10) fsub_batch<10, TWO>(acc, x, acz, zz, sq, row, c);
+    if (n > 15) fsub_batch<15, TWO>(acc, x, acz, zz, sq, row, c);
+}
+// backward batch U0+4 .. U0 (descending): the loads E[u][l] (lanes < u), step U0 + 4's product, one wait.
+// g: the gate of step U0 + 4 (the entry EXEC, or 0 if the step lies at or above n)
+template <int U0>
+__device__ __forceinline__ void bsub_open(double (&e)[5], double acc, double& mu, double sq, unsigned col,
+                                          unsigned long long g, const LaneExec& c) {
+    static_assert(U0 >= 0 && U0 + 5 <= 20, "steps 19..0");
+    constexpr int o0 = 4 * (U0 + 4) * (U0 + 5), o1 = 4 * (U0 + 3) * (U0 + 4), o2 = 4 * (U0 + 2) * (U0 + 3),
+                  o3 = 4 * (U0 + 1) * (U0 + 2), o4 = 4 * U0 * (U0 + 1);           // 8 u (u + 1) / 2 bytes
+    asm volatile(NTM_ESUB_LD(0) NTM_ESUB_LD(1) NTM_ESUB_LD(2) NTM_ESUB_LD(3) NTM_ESUB_LD(4)
+                 "s_and_b64 exec, %[g], %[le]\n\tv_mul_f64 %[x], %[sq], %[acc]\n\t"
+                 "s_waitcnt lgkmcnt(0)\n\ts_mov_b64 exec, %[sv]"
+                 : [e0] "=&v"(e[0]), [e1] "=&v"(e[1]), [e2] "=&v"(e[2]), [e3] "=&v"(e[3]), [e4] "=&v"(e[4]), [x] "+v"(mu)
+                 : [acc] "v"(acc), [sq] "v"(sq), [at] "v"(col), [mk] "s"(c.sv), [sv] "s"(c.sv), [g] "s"(g),
+                   [le] "n"(esub_le(U0 + 4)), [m0] "n"(esub_lt(U0 + 4)), [m1] "n"(esub_lt(U0 + 3)),
+                   [m2] "n"(esub_lt(U0 + 2)), [m3] "n"(esub_lt(U0 + 1)), [m4] "n"(esub_lt(U0)), [o0] "n"(o0),
+                   [o1] "n"(o1), [o2] "n"(o2), [o3] "n"(o3), [o4] "n"(o4)
+                 : "scc", "memory");
+}
+// backward step U: acc -= E[U][l] mu_U on lanes < U under the step's gate g, then (NEXT) step U - 1's product
+// on lanes <= U - 1 (the same lanes) under its gate gn
+template <int U, bool NEXT, bool GATED>
+__device__ __forceinline__ void bsub_step(double eu, double& acc, double& mu, double sq, unsigned long long g,
+                                          unsigned long long gn, const LaneExec& c) {
+    const double mu_u = gbcast<64>(mu, U);
+    if constexpr (NEXT && U > 0 && !GATED)               // both gates are the entry EXEC: one mask
+        asm volatile("s_and_b64 exec, %[g], %[lt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
+                     "v_mul_f64 %[x], %[sq], %[acc]\n\ts_mov_b64 exec, %[sv]"
+                     : [acc] "+v"(acc), [x] "+v"(mu)
+                     : [e] "v"(eu), [xt] "s"(mu_u), [sq] "v"(sq), [g] "s"(g), [sv] "s"(c.sv), [lt] "n"(esub_lt(U))
+                     : "scc");
+    else if constexpr (NEXT && U > 0)
+        asm volatile("s_and_b64 exec, %[g], %[lt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
+                     "s_and_b64 exec, %[gn], %[le]\n\tv_mul_f64 %[x], %[sq], %[acc]\n\t"
+                     "s_mov_b64 exec, %[sv]"
+                     : [acc] "+v"(acc), [x] "+v"(mu)
+                     : [e] "v"(eu), [xt] "s"(mu_u), [sq] "v"(sq), [g] "s"(g), [gn] "s"(gn), [sv] "s"(c.sv),
+                       [lt] "n"(esub_lt(U)), [le] "n"(esub_le(U > 0 ? U - 1 : 0))
+                     : "scc");
+    else if constexpr (U > 0)
+        asm volatile("s_and_b64 exec, %[g], %[lt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
+                     "s_mov_b64 exec, %[sv]"
+                     : [acc] "+v"(acc)
+                     : [e] "v"(eu), [xt] "s"(mu_u), [g] "s"(g), [sv] "s"(c.sv), [lt] "n"(esub_lt(U))
+                     : "scc");
+}
+template <int U0, bool GATED>
+__device__ __forceinline__ void bsub_batch(int n, double& acc, double& mu, double sq, unsigned col, const LaneExec& c) {
+    double e[5];
+    auto gate = [&](int u) -> unsigned long long { return (!GATED || u < n) ? c.sv : 0ull; };
+    bsub_open<U0>(e, acc, mu, sq, col, gate(U0 + 4), c);
+    bsub_step<U0 + 4, true, GATED>(e[0], acc, mu, sq, gate(U0 + 4), gate(U0 + 3), c);
+    bsub_step<U0 + 3, true, GATED>(e[1], acc, mu, sq, gate(U0 + 3), gate(U0 + 2), c);
+    bsub_step<U0 + 2, true, GATED>(e[2], acc, mu, sq, gate(U0 + 2), gate(U0 + 1), c);
+    bsub_step<U0 + 1, true, GATED>(e[3], acc, mu, sq, gate(U0 + 1), gate(U0), c);
+    bsub_step<U0, false, GATED>(e[4], acc, mu, sq, gate(U0), 0ull, c);
+}
+// E' mu = acc for the lanes < n of the entry EXEC; col: the LDS byte address of E[0][l] (Ep + l), sq: 1 /
+// E[l][l].  The batch that holds step n - 1 is gated per step, the ones below it are not
+template <int U0>
+__device__ __forceinline__ void bsub_from(int n, double& acc, double& mu, double sq, unsigned col, const LaneExec& c) {
+    if (n > U0) {
+        if (n >= U0 + 5) bsub_batch<U0, false>(n, acc, mu, sq, col, c);
+        else bsub_batch<U0, true>(n, acc, mu, sq, col, c);
+    }
+}
+__device__ __forceinline__ void bsub_lanes(int n, double& acc, double& mu, double sq, unsigned col) {
+    const LaneExec c = esub_enter(n);
+    bsub_from<15>(n, acc, mu, sq, col, c);
+    bsub_from<10>(n, acc, mu, sq, col, c);
+    bsub_from<5>(n, acc, mu, sq, col, c);
+    bsub_from<0>(n, acc, mu, sq, col, c);
+}
+#undef NTM_ESUB_LD
 // chunk J0 / 5 of row `lane`'s dot(s): the batched loads at compile-time offsets, then the masked terms
 template <int J0, class W>
 __device__ __forceinline__ void gamma_row_chunk_lanes(const W& w, const double* gr, const double* v, double& y) {
@@ -3508,6 +3740,13 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
         // E_p V_p = h and (k = 1) E_p Z_p = -e_c: lane t owns row t; step t broadcasts
         // x_t (z_t) and updates the rows below
         double x = 0.0, zz = 0.0, zz2 = 0.0, zz3 = 0.0;
+        if constexpr (esub_lanes_ok<P, NTM_CH, W>()) {
+            // the slim far N = 20 kernels: unrolled in batches of five under narrowed EXEC (fsub_lanes)
+            const unsigned row = (unsigned)(uintptr_t)(__attribute__((address_space(3))) double*)(Ep + w.eidx(l, 0));
+            const int nu = __builtin_amdgcn_readfirstlane(n);
+            if (nc >= 0) fsub_lanes<true>(nu, acc, x, acz, zz, sq_id, row);
+            else fsub_lanes<false>(nu, acc, x, acz, zz, sq_id, row);
+        } else {
         // E[l][t] loaded kAhead steps ahead (a register queue)
         constexpr int kAhead = 1;
         double eq[kAhead];
@@ -3544,6 +3783,7 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
                 if (l == t) zz3 = zt3;
                 acz3 -= et * zt3;
             }
+        }
         }
         ok = !gany<P>(l < n && !(isfinite(x) && isfinite(zz) && isfinite(zz2) && isfinite(zz3)));
         // V_0 (pivots from E_p V_p = h, fixed values, 0 on the non-pivot columns) and Z
@@ -4082,6 +4322,11 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
             // one collision: a second right-hand side, the left-out row B at the pivot columns
             double acb = (kCollision && xb >= 0 && l < n) ? gen_n(xb, w.fidx()[pl]) : 0.0, mb = 0.0;
             double acb2 = (kColl2 && xb2 >= 0 && l < n) ? gen_n(xb2, w.fidx()[pl]) : 0.0, mb2 = 0.0;
+            if constexpr (esub_lanes_ok<P, NTM_CH, W>()) {
+                // the slim far N = 20 kernels: descending batches of five under narrowed EXEC (bsub_lanes)
+                const unsigned col = (unsigned)(uintptr_t)(__attribute__((address_space(3))) double*)(w.Ep() + l);
+                bsub_lanes(__builtin_amdgcn_readfirstlane(n), acc, mu, sq_id, col);
+            } else {
             // E[u][l] loaded kAheadB steps ahead (long horizons: NTM_MU_AHEAD; a register queue)
             constexpr int kAheadB = (W::kNN > 32) ? NTM_MU_AHEAD : 0;
             double bq[kAheadB > 0 ? kAheadB : 1];
@@ -4117,6 +4362,7 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
                     if (l == u) mb2 = mb2_u;
                     acb2 -= eu * mb2_u;
                 }
+            }
             }
             if (kColl2 && xb2 >= 0) {
                 // mu = a - mu_1 b1 - mu_2 b2; the two hole columns' equations give mu_1, mu_2:
