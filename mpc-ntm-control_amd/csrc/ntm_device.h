@@ -21,2242 +21,46 @@
 // call on gfx950 (the Prob and WS references copied to scratch, the caller's
 // live VGPRs saved around it): 15.9 -> 14.7 ms per step-batch at B=1e5, N=20
 // once everything was inlined again.
+//
+// The layers below the solver have headers of their own, included here in this order (each
+// is #pragma once, includes exactly what it uses and compiles on its own):
+//   ntm_prob.h         Coef, Gen, Prob; the counter-based scenario generator (host and device)
+//   ntm_diag.h         NTM_TRACE*, the stamp macros, NTM_NSTAMPS, the ST_* / CN_* slots, ST_COUNT
+//   ntm_base.h         kInf, rsqrt_nr, the solver constants, the build switches and how a
+//                      translation unit sets them, NTM_CH, NTM_CHUNK_PRAGMA, NTM_WSYNC
+//   ntm_collectives.h  dpp_d .. gargmin: reductions, ballots and broadcasts over a group
+//   ntm_ws.h           rho_eval / coef_*, ws_far, WS, ws_bytes, ws_carve, ru_on, qi_on, OmQ,
+//                      scn_coef, scn_store
+//   ntm_lanes.h        every inline-assembly helper that runs under a narrowed EXEC, with the
+//                      rules they share: lane_masked_ok, fmac5*_lanes_from, fadd5*_lanes_upto,
+//                      lift_chunk_lanes, esub_lanes_ok, fsub_lanes, bsub_lanes
+//                      (lift_lanes_ok names fuse_colsum and stays with it in ntm_lift.h)
+//   ntm_dots.h         qdot_rows, dot_batched, dot_range, sub_dot, axpy_sub, gamma_row_dot,
+//                      gamma_row_dot2, dot_rows2
+//   ntm_lift.h         lift_literal, ColSums, fuse_colsum, lift_lanes_ok, lift_chunk_at,
+//                      lift_phase, free_response
+//   ntm_gram.h         gram_mfma, gram_rows*, cost_phase, scale_gram, scale_col_chunk_lanes,
+//                      diag_scale_phase, full_gram, scale_phase
+// This file still holds the constraint-row providers (Pick, StructRows, DenseRows), the small
+// dense kernels and Goldfarb-Idnani (chol_*, fwd_lanes, bwd_lanes, gi_solve), the two polishers
+// (polish_phase, polish_compact) and the QP driver (rollout_phase, plant_step, shifted_into_act,
+// gi_fallback, qp_phase).
 #pragma once
 #include <hip/hip_runtime.h>
-#include <stdint.h>
 
 #include "../../include/ntm_mpc.h"
 
+#include "ntm_prob.h"
+#include "ntm_diag.h"
+#include "ntm_base.h"
+#include "ntm_collectives.h"
+#include "ntm_ws.h"
+#include "ntm_lanes.h"
+#include "ntm_dots.h"
+#include "ntm_lift.h"
+#include "ntm_gram.h"
+
 namespace ntm {
-
-// ---------------------------------------------------------------------------
-// launch-constant problem description (derived on the host, see ntm_capi.hip)
-// ---------------------------------------------------------------------------
-struct Coef {
-    double a11c;    // (4/3)(kappa rs/(0.82 tau_r)) Ts           A.m:2
-    double za3;     // zeta * a^3 (D19, divides rho2*Ts)         A.m:2
-    double a22;     // 1 - Ts/tau_E                              A.m:2
-    double bc;      // kappa Ts eta_CD / w_dep                   B.m:2
-    double C1, C2;  // NTM_MPC_Sim.m:37
-    double wmarg2;  // w_marg^2                                  rho1.m:2
-    double wdep;    // w_dep                                     rho3.m:2
-    double Ts;
-    int rho1_sq;    // D18 switch
-};
-
-// Scenario generator (ntm_ctx_set_scenarios): per-scenario plasma parameters
-// and per-step plant disturbances, counter-based on (seed, global scenario id,
-// time index), so any sharding or batching reproduces the same realisations.
-struct Gen {
-    uint64_t seed;
-    int64_t first_id;   // global id of the launch's scenario 0
-    int k0;             // time index of the launch's first plant step
-    int dist_on;        // sigma_w or sigma_omega non-zero
-    int phys_on;        // a parameter spread non-zero
-    double sw, so;      // disturbance standard deviations (w [m], omega [rad/s])
-    double sj, sd;      // j_BS / w_dep spreads
-    // host-computed pieces of NTM_MPC_Sim.m:24,37 and B.m:2 the per-scenario
-    // C1 and b coefficient are rebuilt from (same expression order as make_prob)
-    double kTs, wsat, den, jbs, kte, wdep;
-};
-
-struct Prob {
-    Coef k;
-    int N, i_sim, mode, flags;
-    double xmin[2], xmax[2], umin, umax, Q[4], r[2], eps;
-    double du;        // input-rate bound (NTM_MODE_FULL_DU)
-    int32_t* stats;  // optional per-scenario counters (4 x B, SoA): QP solves,
-                      // GI iterations, final active rows, general (state) active rows
-    Gen g;
-    double* far;      // far workspace (HBM, far_doubles(N) per scenario) of the kernels
-                      // whose WS keeps J/R out of LDS (ws_far); null otherwise
-    double Ru;        // input weight (ABI v5): G = 2 Gamma' Om Gamma + 2 Ru I; read by the
-                      // generic (NN = 0) kernels only, the host sends Ru != 0 there (ru_on);
-                      // last, so the specialised kernels' argument layout is unchanged
-};
-
-constexpr double kInf = __builtin_huge_val();
-
-// ---------------------------------------------------------------------------
-// Counter-based scenario generator (host and device share this code, so the
-// library's host-side sampler ntm_scenario_sample returns the device's values)
-// ---------------------------------------------------------------------------
-__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-// uniform [0, 1) from (seed, global scenario id, time index k, channel ch < 256)
-__host__ __device__ __forceinline__ double gen_u01(uint64_t seed, int64_t sid, uint32_t k, uint32_t ch) {
-    uint64_t h = splitmix64(seed ^ 0xD1B54A32D192ED03ull);
-    h = splitmix64(h ^ (uint64_t)sid);
-    h = splitmix64(h ^ (((uint64_t)k << 8) | ch));
-    return (double)(h >> 11) * (1.0 / 9007199254740992.0);
-}
-// unit-variance, zero-mean Irwin-Hall(4) sample (bounded at +-2 sqrt(3)); only
-// + and * so host and device agree bit for bit.  Channel c uses sub-channels 4c..4c+3.
-__host__ __device__ __forceinline__ double gen_normal(uint64_t seed, int64_t sid, uint32_t k, uint32_t c) {
-    double s = gen_u01(seed, sid, k, 4 * c);
-    s = s + gen_u01(seed, sid, k, 4 * c + 1);
-    s = s + gen_u01(seed, sid, k, 4 * c + 2);
-    s = s + gen_u01(seed, sid, k, 4 * c + 3);
-    return (s - 2.0) * 1.7320508075688772;
-}
-constexpr uint32_t kGenParamK = 0xFFFFFFFFu;   // time index of the per-scenario parameters
-// per-scenario factor 1 + spread (2u - 1) of parameter channel c (0 j_BS, 1 w_dep)
-// (an explicit fused multiply-add: compilers may or may not contract 1 + a b, so the
-// generator fixes the rounding itself and every implementation agrees bit for bit)
-__host__ __device__ __forceinline__ double gen_factor(uint64_t seed, int64_t sid, uint32_t c, double spread) {
-    return fma(spread, 2.0 * gen_u01(seed, sid, kGenParamK, c) - 1.0, 1.0);
-}
-// scenario sid's plasma (j_BS, w_dep) into the coefficients that depend on them:
-// C1 (NTM_MPC_Sim.m:37), the B.m:2 gain and rho3's w_dep (rho3.m:2)
-__host__ __device__ __forceinline__ void gen_apply_physics(Prob& p, int64_t sid) {
-    const Gen& g = p.g;
-    const double jbs = g.jbs * gen_factor(g.seed, sid, 0, g.sj);
-    const double wdep = g.wdep * gen_factor(g.seed, sid, 1, g.sd);
-    p.k.C1 = -4.0 / 3.0 * (g.kTs * jbs * g.wsat) / g.den;
-    p.k.bc = g.kte / wdep;
-    p.k.wdep = wdep;
-}
-
-
-// 1/sqrt(x) for x > 0: v_rsq_f64 plus two Newton steps (full fp64 accuracy;
-// the pivots of the small Cholesky factorisations sit on their sequential
-// critical path, where the IEEE sqrt + division expansions cost ~25 dependent ops)
-__device__ __forceinline__ double rsqrt_nr(double x) {
-    double y = __builtin_amdgcn_rsq(x);
-    const double h = 0.5 * x;
-    y = fma(y, fma(-h * y, y, 0.5), y);
-    y = fma(y, fma(-h * y, y, 0.5), y);
-    return y;
-}
-
-// Trace build only (make trace NTM_DEBUG_SCEN=s): printf GI's iterations for
-// one scenario.  The production library compiles every trace away.
-#ifdef NTM_DEBUG_SCEN
-__shared__ int ntm_trace_grp;   // group (of this one-wave block) that owns the traced scenario
-#define NTM_TRACE_SET(s, g, l)                                                  \
-    do {                                                                        \
-        if (threadIdx.x == 0) ntm_trace_grp = -1;                               \
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");                 \
-        __builtin_amdgcn_wave_barrier();                                        \
-        if ((l) == 0 && (s) == NTM_DEBUG_SCEN) ntm_trace_grp = (g);             \
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");                 \
-        __builtin_amdgcn_wave_barrier();                                        \
-    } while (0)
-#define NTM_TRACE(...) \
-    do { if (ntm_trace_grp == (int)((threadIdx.x & 63) / P) && l == 0) printf(__VA_ARGS__); } while (0)
-#else
-#define NTM_TRACE_SET(s, g, l) (void)0
-#define NTM_TRACE(...) (void)0
-#endif
-
-// Diagnostic build only (-DNTM_STAMPS): per-phase s_memtime cycle totals,
-// summed over waves into ntm_stamps[] (read with ntm_debug_stamps).  The
-// production library compiles every stamp away.
-#define NTM_NSTAMPS 104
-#ifdef NTM_STAMPS
-extern __device__ unsigned long long ntm_stamps[NTM_NSTAMPS];
-__shared__ unsigned long long ntm_lds_stamps[NTM_NSTAMPS];   // per block (= per wave), flushed once
-#define NTM_T0(v) unsigned long long v = __builtin_amdgcn_s_memtime()
-#define NTM_ACC(i, v)                                                                   \
-    do {                                                                                \
-        unsigned long long t1_ = __builtin_amdgcn_s_memtime();                         \
-        if ((threadIdx.x & 63) == 0) ntm_lds_stamps[i] += t1_ - (v);                   \
-        v = t1_;                                                                        \
-    } while (0)
-#define NTM_CNT(i) \
-    do { if ((threadIdx.x & 63) == 0) ntm_lds_stamps[i] += 1ull; } while (0)
-#define NTM_STAMPS_INIT() \
-    do { for (int i_ = threadIdx.x; i_ < NTM_NSTAMPS; i_ += blockDim.x) ntm_lds_stamps[i_] = 0; __syncthreads(); } while (0)
-#define NTM_STAMPS_FLUSH() \
-    do { __syncthreads(); for (int i_ = threadIdx.x; i_ < NTM_NSTAMPS; i_ += blockDim.x) atomicAdd(&ntm_stamps[i_], ntm_lds_stamps[i_]); } while (0)
-#else
-#define NTM_T0(v) (void)0
-#define NTM_ACC(i, v) (void)0
-#define NTM_CNT(i) (void)0
-#define NTM_STAMPS_INIT() (void)0
-#define NTM_STAMPS_FLUSH() (void)0
-#endif
-enum { ST_LIFT, ST_COST, ST_SCALE, ST_CAND, ST_REGRAM, ST_GI, ST_POLISH, ST_ROLL, ST_GI_FACT, ST_GI_CHECK,
-       ST_GI_DIR, ST_GI_ADD, ST_GI_DROP, CN_CHECK, CN_CAND, CN_HIT,
-       ST_P_CLASS, ST_P_GRAM, ST_P_CHOL, ST_P_SCHUR, ST_P_BWD, ST_P_KKT, CN_REPAIR, CN_GIRUN,
-       ST_S_E, ST_S_Y, ST_S_K, ST_S_CHOL, ST_S_SOLVE, CN_TRY_EARLY, CN_FAIL_EARLY, CN_FAIL_LATE,
-       CN_FAIL_IT1, CN_FAIL_IT2, CN_GI_IT1, CN_GI_IT2, CN_GI_LATE, CN_TRY_IT1, CN_TRY_IT2, CN_WARM_TRY, CN_WARM_OK, CN_WARM_DEP, CN_WARM_NEG, CN_WARM_FULL, CN_ALT_TRY, CN_ALT_HIT,
-       ST_K_Y, ST_K_CHK, ST_K_GRAD, ST_K_MU, ST_K_SUB, ST_C_A, ST_C_B, ST_C_Y, ST_C_SQ,
-       ST_SC_COL, ST_SC_ROW, ST_SC_END, ST_L_COEF, ST_L_LOOP, CN_CYC_HIT, CN_CYC_SKIP,
-       CN_FK_DUAL, CN_FK_PRIMAL, CN_FK_SING, CN_FK_BOTH, ST_GI_WARM,
-       CN_CDP_DROP, CN_CDP_RES, CN_CDP_PART, CN_CDP_DIR, CN_CDP_GI,
-       CN_CDPX_SING0, CN_CDPX_SING1, CN_CDPX_BUDGET, CN_CDPX_DIR, CN_CDPX_NOVIOL, CN_CDPX_FULLDUAL, CN_CDPX_TINF,
-       CN_BORD_K0, CN_BORD_K1, CN_BORD_K2, CN_BORD_K3, CN_BORD_K4P, CN_SQ_K0, CN_SQ_K1, CN_SQ_K2, CN_SQ_COLL,
-       CN_CDPX_NAN, CN_NAN_BORD, CN_NAN_K0, CN_NAN_K1, CN_NAN_K2, CN_NAN_COLL, CN_NAN_COLL2, CN_NAN_PRIMFAIL,
-       CN_NAN_V, CN_BX_O1, CN_BX_O2, CN_BX_O3P, CN_BX_NEG, CN_BX_NOCLASS, CN_CDP_SKIP, CN_CDP_SKIPDIR };
-constexpr double kDepTol = 1e-8;   // GI linear-dependence threshold (oracle GI_DEP_TOL)
-constexpr int kMaxNT = 32;         // explicit R^{-1} in GI up to this horizon (WS::useT)
-// a failed candidate continues on Goldfarb-Idnani's dual path with certified
-// re-solves (qp_phase); up to N + kCdpExtra re-solves before GI itself takes over
-constexpr int kCdpExtra = 8;
-#ifndef NTM_SUB_PRESCALE
-#define NTM_SUB_PRESCALE 0 // 1: long horizons, echelon substitutions on accumulators scaled by 1/E[l][l] (slower)
-#endif
-#ifndef NTM_MU_AHEAD
-#define NTM_MU_AHEAD 0     // long horizons: steps ahead the multipliers' back substitution loads E (0: none)
-#endif
-#ifndef NTM_SUB_LANEIDX
-#define NTM_SUB_LANEIDX 0  // 1: the certificate's sparse pass takes rows and z by readlane (long horizons;
-#endif                     // on in the mode-3 TU: 76.9 -> 76.3 ms, while mode 2 ran 64.9 -> 65.6 ms)
-constexpr int kBoxRepairs = 16;   // box-only QPs: single-row exchanges before GI (qp_phase)   // also at N = 50: 16 / 32 were no faster in mode 2, 6% / 10% slower in mode 3
-// A constant row (Lin_i = 0: the x_0 rows of getWLc, state rows Gamma doesn't
-// reach) is violated when b_i < -kConstTol (D22, oracle CONST_ROW_TOL): the same
-// absolute 1e-9 the KKT certificate allows on a unit-scale row.  An exact test
-// turned a state that the plant step leaves one ulp outside a bound the
-// previous plan held it at (x_{k+1} = xmin - ulp) into an infeasible QP.
-constexpr double kConstTol = 1e-9;
-constexpr int kRowMulti = 256;     // WS::rinfo flag: the state row has two or more non-zeros
-constexpr int kGiWarmRejected = 100;   // gi_solve: the warm-start set was not dual feasible (caller reruns cold)
-
-// Terms per batch of the LDS contractions (loads issued ahead of their uses);
-// a translation unit may set its own (ntm_n50.hip)
-#ifndef NTM_CH
-#define NTM_CH 4
-#endif
-// Unroll count of the CH-batched chunk loops: empty (the compiler's choice, full
-// unrolling at the BASELINE horizons) unless a build sets NTM_CHUNK_UNROLL
-#define NTM_STR_(x) #x
-#define NTM_STR(x) NTM_STR_(x)
-#ifdef NTM_CHUNK_UNROLL
-#define NTM_CHUNK_PRAGMA _Pragma(NTM_STR(unroll NTM_CHUNK_UNROLL))
-#else
-#define NTM_CHUNK_PRAGMA
-#endif
-
-#define NTM_WSYNC()                                              \
-    do {                                                         \
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   \
-        __builtin_amdgcn_wave_barrier();                         \
-    } while (0)
-
-// ---------------------------------------------------------------------------
-// group collectives (width-P segments of the 64-lane wave)
-//
-// Butterflies run on DPP / permlane VALU ops, not ds_bpermute: quad_perm
-// (xor 1, xor 2), row_half_mirror (pairs the quads of an 8-lane group),
-// row_mirror (pairs the 8-lane halves of a row), v_permlane16_swap (pairs
-// the 16-lane rows of a 32-lane group) and v_permlane32_swap (pairs the wave
-// halves).  Every pairing step combines the two operands symmetrically, so
-// each lane of a group ends with the bit-identical result and every control
-// decision taken on it stays group-uniform.  Callers must be in
-// group-uniform control flow (all P lanes active).
-// ---------------------------------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v) {
-    int2 a = __builtin_bit_cast(int2, v);
-    a.x = __builtin_amdgcn_update_dpp(0, a.x, CTRL, 0xF, 0xF, false);
-    a.y = __builtin_amdgcn_update_dpp(0, a.y, CTRL, 0xF, 0xF, false);
-    return __builtin_bit_cast(double, a);
-}
-template <int CTRL>
-__device__ __forceinline__ int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false); }
-
-// (lower-row value, upper-row value) of a 16-lane (S=16) or 32-lane (S=32) pairing, same in both partners
-template <int S>
-__device__ __forceinline__ void pair_d(double v, double& lo, double& hi) {
-    int2 a = __builtin_bit_cast(int2, v);
-    int2 x, y;
-    if constexpr (S == 16) {
-        auto r0 = __builtin_amdgcn_permlane16_swap(a.x, a.x, false, false);
-        auto r1 = __builtin_amdgcn_permlane16_swap(a.y, a.y, false, false);
-        x.x = r0[0]; x.y = r1[0]; y.x = r0[1]; y.y = r1[1];
-    } else {
-        auto r0 = __builtin_amdgcn_permlane32_swap(a.x, a.x, false, false);
-        auto r1 = __builtin_amdgcn_permlane32_swap(a.y, a.y, false, false);
-        x.x = r0[0]; x.y = r1[0]; y.x = r0[1]; y.y = r1[1];
-    }
-    lo = __builtin_bit_cast(double, x);
-    hi = __builtin_bit_cast(double, y);
-}
-template <int S>
-__device__ __forceinline__ void pair_i(int v, int& lo, int& hi) {
-    if constexpr (S == 16) {
-        auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-        lo = r[0]; hi = r[1];
-    } else {
-        auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-        lo = r[0]; hi = r[1];
-    }
-}
-
-// P = 64 (one scenario per wave): results of group reductions are identical
-// in every lane; readfirstlane makes that visible to the compiler, so the
-// branches they feed become scalar branches and loop counters live in SGPRs.
-template <int P>
-__device__ __forceinline__ int uni(int v) {
-    if constexpr (P == 64) return __builtin_amdgcn_readfirstlane(v);
-    else return v;
-}
-template <int P>
-__device__ __forceinline__ double uni(double v) {
-    if constexpr (P == 64) {
-        int2 a = __builtin_bit_cast(int2, v);
-        a.x = __builtin_amdgcn_readfirstlane(a.x);
-        a.y = __builtin_amdgcn_readfirstlane(a.y);
-        return __builtin_bit_cast(double, a);
-    } else {
-        return v;
-    }
-}
-template <int P>
-__device__ __forceinline__ double gsum(double v) {
-    v = v + dpp_d<0xB1>(v);                       // quad_perm [1,0,3,2]
-    v = v + dpp_d<0x4E>(v);                       // quad_perm [2,3,0,1]
-    if constexpr (P >= 8) v = v + dpp_d<0x141>(v);   // row_half_mirror
-    if constexpr (P >= 16) v = v + dpp_d<0x140>(v);  // row_mirror
-    if constexpr (P >= 32) { double a, b; pair_d<16>(v, a, b); v = a + b; }
-    if constexpr (P >= 64) { double a, b; pair_d<32>(v, a, b); v = a + b; }
-    return uni<P>(v);
-}
-template <int P>
-__device__ __forceinline__ double gmax(double v) {
-    v = fmax(v, dpp_d<0xB1>(v));
-    v = fmax(v, dpp_d<0x4E>(v));
-    if constexpr (P >= 8) v = fmax(v, dpp_d<0x141>(v));
-    if constexpr (P >= 16) v = fmax(v, dpp_d<0x140>(v));
-    if constexpr (P >= 32) { double a, b; pair_d<16>(v, a, b); v = fmax(a, b); }
-    if constexpr (P >= 64) { double a, b; pair_d<32>(v, a, b); v = fmax(a, b); }
-    return uni<P>(v);
-}
-template <int P>
-__device__ __forceinline__ int gmaxi(int v) {
-    v = max(v, dpp_i<0xB1>(v));
-    v = max(v, dpp_i<0x4E>(v));
-    if constexpr (P >= 8) v = max(v, dpp_i<0x141>(v));
-    if constexpr (P >= 16) v = max(v, dpp_i<0x140>(v));
-    if constexpr (P >= 32) { int a, b; pair_i<16>(v, a, b); v = max(a, b); }
-    if constexpr (P >= 64) { int a, b; pair_i<32>(v, a, b); v = max(a, b); }
-    return uni<P>(v);
-}
-// Predicate collectives: does any / every lane of the group hold p?  One v_cmp
-// into a lane mask instead of gmaxi's six dependent DPP steps.  P = 64: the
-// wave's ballot, a scalar result (so the branch it feeds is a scalar branch);
-// P < 64: the ballot masked to the lane's own group.  Same contract as the
-// reductions above: group-uniform control flow, all P lanes of the group active
-// (lanes of other groups may be inactive: their ballot bits are masked off).
-template <int P>
-__device__ __forceinline__ unsigned long long group_mask() {
-    if constexpr (P == 64) return ~0ull;
-    else return ((1ull << P) - 1ull) << ((threadIdx.x & 63) & ~(P - 1));
-}
-template <int P>
-__device__ __forceinline__ bool gany(bool p) {
-    if constexpr (P == 64) return __ballot(p) != 0ull;
-    else return (__ballot(p) & group_mask<P>()) != 0ull;
-}
-template <int P>
-__device__ __forceinline__ bool gall(bool p) { return !gany<P>(!p); }
-// broadcast lane `src` of the group (src group-uniform)
-template <int P>
-__device__ __forceinline__ double gbcast(double v, int src) {
-    if constexpr (P == 64) {
-        int2 a = __builtin_bit_cast(int2, v);
-        a.x = __builtin_amdgcn_readlane(a.x, src);
-        a.y = __builtin_amdgcn_readlane(a.y, src);
-        return __builtin_bit_cast(double, a);
-    } else {
-        return __shfl(v, src, P);
-    }
-}
-
-// argmin over (v, id) with ties broken towards the smaller id; carries two
-// payload doubles.  Identical result in every lane of the group.
-__device__ __forceinline__ void amin_sel(double& v, int& id, double& a, double& b, double ov, int oid, double oa,
-                                         double ob) {
-    if (ov < v || (ov == v && oid < id)) { v = ov; id = oid; a = oa; b = ob; }
-}
-template <int CTRL>
-__device__ __forceinline__ void amin_dpp(double& v, int& id, double& a, double& b) {
-    amin_sel(v, id, a, b, dpp_d<CTRL>(v), dpp_i<CTRL>(id), dpp_d<CTRL>(a), dpp_d<CTRL>(b));
-}
-template <int S>
-__device__ __forceinline__ void amin_pair(double& v, int& id, double& a, double& b) {
-    double v0, v1, a0, a1, b0, b1;
-    int i0, i1;
-    pair_d<S>(v, v0, v1);
-    pair_i<S>(id, i0, i1);
-    pair_d<S>(a, a0, a1);
-    pair_d<S>(b, b0, b1);
-    v = v0; id = i0; a = a0; b = b0;
-    amin_sel(v, id, a, b, v1, i1, a1, b1);
-}
-template <int P>
-__device__ __forceinline__ void gargmin(double& v, int& id, double& a, double& b) {
-    amin_dpp<0xB1>(v, id, a, b);
-    amin_dpp<0x4E>(v, id, a, b);
-    if constexpr (P >= 8) amin_dpp<0x141>(v, id, a, b);
-    if constexpr (P >= 16) amin_dpp<0x140>(v, id, a, b);
-    if constexpr (P >= 32) amin_pair<16>(v, id, a, b);
-    if constexpr (P >= 64) amin_pair<32>(v, id, a, b);
-    v = uni<P>(v);
-    id = uni<P>(id);
-    a = uni<P>(a);
-    b = uni<P>(b);
-}
-// the same without payloads (same comparison, same tie rule: smaller id)
-__device__ __forceinline__ void amin_sel(double& v, int& id, double ov, int oid) {
-    if (ov < v || (ov == v && oid < id)) { v = ov; id = oid; }
-}
-template <int S>
-__device__ __forceinline__ void amin_pair(double& v, int& id) {
-    double v0, v1;
-    int i0, i1;
-    pair_d<S>(v, v0, v1);
-    pair_i<S>(id, i0, i1);
-    v = v0; id = i0;
-    amin_sel(v, id, v1, i1);
-}
-template <int P>
-__device__ __forceinline__ void gargmin(double& v, int& id) {
-    amin_sel(v, id, dpp_d<0xB1>(v), dpp_i<0xB1>(id));
-    amin_sel(v, id, dpp_d<0x4E>(v), dpp_i<0x4E>(id));
-    if constexpr (P >= 8) amin_sel(v, id, dpp_d<0x141>(v), dpp_i<0x141>(id));
-    if constexpr (P >= 16) amin_sel(v, id, dpp_d<0x140>(v), dpp_i<0x140>(id));
-    if constexpr (P >= 32) amin_pair<16>(v, id);
-    if constexpr (P >= 64) amin_pair<32>(v, id);
-    v = uni<P>(v);
-    id = uni<P>(id);
-}
-
-// ---------------------------------------------------------------------------
-// L0 / L1: scheduling parameters and LPV coefficients
-// ---------------------------------------------------------------------------
-// rho1.m:2, rho2.m:2, rho3.m:2-3 (same operation order as the oracle)
-__device__ __forceinline__ void rho_eval(const Coef& k, double w, double om,
-                                         double& r1, double& r2, double& r3) {
-    r1 = 1.0 / ((k.rho1_sq ? w * w : w) + k.wmarg2);
-    r2 = (w * w) / om;
-    double ws = w / k.wdep;
-    r3 = (0.25 + 0.24 * ws) / (1 + 1.5 * ws + 0.43 * (ws * ws) + 0.64 * (ws * ws * ws));
-}
-// A.m:2 entries a11, a21 (a12 = 0, a22 = k.a22); B.m:2 as the column [b; 0] (D5)
-__device__ __forceinline__ double coef_a11(const Coef& k, double r1) { return k.a11c * r1 + 1; }
-__device__ __forceinline__ double coef_a21(const Coef& k, double r2) { return (r2 * k.Ts) / k.za3; }
-__device__ __forceinline__ double coef_b(const Coef& k, double r3) { return k.bc * r3; }
-
-// ---------------------------------------------------------------------------
-// per-scenario LDS workspace (all offsets in doubles; see ws_doubles())
-// ---------------------------------------------------------------------------
-// NN > 0: horizon fixed at compile time (strides become immediates, loops
-// unroll); NN == 0: runtime horizon (generic kernels).
-// GEN: the kernel is built with the scenario generator (per-scenario plasma in
-// the workspace, plant disturbances); without it those paths are compiled out
-// (they cost the N=20 step kernel 2% through register allocation even when off)
-//
-// FAR (ws_far: N = 20 and N > 32): the J/R(/T) block (GI's factors and the
-// bordered KKT factor) lives in a per-scenario HBM block (Prob::far, L2-resident
-// while the wave runs) instead of LDS, and the echelon re-solve's sorted E moves
-// to an LDS block of its own, packed lower triangular (row t at t(t+1)/2).  The
-// certified re-solve of an echelon set, the common path, stays LDS-only; GI and
-// the bordered elimination read and write HBM.  More scenarios fit a CU:
-//   N = 50: 78.5 -> 47.9 KB, 3 scenarios per CU instead of 2 (one wave on each
-//           of 3 SIMDs instead of 2; the kernel has the 512-register budget of
-//           one wave per SIMD either way);
-//   N = 20: 20.4 -> 12.0 KB, 12 scenarios per CU instead of 8, i.e. 3 waves per
-//           SIMD, which the kernel is built for (168 VGPRs, NTM_WAVES_PER_EU).
-// Neither pays without the occupancy: at 2 waves per SIMD the N = 20 kernel is 6%
-// slower with its GI in HBM.  NTM_FAR_N20=0 builds the all-LDS N = 20 kernel.
-#ifndef NTM_FAR_N20
-#define NTM_FAR_N20 1
-#endif
-__host__ __device__ constexpr bool ws_far(int NN) { return NN > 32 || (NTM_FAR_N20 && NN == 20); }
-// The slim far layout (N = 20 far, round 5): 16 scenarios per CU (4 waves per SIMD,
-// <= 10,240 B of LDS each) instead of 12.  What leaves LDS: the A/B coefficient
-// arrays (each lane keeps its stage's in registers, broadcast by readlane in the
-// lift), Phi and Lambda (the lift runs the free response e = Phi x_k + Lambda as a
-// recursion of its own, one more lane; 2N of the old Phi stay as the re-solve's
-// scratch), the hoisted V-space box (vlo / vhi, recomputed from D), and the
-// diagonal reciprocals of the bordered factor and GI's Cholesky (ldi / kdi), which
-// move to the far block with the rate-row norms (idun, mode 3 never runs here).
-// The Om products are the identity (qi_on), so the certificate's Om y is y itself.
-// The slim N = 50 layout (round 5): 4 scenarios per CU (one wave on each SIMD) instead
-// of 3, <= 40,960 B each.  Besides the N = 20 slim changes (its Om is general: the
-// certificate's Om y goes to the 2N of scratch), rho, U_old and the two carried
-// active sets move to the far block (touched once or twice per LPV iteration).
-__host__ __device__ constexpr bool ws_slim(int N, bool far) {
-    return far && (N == 20 || N == 50);
-}
-__host__ __device__ constexpr bool slim_far(int N, bool far) { return ws_slim(N, far) && N == 50; }
-// the slim N = 20 layout keeps a11 / a21 in LDS after all (2N doubles, paid for by
-// active-row flags for the 6N+4 getWLc rows only: mode 3 never runs on these kernels)
-__host__ __device__ constexpr int slim_ab(int N, bool far) { return N == 20 && ws_slim(N, far) ? 2 : 0; }
-
-template <int NN, bool GEN = false, bool FAR = ws_far(NN)>
-struct WS {
-    static constexpr int kNN = NN;
-    static constexpr bool kGen = GEN;
-    static constexpr bool kFar = FAR;
-    static constexpr bool kSlim = ws_slim(NN, FAR);
-    int N_rt;
-    double* base;
-    double* far;       // kFar: this scenario's J/R block in HBM
-    __device__ __forceinline__ int n() const { return NN > 0 ? NN : N_rt; }
-    __device__ __forceinline__ int ldj() const { return n() | 1; }
-    __device__ __forceinline__ int ldg() const { return 2 * n(); }
-    // double offsets of each array (n() is launch-uniform, so these fold to scalar math)
-    static constexpr int kAB = slim_ab(NN, FAR);           // kSlim: a11 / a21 (N each) in LDS
-    static constexpr bool kSF = slim_far(NN, FAR);          // rho, U_old, cand in the far block
-    static constexpr int kRL = kSF ? 0 : 3;                 // kSlim: rho's N-vectors in LDS
-    __device__ __forceinline__ int oJ() const { return (kSlim ? kRL + 4 + kAB : 14) * n() + n() * (n() + 1); }
-    __device__ __forceinline__ int oR() const { return oJ() + n() * ldj(); }
-    // T = R^{-1} is kept for N <= kMaxNT only: at long horizons its N^2 doubles would
-    // halve the scenarios per CU, and the dual direction falls back to back substitution.
-    // The far layouts keep no T either: maintaining it in HBM (a column per add, a
-    // Givens sweep and a row shift per drop) cost more than the back substitution
-    // on R saves (N = 20, 3 waves per SIMD: 10.09 -> 9.99 ms per step-batch without it)
-    __device__ __forceinline__ bool useT() const { return !kFar && n() <= kMaxNT; }
-    __device__ __forceinline__ int oT() const { return oR() + (n() + 1) * ldj(); }
-    // kFar: the E block (packed lower-triangular E, then 2(N+1) ints) replaces J/R/T in LDS
-    __device__ __forceinline__ int oV() const {
-        if constexpr (kFar) return oJ() + (n() * (n() + 1)) / 2 + (n() + 1);
-        else return oT() + (useT() ? n() * ldj() : 0);   // vector block
-    }
-    __device__ __forceinline__ double* rho() const {                                  // 3N (3xN col-major)
-        if constexpr (kSF) return far + n() * ldj() + (n() + 1) * ldj() + 3 * n();
-        else return base;
-    }
-    // (kSlim: no a11 / a21 / bb / Lam, Phi is 2N of scratch; never called there)
-    __device__ __forceinline__ double* a11() const { return base + 3 * n(); }         // n()
-    __device__ __forceinline__ double* a21() const { return base + 4 * n(); }         // n()
-    __device__ __forceinline__ double* bb() const { return base + 5 * n(); }          // n()
-    __device__ __forceinline__ double* Phi() const { return base + (kSlim ? kRL + kAB : 6) * n(); }   // 4N Phi_i (2x2 col-major)
-    __device__ __forceinline__ double* Lam() const { return base + 10 * n(); }        // 2N
-    __device__ __forceinline__ double* e() const { return base + (kSlim ? kRL + 2 + kAB : 12) * n(); }    // 2N free response
-    // Gamma, block-lower-triangular and packed by column: column j holds rows 2j..2N-1
-    __device__ __forceinline__ double* Gt() const { return base + (kSlim ? kRL + 4 + kAB : 14) * n(); }   // n()(n()+1)
-    __device__ __forceinline__ int gidx(int r, int j) const { return j * (2 * n() - j + 1) + r - 2 * j; }
-    __device__ __forceinline__ double& gt(int r, int j) const { return Gt()[gidx(r, j)]; }   // r >= 2j
-    __device__ __forceinline__ double* J() const {                                   // n() x ldj() row-major
-        if constexpr (kFar) return far;
-        else return base + oJ();
-    }
-    // R: n() rows x (n()+1) columns col-major; the polish keeps its Schur complement
-    // K in the strict upper triangle: K(a, c), a >= c, at R[c + (a+1) ldj()]
-    __device__ __forceinline__ double* R() const {
-        if constexpr (kFar) return far + n() * ldj();
-        else return base + oR();
-    }
-    // T = R^{-1} of the GI factorisation (upper triangular, row-major n() x ldj();
-    // zero outside the leading q x q block), so the dual direction is a matvec
-    __device__ __forceinline__ double* T() const {
-        if constexpr (kFar) return far;   // never dereferenced: far layouts keep no T (useT)
-        else return base + oT();
-    }
-    // element (r, c) of J (and of T) at J()[r jr() + c jc()]: row-major
-    __device__ __forceinline__ int jr() const { return ldj(); }
-    __device__ __forceinline__ int jc() const { return 1; }
-    // packed bordered KKT factor (rows 0..nt, row nt the right-hand side), entry
-    // (r, c), c <= r, at J()[brow(r) + bcol(c, nt)]: row-major (row r at r(r+1)/2)
-    __device__ __forceinline__ int brow(int r) const { return (r * (r + 1)) / 2; }
-    __device__ __forceinline__ int bcol(int c, int /*nt*/) const { return c; }
-    // echelon re-solve: sorted E (entry (t, u), u <= t, at Ep()[eidx(t, u)]) and the
-    // GI's triangular factor R (and, before it, the scaled Gram G~ and its Cholesky
-    // factor L): element (i, j) at R()[i + j ldj()], or, in the far layouts
-    // (kGiLds), in the LDS E block, which is dead while GI runs (the echelon
-    // re-solve's sorted E is rebuilt by every re-solve): the lower triangle row-major
-    // packed (row i at i(i+1)/2, so G~ / L rows are contiguous), the upper triangle
-    // column-major packed in the same slots ((i, j) and (j, i) share one: the lower
-    // triangle is dead once R is being built, the factor below R's subdiagonal is
-    // never touched), and R's superdiagonal (i, i+1) apart after the triangle, so
-    // that a drop's upper-Hessenberg subdiagonal (i+1, i) does not collide with it.
-    // N(N+1)/2 + N-1 doubles <= the E block's N(N+1)/2 + N+1.  GI's back and forward
-    // substitutions, adds and drops then run on LDS instead of the HBM far block
-    // (J stays there).  kGiLdsL: G~ and L; kGiLds: R
-    static constexpr bool kGiLdsL = FAR;
-    static constexpr bool kGiLds = FAR;
-    __device__ __forceinline__ int gio(int i, int j) const {
-        if (i >= j) return (i * (i + 1)) / 2 + j;
-        if (i == j - 1) return (n() * (n() + 1)) / 2 + i;
-        return (j * (j + 1)) / 2 + i;
-    }
-    __device__ __forceinline__ double& gr(int i, int j) const {
-        if constexpr (kGiLds) return Ep()[gio(i, j)];
-        else return R()[i + j * ldj()];
-    }
-    __device__ __forceinline__ double& grL(int i, int j) const {   // lower triangle, i >= j
-        if constexpr (kGiLdsL) return Ep()[(i * (i + 1)) / 2 + j];
-        else return R()[i + j * ldj()];
-    }
-    // row i of the lower triangle (elements (i, 0..i) at stride grs())
-    __device__ __forceinline__ double* grow(int i) const {
-        if constexpr (kGiLdsL) return Ep() + (i * (i + 1)) / 2;
-        else return R() + i;
-    }
-    __device__ __forceinline__ int grs() const { return kGiLdsL ? 1 : ldj(); }
-    // row permutation / column owner ints (2(N+1)); in the J/R block unless kFar
-    __device__ __forceinline__ double* Ep() const {
-        if constexpr (kFar) return base + oJ();
-        else return J();
-    }
-    __device__ __forceinline__ int eidx(int t, int u) const {
-        if constexpr (kFar) return (t * (t + 1)) / 2 + u;
-        else return t * ldj() + u;
-    }
-    __device__ __forceinline__ int* permi() const {
-        if constexpr (kFar) return reinterpret_cast<int*>(base + oJ() + (n() * (n() + 1)) / 2);
-        else return reinterpret_cast<int*>(R());
-    }
-    // 2N ints (in 2N doubles of space): per state row r, (last column j with
-    // Gamma_rj != 0) + 1, plus kRowMulti if it has two or more non-zeros
-    __device__ __forceinline__ int* rinfo() const { return reinterpret_cast<int*>(base + oV()); }
-    // kSlim: the 2N rinfo ints take N doubles, and vlo / vhi / ldi / kdi / idun leave LDS
-    static constexpr int kRi = kSlim ? 1 : 2;                // doubles of rinfo per N
-    __device__ __forceinline__ double* F() const { return base + oV() + kRi * n(); }         // n()  F~
-    __device__ __forceinline__ double* D() const { return base + oV() + (kRi + 1) * n(); }   // n()  Jacobi scaling
-    __device__ __forceinline__ double* V() const { return base + oV() + (kRi + 2) * n(); }   // n()  scaled variables
-    __device__ __forceinline__ double* d() const { return base + oV() + (kRi + 3) * n(); }   // n()
-    __device__ __forceinline__ double* np() const { return base + oV() + (kRi + 4) * n(); }  // n()  GI normal
-    __device__ __forceinline__ double* hv() const { return base + oV() + (kRi + 5) * n(); }  // n()  Householder / polish
-    __device__ __forceinline__ double* Vb() const { return base + oV() + (kRi + 6) * n(); }  // n()  polish fixed (V)
-    __device__ __forceinline__ double* Uf() const { return base + oV() + (kRi + 7) * n(); }  // n()  polish fixed (U)
-    __device__ __forceinline__ double* uu() const { return base + oV() + (kRi + 8) * n(); }  // n()+1 multipliers
-    __device__ __forceinline__ double* xp() const { return base + oV() + (kRi + 9) * n() + 1; }    // 2(n()+1) rollout
-    __device__ __forceinline__ double* U() const { return base + oV() + (kRi + 11) * n() + 3; }    // n()
-    static constexpr int kUo = kSF ? 0 : 1;                  // U_old's N-vector in LDS
-    __device__ __forceinline__ double* Uold() const {                                              // n()
-        if constexpr (kSF) return rho() + 3 * n();
-        else return base + oV() + (kRi + 12) * n() + 3;
-    }
-    __device__ __forceinline__ double* dr() const { return base + oV() + (kRi + 12 + kUo) * n() + 3; }    // N: d masked to b < q (GI)
-    __device__ __forceinline__ double* irn() const { return base + oV() + (kRi + 13 + kUo) * n() + 3; }   // 2N: 1/rn_r (0: const row)
-    __device__ __forceinline__ double* ssg() const { return base + oV() + (kRi + 15 + kUo) * n() + 3; }   // N: sign of general row s
-    // per-QP constants hoisted out of the solver loops (not kSlim: recomputed from D)
-    __device__ __forceinline__ double* vlo() const { return base + oV() + (kRi + 17) * n() + 3; }   // N: umin/D_j
-    __device__ __forceinline__ double* vhi() const { return base + oV() + (kRi + 18) * n() + 3; }   // N: umax/D_j
-    // 1/L(k,k) (Cholesky), 1/K(k,k) (Schur), contiguous; 1/|D (e_i - e_{i-1})|: in the far block when kSlim
-    __device__ __forceinline__ double* ldi() const {
-        if constexpr (kSlim) return far + n() * ldj() + (n() + 1) * ldj();
-        else return base + oV() + (kRi + 19) * n() + 3;
-    }
-    __device__ __forceinline__ double* kdi() const { return ldi() + n(); }
-    __device__ __forceinline__ double* idun() const {
-        if constexpr (kSlim) return ldi() + 2 * n();
-        else return base + oV() + (kRi + 21) * n() + 3;
-    }
-    static constexpr int kVec = kSlim ? 17 + kUo : 24;        // N-vectors of the block (+ 3 + 3 scn)
-    // this scenario's C1, B.m gain and w_dep (scenario generator; read only when pb.g.phys_on)
-    __device__ __forceinline__ double* scn() const { return base + oV() + kVec * n() + 3; }
-    __device__ __forceinline__ int* act() const { return reinterpret_cast<int*>(base + oV() + kVec * n() + 6); }
-    __device__ __forceinline__ int* sidx() const { return act() + n() + 1; }
-    static constexpr int kCL = kSF ? 0 : 2;                  // the carried sets' (N+1)-int tables in LDS
-    __device__ __forceinline__ int* cand() const {                                   // 2(n()+1): last two active sets
-        if constexpr (kSF) return reinterpret_cast<int*>(Uold() + n());
-        else return act() + 2 * (n() + 1);
-    }
-    __device__ __forceinline__ int* fidx() const { return act() + (2 + kCL) * (n() + 1); }   // n()+1: free variables (polish)
-    __device__ __forceinline__ int* srw() const { return act() + (3 + kCL) * (n() + 1); }    // n()+1: state row of general row s
-    __device__ __forceinline__ unsigned char* fx() const {
-        return reinterpret_cast<unsigned char*>(act() + (4 + kCL) * (n() + 1));
-    }
-    __device__ __forceinline__ unsigned char* aflag() const { return fx() + n(); }
-};
-
-__host__ __device__ constexpr int ldj_of(int N) { return N | 1; }
-// the J/R block of a far layout, in HBM per scenario (no T: WS::useT)
-__host__ __device__ constexpr int far_doubles(int N) {
-    // + ldi, kdi, idun (slim); + rho, U_old and the carried sets' 2(N+1) ints (slim_far)
-    return N * ldj_of(N) + (N + 1) * ldj_of(N) + (ws_slim(N, true) ? 3 * N : 0) +
-           (slim_far(N, true) ? 4 * N + (N + 1) : 0);
-}
-__host__ __device__ constexpr int ws_doubles(int N, bool far = false) {
-    // LDS: the E block (far), or J, R and (N <= kMaxNT) T
-    const int jr = far ? (N * (N + 1)) / 2 + (N + 1) : (N <= kMaxNT ? 2 : 1) * N * ldj_of(N) + (N + 1) * ldj_of(N);
-    const int rl = slim_far(N, far) ? 0 : 3, uo = slim_far(N, far) ? 0 : 1;
-    return ws_slim(N, far) ? (rl + 4 + slim_ab(N, far)) * N + N * (N + 1) + jr + (17 + uo) * N + 6
-                           : 14 * N + N * (N + 1) + jr + 24 * N + 6;
-}
-// workspace bytes with room for `rows` active-row flags: the structured rows of
-// the MPC step are at most 8N+2 (getWLc 6N+4 plus 2(N-1) rate rows); a dense
-// quadprog problem (k_qp) may carry more
-__host__ __device__ constexpr int ws_bytes_rows(int N, int rows, bool far = false) {
-    const int fmin = slim_ab(N, far) ? 6 * N + 4 : 8 * N + 4;      // (slim_ab: no rate rows)
-    const int flags = rows > fmin ? rows : fmin;
-    int b = ws_doubles(N, far) * 8 + (slim_far(N, far) ? 4 : 6) * (N + 1) * 4 + N + flags;   // ..., fx (N), aflag
-    return (b + 15) & ~15;
-}
-__host__ __device__ constexpr int ws_bytes(int N, bool far = false) {
-    return ws_bytes_rows(N, slim_ab(N, far) ? 6 * N + 4 : 8 * N + 4, far);
-}
-static_assert(16 * ws_bytes(20, true) <= 160 * 1024, "slim N = 20: 16 scenarios per CU");
-static_assert(4 * ws_bytes(50, true) <= 160 * 1024, "slim N = 50: 4 scenarios per CU");
-
-// s: the scenario's index in the launch (its far block, when the WS has one)
-template <int NN, bool GEN = false, bool FAR = ws_far(NN)>
-__device__ inline WS<NN, GEN, FAR> ws_carve(char* base, int N, const Prob* pb = nullptr, int64_t s = 0) {
-    WS<NN, GEN, FAR> w;
-    w.N_rt = N;
-    w.base = reinterpret_cast<double*>(base);
-    w.far = nullptr;
-    if constexpr (FAR) w.far = pb->far + s * (int64_t)far_doubles(N);
-    return w;
-}
-
-// The scenario's LPV coefficients: the launch constants, with C1, the B.m gain and
-// w_dep taken from the workspace when the scenario generator varies the plasma
-// (written once per launch by scn_store).  Keeping the launch constants in the
-// kernel arguments matters: a copy of the whole Prob per scenario cost the N=20
-// step kernel 100 B of scratch per lane and 20 more spilled SGPRs.
-// The input weight R_u: its term 2 Ru I of the Hessian enters the
-// Gram diagonal (scaling, GI's full G~, the re-solve's G~_FF), the echelon k = 1 line
-// search and the certificate's gradient.  Compiled into the generic kernels only
-// (ru_on): the specialised N = 10 / 20 / 50 kernels keep their register allocation,
-// and the host dispatches a launch with Ru != 0 to the generic ones (as D4 / D6)
-template <class W>
-__device__ __forceinline__ constexpr bool ru_on() { return W::kNN == 0; }
-template <class W>
-__device__ __forceinline__ double ru_of(const Prob& pb) {
-    if constexpr (ru_on<W>()) return pb.Ru;
-    else return 0.0;
-}
-// The reference's stage weight is Q = I (NTM_MPC_Sim.m:59, Omega = blkdiag(Q, ...)).
-// The specialised kernels (compile-time horizons) assume it, so their Om products
-// are the identity (bit for bit what 1 x + 0 y gives for finite data) and the
-// weight's four launch constants leave their scalar registers; a launch with any
-// other Q runs on the generic kernels (host dispatch, like Ru and D4 / D6).
-#ifndef NTM_QI_MAXN
-#define NTM_QI_MAXN 32     // compile-time horizons up to this one assume Q = I (qi_on): N = 10, 20 (at
-                           // N = 50 it cost 11% through register allocation, A/B on one box)
-#endif
-template <class W>
-__device__ __forceinline__ constexpr bool qi_on() { return W::kNN > 0 && NTM_QI_MAXN >= W::kNN; }
-template <bool QI>
-struct OmQ {                       // x -> Q x for one stage's 2-vector
-    double q00, q01, q10, q11;
-    __device__ __forceinline__ explicit OmQ(const double* Q) {
-        if constexpr (QI) { q00 = 1.0; q01 = 0.0; q10 = 0.0; q11 = 1.0; }
-        else { q00 = Q[0]; q01 = Q[1]; q10 = Q[2]; q11 = Q[3]; }
-    }
-    __device__ __forceinline__ double o0(double x0, double x1) const {
-        if constexpr (QI) return x0;
-        else return q00 * x0 + q01 * x1;
-    }
-    __device__ __forceinline__ double o1(double x0, double x1) const {
-        if constexpr (QI) return x1;
-        else return q10 * x0 + q11 * x1;
-    }
-};
-__device__ __forceinline__ bool gen_phys(const Prob& pb) { return pb.g.phys_on != 0; }
-__device__ __forceinline__ bool gen_dist(const Prob& pb) { return pb.g.dist_on != 0; }
-template <class W>
-__device__ __forceinline__ Coef scn_coef(const Prob& pb, const W& w) {
-    Coef k = pb.k;
-    if (W::kGen && gen_phys(pb)) {
-        k.C1 = w.scn()[0];
-        k.bc = w.scn()[1];
-        k.wdep = w.scn()[2];
-    }
-    return k;
-}
-template <class W>
-__device__ __forceinline__ void scn_store(const Prob& pb, const W& w, int64_t gid, int l) {
-    if (W::kGen && gen_phys(pb) && l == 0) {
-        Prob q = pb;
-        gen_apply_physics(q, gid);
-        w.scn()[0] = q.k.C1;
-        w.scn()[1] = q.k.bc;
-        w.scn()[2] = q.k.wdep;
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Batched LDS contractions.  The long masked fixed-trip loops below are LDS
-// latency chains when the scheduler interleaves each load with its use (the
-// 256-VGPR kernels leave it no room to hoist); these helpers issue CH rows of
-// loads, fence the scheduler, then consume them, so one LDS round trip serves
-// CH terms.  Same terms in the same order as the plain loops.  Loads of the
-// tail chunk past n are skipped (zero), never read out of the workspace.
-// ---------------------------------------------------------------------------
-// sum_{imin <= i < n} a_i' Q b_i over 2-vectors stored at stride 2
-template <int CH, class OM>
-__device__ __forceinline__ double qdot_rows(const double* a, const double* b, int n, int imin, const OM& om) {
-    double s = 0.0;
-    NTM_CHUNK_PRAGMA
-    for (int i0 = 0; i0 < n; i0 += CH) {
-        double a0[CH], a1[CH], b0[CH], b1[CH];
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int i = i0 + u;
-            const bool in = i < n;
-            a0[u] = in ? a[2 * i] : 0.0;
-            a1[u] = in ? a[2 * i + 1] : 0.0;
-            b0[u] = in ? b[2 * i] : 0.0;
-            b1[u] = in ? b[2 * i + 1] : 0.0;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int i = i0 + u;
-            const double o0 = om.o0(b0[u], b1[u]);
-            const double o1 = om.o1(b0[u], b1[u]);
-            const double t = a0[u] * o0 + a1[u] * o1;
-            s += (i >= imin && i < n) ? t : 0.0;
-        }
-    }
-    return s;
-}
-// sum_{j < n} a[j sa] b[j sb] (strided LDS vectors)
-template <int CH>
-__device__ __forceinline__ double dot_batched(const double* a, int sa, const double* b, int sb, int n) {
-    double y = 0.0;
-    NTM_CHUNK_PRAGMA
-    for (int j0 = 0; j0 < n; j0 += CH) {
-        double x[CH], z[CH];
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int j = j0 + u;
-            const bool in = j < n;
-            x[u] = in ? a[j * sa] : 0.0;
-            z[u] = in ? b[j * sb] : 0.0;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < CH; ++u) y += x[u] * z[u];
-    }
-    return y;
-}
-// sum_{lo <= j < hi} a[j sa] b[j sb] (per-lane bounds; terms added in index order)
-template <int CH>
-__device__ __forceinline__ double dot_range(const double* a, int sa, const double* b, int sb, int lo, int hi) {
-    double y = 0.0;
-    NTM_CHUNK_PRAGMA
-    for (int j0 = lo; j0 < hi; j0 += CH) {
-        double x[CH], z[CH];
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int j = j0 + u;
-            const bool in = j < hi;
-            x[u] = in ? a[j * sa] : 0.0;
-            z[u] = in ? b[j * sb] : 0.0;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < CH; ++u) y += x[u] * z[u];
-    }
-    return y;
-}
-// s - sum_{lo <= j < hi} a[j sa] b[j sb], the terms subtracted one by one in index order
-template <int CH>
-__device__ __forceinline__ double sub_dot(double s, const double* a, int sa, const double* b, int sb, int lo, int hi) {
-    NTM_CHUNK_PRAGMA
-    for (int j0 = lo; j0 < hi; j0 += CH) {
-        double x[CH], z[CH];
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int j = j0 + u;
-            const bool in = j < hi;
-            x[u] = in ? a[j * sa] : 0.0;
-            z[u] = in ? b[j * sb] : 0.0;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < CH; ++u) s -= x[u] * z[u];
-    }
-    return s;
-}
-// a[j] -= f b[j] for lo <= j < hi, the loads of CH entries issued ahead of their stores
-template <int CH>
-__device__ __forceinline__ void axpy_sub(double* a, const double* b, double f, int lo, int hi, int sa = 1) {
-    NTM_CHUNK_PRAGMA
-    for (int j0 = lo; j0 < hi; j0 += CH) {
-        double x[CH], z[CH];
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int j = j0 + u;
-            const bool in = j < hi;
-            x[u] = in ? a[j * sa] : 0.0;
-            z[u] = in ? b[j] : 0.0;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < CH; ++u)
-            if (j0 + u < hi) a[(j0 + u) * sa] = x[u] - f * z[u];
-    }
-}
-// ---------------------------------------------------------------------------
-// Lane-masked accumulation (N = 20, one scenario per wave, row or column =
-// lane).  The triangular passes over the packed Gamma sum N fixed terms per
-// lane and zero the ones outside the lane's row or column with a select (two
-// v_cndmask and a v_cmp per fp64 term).  The lanes a term belongs to are
-// contiguous and known at compile time (lanes >= 2j for the term j of a row
-// pass, lanes <= i for the term i of a column pass), so the one accumulating
-// instruction runs with EXEC narrowed to them instead: a lane that is off keeps
-// its accumulator, which is what y + (+-0) leaves for any y other than -0.0.
-//   Row dots (v_fmac_f64; a row's own terms come first, the masked ones after):
-// the two forms differ on a lane the term does not belong to when x is not
-// finite (NaN from 0 x against y untouched) and when y is -0.0 there (+0.0 from
-// -0.0 + 0 against -0.0); never on a lane the term belongs to.
-//   Column passes (v_add_f64 of a term formed on every lane; the select form adds
-// +0.0, never a product with 0): a column's masked terms come first, onto the
-// +0.0 the sum starts from, so no accumulator is -0.0 where a term is masked
-// and the two forms are identical, whatever the data.
-//   Measured on the far N = 20 kernel at B = 1e5 (A/B on one box, three runs
-// each): the row dots 6.057 -> 5.962 ms per step-batch, the certificate's
-// gradient and the scaling pass's column pass on top 5.949 -> 5.772 ms; the
-// scaling pass's row pass (masked adds of the squares, the last / cnt tracking
-// left select-based) 5.762 -> 5.792 ms: not kept.  qdot_rows' callers take the
-// column from fidx[], not from the lane, so it keeps its selects.
-// One asm block per chunk of five terms: EXEC is saved on entry, every mask is
-// ANDed with the saved value (lanes off on entry stay off), only SALU builds
-// the masks (s_lshl_b64 / s_lshr_b64 from -1), and EXEC is restored before the
-// block ends.  Wait states: a SALU write of EXEC needs none before a VALU (the
-// sequence the compiler emits for every divergent branch), nor does a VALU
-// write of an SGPR pair before the SALU that reads it (v_cmp then s_and); the
-// blocks have no DPP, lane access, v_div_fmas, EXECZ / VCCZ read or memory
-// instruction, the cases the ISA lists for EXEC and VALU-written SGPRs.
-// After a block: the compiler's hazard pass does not see the block's last VALU
-// write, and a DPP read of that VGPR needs two wait states; the restoring
-// s_mov_b64 is one, the s_nop 0 behind it the second, so whatever the scheduler
-// places next (a DPP or lane read of the sum included) is covered.
-// ---------------------------------------------------------------------------
-template <int P, int CH, class W>
-__device__ __forceinline__ constexpr bool lane_masked_ok() {
-    // row r / column l sits on lane r / l: one scenario per wave, 2N <= 64, one trip of `r += P`.
-    // The far build only: its chunks hold five terms, which is what the asm blocks are written
-    // for; the all-LDS builds batch four terms per round trip (ntm_n20near.hip) and run their
-    // scaling pass split over idle lanes
-    return P == 64 && CH == 5 && W::kNN == 20 && W::kFar;
-}
-// EXEC = entry EXEC & (lanes >= s<k>) / (lanes <= 63 - s<k>), s<k> a compile-time shift
-#define NTM_LANES_FROM(k) "s_lshl_b64 %[m], -1, %[s" #k "]\n\ts_and_b64 exec, %[sv], %[m]\n\t"
-#define NTM_LANES_UPTO(k) "s_lshr_b64 %[m], -1, %[s" #k "]\n\ts_and_b64 exec, %[sv], %[m]\n\t"
-#define NTM_SHIFTS_FROM(J0) \
-    [s0] "n"(2 * (J0)), [s1] "n"(2 * (J0) + 2), [s2] "n"(2 * (J0) + 4), [s3] "n"(2 * (J0) + 6), [s4] "n"(2 * (J0) + 8)
-#define NTM_SHIFTS_UPTO(I0) \
-    [s0] "n"(63 - (I0)), [s1] "n"(62 - (I0)), [s2] "n"(61 - (I0)), [s3] "n"(60 - (I0)), [s4] "n"(59 - (I0))
-#define NTM_V5(n, a) [n##0] "v"(a[0]), [n##1] "v"(a[1]), [n##2] "v"(a[2]), [n##3] "v"(a[3]), [n##4] "v"(a[4])
-// y += g[u] x[u] on lanes >= 2 (J0 + u), u = 0..4 in order, one v_fmac_f64 each
-template <int J0>
-__device__ __forceinline__ void fmac5_lanes_from(double& y, const double (&g)[5], const double (&x)[5]) {
-    unsigned long long sv, m;
-#define NTM_TERM(k) NTM_LANES_FROM(k) "v_fmac_f64_e32 %[y], %[g" #k "], %[x" #k "]\n\t"
-    asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_TERM(0) NTM_TERM(1) NTM_TERM(2) NTM_TERM(3) NTM_TERM(4)
-                 "s_mov_b64 exec, %[sv]\n\ts_nop 0"
-                 : [y] "+v"(y), [sv] "=&s"(sv), [m] "=&s"(m)
-                 : NTM_V5(g, g), NTM_V5(x, x), NTM_SHIFTS_FROM(J0)
-                 : "scc");
-#undef NTM_TERM
-}
-// the same for two accumulators that share g and the masks: y1 += g x1, then y2 += g x2, per term
-template <int J0>
-__device__ __forceinline__ void fmac5x2_lanes_from(double& y1, double& y2, const double (&g)[5],
-                                                   const double (&x1)[5], const double (&x2)[5]) {
-    unsigned long long sv, m;
-#define NTM_TERM(k) \
-    NTM_LANES_FROM(k) "v_fmac_f64_e32 %[y1], %[g" #k "], %[a" #k "]\n\tv_fmac_f64_e32 %[y2], %[g" #k "], %[b" #k "]\n\t"
-    asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_TERM(0) NTM_TERM(1) NTM_TERM(2) NTM_TERM(3) NTM_TERM(4)
-                 "s_mov_b64 exec, %[sv]\n\ts_nop 0"
-                 : [y1] "+v"(y1), [y2] "+v"(y2), [sv] "=&s"(sv), [m] "=&s"(m)
-                 : NTM_V5(g, g), NTM_V5(a, x1), NTM_V5(b, x2), NTM_SHIFTS_FROM(J0)
-                 : "scc");
-#undef NTM_TERM
-}
-// s += t[u] on lanes <= I0 + u (column pass), one v_add_f64 each
-template <int I0>
-__device__ __forceinline__ void fadd5_lanes_upto(double& s, const double (&t)[5]) {
-    unsigned long long sv, m;
-#define NTM_TERM(k) NTM_LANES_UPTO(k) "v_add_f64 %[y], %[y], %[t" #k "]\n\t"
-    asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_TERM(0) NTM_TERM(1) NTM_TERM(2) NTM_TERM(3) NTM_TERM(4)
-                 "s_mov_b64 exec, %[sv]\n\ts_nop 0"
-                 : [y] "+v"(s), [sv] "=&s"(sv), [m] "=&s"(m)
-                 : NTM_V5(t, t), NTM_SHIFTS_UPTO(I0)
-                 : "scc");
-#undef NTM_TERM
-}
-// The scaling pass's column terms on lanes <= I0 + u: s += t[u], fs += tf[u], and the
-// lanes on which g0[u] or g1[u] is an infinity or a NaN ORed into the lane mask nf
-// (v_cmp_class under the narrowed EXEC writes zeros for the lanes that are off)
-template <int I0>
-__device__ __forceinline__ void fadd5x2_class_lanes_upto(double& s, double& fs, unsigned long long& nf,
-                                                         const double (&t)[5], const double (&tf)[5],
-                                                         const double (&g0)[5], const double (&g1)[5]) {
-    unsigned long long sv, m, c;
-    const int cls = 0x207;                                // signalling / quiet NaN, -inf, +inf
-#define NTM_TERM(k)                                                                                       \
-    NTM_LANES_UPTO(k) "v_cmp_class_f64_e64 %[c], %[p" #k "], %[cls]\n\ts_or_b64 %[nf], %[nf], %[c]\n\t" \
-                      "v_cmp_class_f64_e64 %[c], %[q" #k "], %[cls]\n\ts_or_b64 %[nf], %[nf], %[c]\n\t" \
-                      "v_add_f64 %[y], %[y], %[t" #k "]\n\tv_add_f64 %[z], %[z], %[u" #k "]\n\t"
-    asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_TERM(0) NTM_TERM(1) NTM_TERM(2) NTM_TERM(3) NTM_TERM(4)
-                 "s_mov_b64 exec, %[sv]\n\ts_nop 0"
-                 : [y] "+v"(s), [z] "+v"(fs), [nf] "+s"(nf), [sv] "=&s"(sv), [m] "=&s"(m), [c] "=&s"(c)
-                 : NTM_V5(t, t), NTM_V5(u, tf), NTM_V5(p, g0), NTM_V5(q, g1), [cls] "s"(cls), NTM_SHIFTS_UPTO(I0)
-                 : "scc");
-#undef NTM_TERM
-}
-// ---------------------------------------------------------------------------
-// Lane-masked lift recursion (the slim far N = 20 lift: Gamma's column l on lane
-// l < N, the free response on lane N).  At stage i the lanes that advance are
-// known at compile time: columns 0..i-1 (their diagonal lies above row i) and
-// lane N, the mask ((1 << i) - 1) | (1 << N).  The select form computes the next
-// 2-vector on every lane, selects it or the old one, selects the store index
-// (i, or the lane's own diagonal again) and builds the address: a v_cmp, five
-// v_cndmask, a v_mov and a v_lshl_add per stage around four fp64 instructions,
-// the selects on the chain to the next stage.  Here the four instructions and the
-// pair store run with EXEC narrowed to that mask: a lane that is off keeps g0 /
-// g1 and stores nothing, where the select form re-stored the same bits to the
-// same place, so registers and LDS hold the same bits whatever the data.
-//   The arithmetic is the select form's as the production build compiles it, which
-// is not one form: the compiler contracts (a21 g0 + a22 g1) + c1 from either
-// product, and it does so by the stage's place in its chunk of five.  First and
-// last stage of a chunk (form A): t = g0 a21; t = fma(a22, g1, t); g0 = fma(g0,
-// a11, c0).  The three between (form B): t = a22 g1; t = fma(a21, g0, t); g0 =
-// fma(a11, g0, c0).  Both end g1 = c1 + t.  The two round differently, so each
-// stage keeps the form, and the operand order, it had.
-//   One asm block per chunk.  EXEC is saved on entry, every mask is a literal ANDed
-// with the saved value (lanes off on entry stay off), EXEC is restored before the
-// block ends.  a22 is wave-uniform in every kernel (an SGPR pair, src0 of the
-// v_fmac / v_mul); c0 / c1 differ between the Gamma lanes and lane N: VGPRs.
-//   The stores are in the block (ds_write2_b64 at rec + 16 i: immediate offsets),
-// so the block clobbers memory and the compiler's wait counts do not include them.
-// LDS operations of one wave complete in order, so a compiler wait for a load
-// issued before or after such a store only waits longer, never too little; the
-// last chunk ends with s_waitcnt lgkmcnt(0), so nothing uncounted is in flight
-// past the lift.  Wait states: a SALU write of EXEC needs none before a VALU or
-// an LDS instruction (s_and_saveexec followed by a ds_write is what the compiler
-// emits for a predicated store), nor does a VALU write of a VGPR before the LDS
-// store that reads it as data (the interlock the compiler's own v_add, ds_write2
-// pairs rely on).  A store's data registers are next written by the following
-// stage's v_fma / v_add, three or more instructions behind it (s_and, v_mul,
-// v_fmac), or behind the restoring s_mov, the s_nop and the next block's s_mov /
-// s_and: the ISA asks for wait states there only after a vector-memory store of
-// more than 64 bits (one or two), LDS stores are not in that list, and the
-// compiler itself rewrites a ds_write2's data one instruction later.  After the
-// block: the last VALU write (g1) is followed by the store, the restoring s_mov
-// and an s_nop 0, more than the two wait states a DPP or lane read of it needs.
-//   Measured on the far N = 20 kernel at B = 1e5 (A/B on one box, three runs
-// each): 5.804 -> 5.602 ms per step-batch, outputs byte-equal; VALU instructions
-// per wave-step 25,977 -> 24,475, the fp64 ones unchanged.
-// ---------------------------------------------------------------------------
-#define NTM_LIFT_MASK(k) "s_and_b64 exec, %[sv], %[m" #k "]\n\t"
-#define NTM_LIFT_PUT(k) "ds_write2_b64 %[rec], %[g0], %[g1] offset0:%[o" #k "] offset1:%[p" #k "]\n\t"
-#define NTM_LIFT_A(k)                                                                                    \
-    NTM_LIFT_MASK(k) "v_mul_f64 %[t], %[g0], %[b" #k "]\n\tv_fmac_f64_e32 %[t], %[a22], %[g1]\n\t"       \
-                     "v_fma_f64 %[g0], %[g0], %[a" #k "], %[c0]\n\tv_add_f64 %[g1], %[c1], %[t]\n\t" NTM_LIFT_PUT(k)
-#define NTM_LIFT_B(k)                                                                                    \
-    NTM_LIFT_MASK(k) "v_mul_f64 %[t], %[a22], %[g1]\n\tv_fmac_f64_e32 %[t], %[b" #k "], %[g0]\n\t"       \
-                     "v_fma_f64 %[g0], %[a" #k "], %[g0], %[c0]\n\tv_add_f64 %[g1], %[c1], %[t]\n\t" NTM_LIFT_PUT(k)
-#define NTM_LIFT_N(k, I0) \
-    [m##k] "n"(((1 << ((I0) + k)) - 1) | (1 << 20)), [o##k] "n"(2 * ((I0) + k)), [p##k] "n"(2 * ((I0) + k) + 1)
-// stages I0 .. I0 + NS - 1 (NS = 5, or 4 in the last chunk, which also drains the stores) of
-// g <- A_i g + c on the lanes < i and lane 20, each stage's pair stored at rec + 16 i bytes
-// (rec: the lane's LDS byte address).  ca / cb: a11 / a21 of the chunk's stages
-template <int I0, int NS>
-__device__ __forceinline__ void lift_chunk_lanes(double& g0, double& g1, const double (&ca)[5], const double (&cb)[5],
-                                                 double a22, double c0, double c1, unsigned rec) {
-    static_assert(I0 >= 1 && (NS == 4 || NS == 5) && I0 + NS <= 20, "stages 1..19 of the N = 20 lift");
-    unsigned long long sv;
-    double t;
-    if constexpr (NS == 5) {
-        asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_LIFT_A(0) NTM_LIFT_B(1) NTM_LIFT_B(2) NTM_LIFT_B(3) NTM_LIFT_A(4)
-                     "s_mov_b64 exec, %[sv]\n\ts_nop 0"
-                     : [g0] "+v"(g0), [g1] "+v"(g1), [t] "=&v"(t), [sv] "=&s"(sv)
-                     : NTM_V5(a, ca), NTM_V5(b, cb), [a22] "s"(a22), [c0] "v"(c0), [c1] "v"(c1), [rec] "v"(rec),
-                       NTM_LIFT_N(0, I0), NTM_LIFT_N(1, I0), NTM_LIFT_N(2, I0), NTM_LIFT_N(3, I0), NTM_LIFT_N(4, I0)
-                     : "scc", "memory");
-    } else {
-        asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_LIFT_A(0) NTM_LIFT_B(1) NTM_LIFT_B(2) NTM_LIFT_B(3)
-                     "s_mov_b64 exec, %[sv]\n\ts_waitcnt lgkmcnt(0)"
-                     : [g0] "+v"(g0), [g1] "+v"(g1), [t] "=&v"(t), [sv] "=&s"(sv)
-                     : [a0] "v"(ca[0]), [a1] "v"(ca[1]), [a2] "v"(ca[2]), [a3] "v"(ca[3]), [b0] "v"(cb[0]),
-                       [b1] "v"(cb[1]), [b2] "v"(cb[2]), [b3] "v"(cb[3]), [a22] "s"(a22), [c0] "v"(c0), [c1] "v"(c1),
-                       [rec] "v"(rec), NTM_LIFT_N(0, I0), NTM_LIFT_N(1, I0), NTM_LIFT_N(2, I0), NTM_LIFT_N(3, I0)
-                     : "scc", "memory");
-    }
-}
-#undef NTM_LIFT_MASK
-#undef NTM_LIFT_PUT
-#undef NTM_LIFT_A
-#undef NTM_LIFT_B
-#undef NTM_LIFT_N
-#undef NTM_LANES_FROM
-#undef NTM_LANES_UPTO
-#undef NTM_SHIFTS_FROM
-#undef NTM_SHIFTS_UPTO
-#undef NTM_V5
-// ---------------------------------------------------------------------------
-// Lane-masked triangular substitutions of the echelon re-solve (the slim far
-// N = 20 kernels: the sorted E packed in LDS, row t at Ep + t(t+1)/2, n <= 20
-// rows, one scenario per wave).  Forward (E V = h, and E Z = -e_c with it when
-// k = 1): lane l owns row l, step t forms x_t = acc_t / E_tt on lane t, takes it
-// by two v_readlane_b32 and subtracts E_lt x_t on the rows below.  Backward (E'
-// mu = grad): lane l owns column l, the steps descend from u = n - 1 and update
-// the columns l < u.  The loop form does every step on every lane: a select
-// captures x on the lane l == t (a v_cmp, two v_mov, two v_cndmask per right-hand
-// side), the element load sits under a saved EXEC with a branch and its wait
-// directly in front of the fma, the address is rebuilt per step.  Here the steps
-// are unrolled over the compile-time t in batches of five: a batch's five
-// elements are loaded first (ds_read_b64 at immediate offsets from one per-lane
-// address, each under EXEC = the lanes that will use it: t < l < n forward, l < u
-// backward, so nothing past a row's diagonal is read), waited for once, and
-// the five chain steps follow without an LDS wait.  Per step and right-hand
-// side: one v_mul_f64 (acc sq_id, written straight into x under EXEC = lanes t <=
-// l < n: lane t's x is final after step t because the later steps exclude it, so
-// there is no select), the two v_readlane_b32 (the compiler's, between two
-// statements: v_readlane ignores EXEC, and a statement cannot name the halves of
-// a 64-bit operand), one v_fma_f64 under EXEC = lanes t < l < n.
-//   Bit-equality with the loop form, whatever the data: a lane l <= t there goes
-// on computing acc -= 0 x_t after its x was captured, and a lane >= n does so from
-// the start; neither acc is read again, by the loop or behind it.  x (zz, mu) of a
-// lane < n is the same product acc sq_id of the same chain (v_mul_f64 with sq_id as
-// src0; v_fma_f64 with the negated element as src0, the broadcast as src1: the
-// operands, and so the NaN a non-finite step propagates, as the loop form was
-// compiled); lanes >= n and lanes off on entry keep what they held (0.0 in the
-// kernel).  A step t >= n inside a batch runs with an empty EXEC (the masks are ANDed
-// with the lanes < n); backward a step u >= n would pass `lanes <= u`, so each
-// step's masks are ANDed with a gate that is the entry EXEC if u < n and 0 if not
-// (SALU, only in the batch the chain enters through).
-//   The masks are 32-bit literals with bit 31 clear (n <= 20), ANDed with the
-// entry EXEC, which every statement restores before it ends.  Wait states: a
-// SALU write of EXEC needs none before a VALU or an LDS instruction; v_mul_f64's
-// result is read by v_readlane_b32 (one wait state): the restoring s_mov_b64
-// stands between them in every statement.  The v_readlane's SGPR result feeds the
-// v_fma_f64 as a source: a VALU read of an SGPR that a VALU wrote needs two wait
-// states, and the compiler does not look into a statement for them, so each
-// step's s_and_b64 is followed by an s_nop 0 (the v_readlane_b32 may be the last
-// thing ahead of the statement).  The loads and their s_waitcnt lgkmcnt(0) are in
-// one statement, so no loaded register is visible to the compiler before it landed.
-//   Measured on the far N = 20 kernel at B = 1e5 (A/B on one box, three runs
-// each): the forward substitution 5.592 -> 5.495 ms per step-batch, the backward
-// one on top 5.490 -> 5.405 ms, outputs byte-equal; VALU instructions per wave-
-// step 24,475 -> 23,419.
-// ---------------------------------------------------------------------------
-template <int P, int CH, class W>
-__device__ __forceinline__ constexpr bool esub_lanes_ok() {
-    if constexpr (W::kSlim) return lane_masked_ok<P, CH, W>();
-    else return false;
-}
-struct LaneExec {
-    unsigned long long sv;                                // EXEC on entry
-    unsigned long long mb;                                // its lanes below n
-};
-__device__ __forceinline__ LaneExec esub_enter(int n) {   // n wave-uniform, 0..20
-    LaneExec x;
-    const unsigned long long low = (1ull << n) - 1ull;
-    asm volatile("s_mov_b64 %[sv], exec\n\ts_and_b64 %[mb], exec, %[lo]"
-                 : [sv] "=&s"(x.sv), [mb] "=&s"(x.mb)
-                 : [lo] "s"(low)
-                 : "scc");
-    return x;
-}
-constexpr unsigned esub_ge(int t) { return 0xFFFFFu & ~((1u << t) - 1u); }   // lanes t..19
-constexpr unsigned esub_gt(int t) { return 0xFFFFFu & ~((2u << t) - 1u); }   // lanes t+1..19
-constexpr unsigned esub_le(int u) { return (2u << u) - 1u; }                 // lanes 0..u
-constexpr unsigned esub_lt(int u) { return (1u << u) - 1u; }                 // lanes 0..u-1
-#define NTM_ESUB_LD(k) "s_and_b64 exec, %[mk], %[m" #k "]\n\tds_read_b64 %[e" #k "], %[at] offset:%[o" #k "]\n\t"
-// forward batch T0..T0+4: the five loads E[l][T0 + k] (lanes > T0 + k below n), step T0's product(s), one wait
-template <int T0, bool TWO>
-__device__ __forceinline__ void fsub_open(double (&e)[5], double acc, double& x, double acz, double& zz, double sq,
-                                          unsigned row, const LaneExec& c) {
-    static_assert(T0 >= 0 && T0 + 5 <= 20, "steps 0..19");
-    if constexpr (TWO) {
-        asm volatile(NTM_ESUB_LD(0) NTM_ESUB_LD(1) NTM_ESUB_LD(2) NTM_ESUB_LD(3) NTM_ESUB_LD(4)
-                     "s_and_b64 exec, %[mk], %[ge]\n\tv_mul_f64 %[x], %[sq], %[acc]\n\tv_mul_f64 %[z], %[sq], %[acz]\n\t"
-                     "s_waitcnt lgkmcnt(0)\n\ts_mov_b64 exec, %[sv]"
-                     : [e0] "=&v"(e[0]), [e1] "=&v"(e[1]), [e2] "=&v"(e[2]), [e3] "=&v"(e[3]), [e4] "=&v"(e[4]),
-                       [x] "+v"(x), [z] "+v"(zz)
-                     : [acc] "v"(acc), [acz] "v"(acz), [sq] "v"(sq), [at] "v"(row), [mk] "s"(c.mb), [sv] "s"(c.sv),
-                       [ge] "n"(esub_ge(T0)), [m0] "n"(esub_gt(T0)), [m1] "n"(esub_gt(T0 + 1)), [m2] "n"(esub_gt(T0 + 2)),
-                       [m3] "n"(esub_gt(T0 + 3)), [m4] "n"(esub_gt(T0 + 4)), [o0] "n"(8 * T0), [o1] "n"(8 * (T0 + 1)),
-                       [o2] "n"(8 * (T0 + 2)), [o3] "n"(8 * (T0 + 3)), [o4] "n"(8 * (T0 + 4))
-                     : "scc", "memory");
-    } else {
-        asm volatile(NTM_ESUB_LD(0) NTM_ESUB_LD(1) NTM_ESUB_LD(2) NTM_ESUB_LD(3) NTM_ESUB_LD(4)
-                     "s_and_b64 exec, %[mk], %[ge]\n\tv_mul_f64 %[x], %[sq], %[acc]\n\t"
-                     "s_waitcnt lgkmcnt(0)\n\ts_mov_b64 exec, %[sv]"
-                     : [e0] "=&v"(e[0]), [e1] "=&v"(e[1]), [e2] "=&v"(e[2]), [e3] "=&v"(e[3]), [e4] "=&v"(e[4]),
-                       [x] "+v"(x)
-                     : [acc] "v"(acc), [sq] "v"(sq), [at] "v"(row), [mk] "s"(c.mb), [sv] "s"(c.sv),
-                       [ge] "n"(esub_ge(T0)), [m0] "n"(esub_gt(T0)), [m1] "n"(esub_gt(T0 + 1)), [m2] "n"(esub_gt(T0 + 2)),
-                       [m3] "n"(esub_gt(T0 + 3)), [m4] "n"(esub_gt(T0 + 4)), [o0] "n"(8 * T0), [o1] "n"(8 * (T0 + 1)),
-                       [o2] "n"(8 * (T0 + 2)), [o3] "n"(8 * (T0 + 3)), [o4] "n"(8 * (T0 + 4))
-                     : "scc", "memory");
-    }
-}
-// forward step T: acc -= E[l][T] x_T on lanes > T, then (NEXT) step T + 1's product(s) on lanes >= T + 1,
-// the same lanes: one mask
-template <int T, bool TWO, bool NEXT>
-__device__ __forceinline__ void fsub_step(double et, double& acc, double& x, double& acz, double& zz, double sq,
-                                          const LaneExec& c) {
-    const double xt = gbcast<64>(x, T);
-    if constexpr (TWO) {
-        const double zt = gbcast<64>(zz, T);
-        if constexpr (NEXT)
-            asm volatile("s_and_b64 exec, %[mk], %[gt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
-                         "v_fma_f64 %[acz], -%[e], %[zt], %[acz]\n\t"
-                         "v_mul_f64 %[x], %[sq], %[acc]\n\tv_mul_f64 %[z], %[sq], %[acz]\n\ts_mov_b64 exec, %[sv]"
-                         : [acc] "+v"(acc), [acz] "+v"(acz), [x] "+v"(x), [z] "+v"(zz)
-                         : [e] "v"(et), [xt] "s"(xt), [zt] "s"(zt), [sq] "v"(sq), [mk] "s"(c.mb), [sv] "s"(c.sv),
-                           [gt] "n"(esub_gt(T))
-                         : "scc");
-        else if constexpr (esub_gt(T) != 0)
-            asm volatile("s_and_b64 exec, %[mk], %[gt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
-                         "v_fma_f64 %[acz], -%[e], %[zt], %[acz]\n\ts_mov_b64 exec, %[sv]"
-                         : [acc] "+v"(acc), [acz] "+v"(acz)
-                         : [e] "v"(et), [xt] "s"(xt), [zt] "s"(zt), [mk] "s"(c.mb), [sv] "s"(c.sv), [gt] "n"(esub_gt(T))
-                         : "scc");
-    } else {
-        if constexpr (NEXT)
-            asm volatile("s_and_b64 exec, %[mk], %[gt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
-                         "v_mul_f64 %[x], %[sq], %[acc]\n\ts_mov_b64 exec, %[sv]"
-                         : [acc] "+v"(acc), [x] "+v"(x)
-                         : [e] "v"(et), [xt] "s"(xt), [sq] "v"(sq), [mk] "s"(c.mb), [sv] "s"(c.sv),
-                           [gt] "n"(esub_gt(T))
-                         : "scc");
-        else if constexpr (esub_gt(T) != 0)
-            asm volatile("s_and_b64 exec, %[mk], %[gt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
-                         "s_mov_b64 exec, %[sv]"
-                         : [acc] "+v"(acc)
-                         : [e] "v"(et), [xt] "s"(xt), [mk] "s"(c.mb), [sv] "s"(c.sv), [gt] "n"(esub_gt(T))
-                         : "scc");
-    }
-}
-template <int T0, bool TWO>
-__device__ __forceinline__ void fsub_batch(double& acc, double& x, double& acz, double& zz, double sq, unsigned row,
-                                           const LaneExec& c) {
-    double e[5];
-    fsub_open<T0, TWO>(e, acc, x, acz, zz, sq, row, c);
-    fsub_step<T0, TWO, true>(e[0], acc, x, acz, zz, sq, c);
-    fsub_step<T0 + 1, TWO, true>(e[1], acc, x, acz, zz, sq, c);
-    fsub_step<T0 + 2, TWO, true>(e[2], acc, x, acz, zz, sq, c);
-    fsub_step<T0 + 3, TWO, true>(e[3], acc, x, acz, zz, sq, c);
-    fsub_step<T0 + 4, TWO, false>(e[4], acc, x, acz, zz, sq, c);
-}
-// E x = acc (TWO: and E zz = acz) for the lanes < n of the entry EXEC; row: the LDS byte address of
-// the lane's row of the packed E, sq: 1 / E[l][l].  n wave-uniform; the chain leaves at a batch boundary
-template <bool TWO>
-__device__ __forceinline__ void fsub_lanes(int n, double& acc, double& x, double& acz, double& zz, double sq,
-                                           unsigned row) {
-    const LaneExec c = esub_enter(n);
-    if (n > 0) fsub_batch<0, TWO>(acc, x, acz, zz, sq, row, c);
-    if (n > 5) fsub_batch<5, TWO>(acc, x, acz, zz, sq, row, c);
-    if (n > 10) fsub_batch<10, TWO>(acc, x, acz, zz, sq, row, c);
-    if (n > 15) fsub_batch<15, TWO>(acc, x, acz, zz, sq, row, c);
-}
-// backward batch U0+4 .. U0 (descending): the loads E[u][l] (lanes < u), step U0 + 4's product, one wait.
-// g: the gate of step U0 + 4 (the entry EXEC, or 0 if the step lies at or above n)
-template <int U0>
-__device__ __forceinline__ void bsub_open(double (&e)[5], double acc, double& mu, double sq, unsigned col,
-                                          unsigned long long g, const LaneExec& c) {
-    static_assert(U0 >= 0 && U0 + 5 <= 20, "steps 19..0");
-    constexpr int o0 = 4 * (U0 + 4) * (U0 + 5), o1 = 4 * (U0 + 3) * (U0 + 4), o2 = 4 * (U0 + 2) * (U0 + 3),
-                  o3 = 4 * (U0 + 1) * (U0 + 2), o4 = 4 * U0 * (U0 + 1);           // 8 u (u + 1) / 2 bytes
-    asm volatile(NTM_ESUB_LD(0) NTM_ESUB_LD(1) NTM_ESUB_LD(2) NTM_ESUB_LD(3) NTM_ESUB_LD(4)
-                 "s_and_b64 exec, %[g], %[le]\n\tv_mul_f64 %[x], %[sq], %[acc]\n\t"
-                 "s_waitcnt lgkmcnt(0)\n\ts_mov_b64 exec, %[sv]"
-                 : [e0] "=&v"(e[0]), [e1] "=&v"(e[1]), [e2] "=&v"(e[2]), [e3] "=&v"(e[3]), [e4] "=&v"(e[4]), [x] "+v"(mu)
-                 : [acc] "v"(acc), [sq] "v"(sq), [at] "v"(col), [mk] "s"(c.sv), [sv] "s"(c.sv), [g] "s"(g),
-                   [le] "n"(esub_le(U0 + 4)), [m0] "n"(esub_lt(U0 + 4)), [m1] "n"(esub_lt(U0 + 3)),
-                   [m2] "n"(esub_lt(U0 + 2)), [m3] "n"(esub_lt(U0 + 1)), [m4] "n"(esub_lt(U0)), [o0] "n"(o0),
-                   [o1] "n"(o1), [o2] "n"(o2), [o3] "n"(o3), [o4] "n"(o4)
-                 : "scc", "memory");
-}
-// backward step U: acc -= E[U][l] mu_U on lanes < U under the step's gate g, then (NEXT) step U - 1's product
-// on lanes <= U - 1 (the same lanes) under its gate gn
-template <int U, bool NEXT, bool GATED>
-__device__ __forceinline__ void bsub_step(double eu, double& acc, double& mu, double sq, unsigned long long g,
-                                          unsigned long long gn, const LaneExec& c) {
-    const double mu_u = gbcast<64>(mu, U);
-    if constexpr (NEXT && U > 0 && !GATED)               // both gates are the entry EXEC: one mask
-        asm volatile("s_and_b64 exec, %[g], %[lt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
-                     "v_mul_f64 %[x], %[sq], %[acc]\n\ts_mov_b64 exec, %[sv]"
-                     : [acc] "+v"(acc), [x] "+v"(mu)
-                     : [e] "v"(eu), [xt] "s"(mu_u), [sq] "v"(sq), [g] "s"(g), [sv] "s"(c.sv), [lt] "n"(esub_lt(U))
-                     : "scc");
-    else if constexpr (NEXT && U > 0)
-        asm volatile("s_and_b64 exec, %[g], %[lt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
-                     "s_and_b64 exec, %[gn], %[le]\n\tv_mul_f64 %[x], %[sq], %[acc]\n\t"
-                     "s_mov_b64 exec, %[sv]"
-                     : [acc] "+v"(acc), [x] "+v"(mu)
-                     : [e] "v"(eu), [xt] "s"(mu_u), [sq] "v"(sq), [g] "s"(g), [gn] "s"(gn), [sv] "s"(c.sv),
-                       [lt] "n"(esub_lt(U)), [le] "n"(esub_le(U > 0 ? U - 1 : 0))
-                     : "scc");
-    else if constexpr (U > 0)
-        asm volatile("s_and_b64 exec, %[g], %[lt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
-                     "s_mov_b64 exec, %[sv]"
-                     : [acc] "+v"(acc)
-                     : [e] "v"(eu), [xt] "s"(mu_u), [g] "s"(g), [sv] "s"(c.sv), [lt] "n"(esub_lt(U))
-                     : "scc");
-}
-template <int U0, bool GATED>
-__device__ __forceinline__ void bsub_batch(int n, double& acc, double& mu, double sq, unsigned col, const LaneExec& c) {
-    double e[5];
-    auto gate = [&](int u) -> unsigned long long { return (!GATED || u < n) ? c.sv : 0ull; };
-    bsub_open<U0>(e, acc, mu, sq, col, gate(U0 + 4), c);
-    bsub_step<U0 + 4, true, GATED>(e[0], acc, mu, sq, gate(U0 + 4), gate(U0 + 3), c);
-    bsub_step<U0 + 3, true, GATED>(e[1], acc, mu, sq, gate(U0 + 3), gate(U0 + 2), c);
-    bsub_step<U0 + 2, true, GATED>(e[2], acc, mu, sq, gate(U0 + 2), gate(U0 + 1), c);
-    bsub_step<U0 + 1, true, GATED>(e[3], acc, mu, sq, gate(U0 + 1), gate(U0), c);
-    bsub_step<U0, false, GATED>(e[4], acc, mu, sq, gate(U0), 0ull, c);
-}
-// E' mu = acc for the lanes < n of the entry EXEC; col: the LDS byte address of E[0][l] (Ep + l), sq: 1 /
-// E[l][l].  The batch that holds step n - 1 is gated per step, the ones below it are not
-template <int U0>
-__device__ __forceinline__ void bsub_from(int n, double& acc, double& mu, double sq, unsigned col, const LaneExec& c) {
-    if (n > U0) {
-        if (n >= U0 + 5) bsub_batch<U0, false>(n, acc, mu, sq, col, c);
-        else bsub_batch<U0, true>(n, acc, mu, sq, col, c);
-    }
-}
-__device__ __forceinline__ void bsub_lanes(int n, double& acc, double& mu, double sq, unsigned col) {
-    const LaneExec c = esub_enter(n);
-    bsub_from<15>(n, acc, mu, sq, col, c);
-    bsub_from<10>(n, acc, mu, sq, col, c);
-    bsub_from<5>(n, acc, mu, sq, col, c);
-    bsub_from<0>(n, acc, mu, sq, col, c);
-}
-#undef NTM_ESUB_LD
-// chunk J0 / 5 of row `lane`'s dot(s): the batched loads at compile-time offsets, then the masked terms
-template <int J0, class W>
-__device__ __forceinline__ void gamma_row_chunk_lanes(const W& w, const double* gr, const double* v, double& y) {
-    double g[5], x[5];
-#pragma unroll
-    for (int u = 0; u < 5; ++u) {
-        g[u] = gr[w.gidx(0, J0 + u)];
-        x[u] = v[J0 + u];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    fmac5_lanes_from<J0>(y, g, x);
-}
-template <int J0, class W>
-__device__ __forceinline__ void gamma_row_chunk2_lanes(const W& w, const double* gr, const double* v1,
-                                                       const double* v2, double& y1, double& y2) {
-    double g[5], x1[5], x2[5];
-#pragma unroll
-    for (int u = 0; u < 5; ++u) {
-        g[u] = gr[w.gidx(0, J0 + u)];
-        x1[u] = v1[J0 + u];
-        x2[u] = v2[J0 + u];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    fmac5x2_lanes_from<J0>(y1, y2, g, x1, x2);
-}
-
-// Gamma_r v restricted to j <= r/2 (row r of the packed block-lower-triangular Gamma).
-// P = 64 is passed where the caller's row is its lane (`for (r = l; r < 2N; r += P)`):
-// the N = 20 far kernel then masks the terms by lane (lane_masked_ok)
-template <int CH, int P = 0, class W>
-__device__ __forceinline__ double gamma_row_dot(const W& w, int r, const double* v) {
-    const double* gr = w.Gt() + r;                        // gt(r, j) = gr[gidx(0, j)]
-    double y = 0.0;
-    if constexpr (lane_masked_ok<P, CH, W>()) {
-        gamma_row_chunk_lanes<0>(w, gr, v, y);
-        gamma_row_chunk_lanes<5>(w, gr, v, y);
-        gamma_row_chunk_lanes<10>(w, gr, v, y);
-        gamma_row_chunk_lanes<15>(w, gr, v, y);
-    } else {
-    const int n = w.n(), jm = r >> 1;
-    NTM_CHUNK_PRAGMA
-    for (int j0 = 0; j0 < n; j0 += CH) {
-        double g[CH], x[CH];
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int j = j0 + u;
-            const bool in = j < n;
-            g[u] = in ? gr[w.gidx(0, j)] : 0.0;
-            x[u] = in ? v[j] : 0.0;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int j = j0 + u;
-            y += (j <= jm ? g[u] : 0.0) * x[u];
-        }
-    }
-    }
-    return y;
-}
-
-// Gamma_r v1 and Gamma_r v2 in one pass over row r (its loads shared)
-template <int CH, int P = 0, class W>
-__device__ __forceinline__ void gamma_row_dot2(const W& w, int r, const double* v1, const double* v2, double& y1,
-                                               double& y2) {
-    const double* gr = w.Gt() + r;
-    y1 = 0.0;
-    y2 = 0.0;
-    if constexpr (lane_masked_ok<P, CH, W>()) {
-        gamma_row_chunk2_lanes<0>(w, gr, v1, v2, y1, y2);
-        gamma_row_chunk2_lanes<5>(w, gr, v1, v2, y1, y2);
-        gamma_row_chunk2_lanes<10>(w, gr, v1, v2, y1, y2);
-        gamma_row_chunk2_lanes<15>(w, gr, v1, v2, y1, y2);
-    } else {
-    const int n = w.n(), jm = r >> 1;
-    NTM_CHUNK_PRAGMA
-    for (int j0 = 0; j0 < n; j0 += CH) {
-        double g[CH], x1[CH], x2[CH];
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int j = j0 + u;
-            const bool in = j < n;
-            g[u] = in ? gr[w.gidx(0, j)] : 0.0;
-            x1[u] = in ? v1[j] : 0.0;
-            x2[u] = in ? v2[j] : 0.0;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const double gm = (j0 + u <= jm) ? g[u] : 0.0;
-            y1 += gm * x1[u];
-            y2 += gm * x2[u];
-        }
-    }
-    }
-}
-
-// ---------------------------------------------------------------------------
-// L2: lifted prediction  (Rho_to_PhiGammaLambda.m:17-52, CANON D4/D6)
-// ---------------------------------------------------------------------------
-// Literal-reference lift (D4 / D6; generic kernels only, the host dispatches any
-// launch that sets these flags there): D6 takes A(rho_{i-j}) for Gamma_ij, i.e.
-// the coefficient index i - j - 1 counted from 0 (Rho_to_PhiGammaLambda.m:32);
-// D4 right-multiplies Phi_i = Phi_{i-1} A_i (:21).  Same arithmetic as
-// oracle/ntm_oracle.c orc_lift.  Lane j < N runs Gamma's column j; lane 0 then
-// runs Phi and Lambda.  Kept apart from lift_phase so that the specialised hot
-// kernels compile exactly as before (folding the switches into lift_phase cost
-// the N=20 kernel 72 B of scratch per lane although they are constant there).
-template <int P, class W>
-__device__ __forceinline__ void lift_literal(const Prob& pb, const W& w, const Coef& k, int l) {
-    const int N = w.n();
-    const bool d6 = (pb.flags & NTM_LITERAL_GAMMA_INDEX) != 0, d4 = (pb.flags & NTM_LITERAL_PHI_RIGHTMUL) != 0;
-    for (int j = l; j < N; j += P) {
-        double* col = w.Gt() + w.gidx(2 * j, j) - 2 * j;
-        double g0 = w.bb()[j], g1 = 0.0;
-        col[2 * j] = g0;
-        col[2 * j + 1] = g1;
-        for (int i = j + 1; i < N; ++i) {
-            const int ai = d6 ? i - j - 1 : i;
-            const double n0 = w.a11()[ai] * g0;
-            const double n1 = w.a21()[ai] * g0 + k.a22 * g1;
-            g0 = n0;
-            g1 = n1;
-            col[2 * i] = g0;
-            col[2 * i + 1] = g1;
-        }
-    }
-    if (l == 0) {
-        double p00 = w.a11()[0], p10 = w.a21()[0], p01 = 0.0, p11 = k.a22;
-        double l0 = k.C1, l1 = k.C2;
-        w.Phi()[0] = p00; w.Phi()[1] = p10; w.Phi()[2] = p01; w.Phi()[3] = p11;
-        w.Lam()[0] = l0; w.Lam()[1] = l1;
-        for (int i = 1; i < N; ++i) {
-            const double a11 = w.a11()[i], a21 = w.a21()[i];
-            double q00, q01, q10, q11;
-            if (d4) {                                  // Phi_{i-1} A_i
-                q00 = p00 * a11 + p01 * a21;
-                q01 = p01 * k.a22;
-                q10 = p10 * a11 + p11 * a21;
-                q11 = p11 * k.a22;
-            } else {                                   // A_i Phi_{i-1}
-                q00 = a11 * p00;
-                q01 = a11 * p01;
-                q10 = a21 * p00 + k.a22 * p10;
-                q11 = a21 * p01 + k.a22 * p11;
-            }
-            p00 = q00; p01 = q01; p10 = q10; p11 = q11;
-            const double m0 = a11 * l0 + k.C1;
-            const double m1 = (a21 * l0 + k.a22 * l1) + k.C2;
-            l0 = m0; l1 = m1;
-            w.Phi()[4 * i] = p00; w.Phi()[4 * i + 1] = p10; w.Phi()[4 * i + 2] = p01; w.Phi()[4 * i + 3] = p11;
-            w.Lam()[2 * i] = l0; w.Lam()[2 * i + 1] = l1;
-        }
-    }
-    NTM_WSYNC();
-}
-
-// The scaling pass's column sums, accumulated by the slim lift at long horizons:
-// lane l < N walks Gamma's column l stage by stage, so it can add G_ll's and F_l's
-// terms as it produces them (the free response e_i is lane N's value at the same
-// stage, read by readlane), instead of the scaling pass reading the column back
-// from LDS.  Same terms in the same order as the pass (diag_scale_phase).  Round 6,
-// A/B on one box: config 5 mode 2 73.9 -> 70.9 ms per step-batch; the far N = 20
-// kernel 6.31 -> 6.50 ms (its register allocation again) and the all-LDS one (config
-// 2 0.193 -> 0.210 ms: e_i takes six lane reads there), so N = 50 only.
-struct ColSums {
-    double s = 0.0, f = 0.0;   // sum_i Gamma_il' Om Gamma_il and sum_i Gamma_il' Om (e_i - r)
-    int bad = 0;               // a non-finite Gamma entry
-};
-template <class W>
-__device__ __forceinline__ constexpr bool fuse_colsum() {
-    if constexpr (W::kSlim) return W::kNN > 32;   // N = 50: on; the far N = 20 kernel: off
-    else return false;                            // the all-LDS N = 20 build and the generic kernels: off
-}
-// The slim far N = 20 lift runs its recursion lane-masked (lift_chunk_lanes): column l on
-// lane l, a11 / a21 in LDS, chunks of five stages, no column sums riding on the loop
-template <int P, int CH, class W>
-__device__ __forceinline__ constexpr bool lift_lanes_ok() {
-    if constexpr (W::kSlim) return lane_masked_ok<P, CH, W>() && W::kAB != 0 && !fuse_colsum<W>();
-    else return false;
-}
-// chunk I0 of the lane-masked lift: the a11 / a21 loads batched at compile-time offsets, then the stages
-template <int I0, int NS, class W>
-__device__ __forceinline__ void lift_chunk_at(const W& w, double& g0, double& g1, double a22, double c0, double c1,
-                                              unsigned rec) {
-    double ca[5], cb[5];
-#pragma unroll
-    for (int u = 0; u < 5; ++u) {
-        ca[u] = u < NS ? w.a11()[I0 + u] : 0.0;
-        cb[u] = u < NS ? w.a21()[I0 + u] : 0.0;
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    lift_chunk_lanes<I0, NS>(g0, g1, ca, cb, a22, c0, c1, rec);
-}
-
-template <int P, class W>
-__device__ __forceinline__ void lift_phase(const Prob& pb, const W& w, int l, double x0 = 0.0, double x1 = 0.0,
-                                           ColSums* cs = nullptr) {
-    const int N = w.n();
-    const Coef k = scn_coef(pb, w);
-    if constexpr (W::kSlim) {
-        // lane l < N keeps stage l's A/B coefficients in registers; the loop takes
-        // stage i's by readlane.  Lanes < N: Gamma columns (as below); lane N: the
-        // free response e = Phi x_k + Lambda as its own recursion e_i = A_i e_{i-1} + C
-        // with e_{-1} = x_k (CANON D4: Phi_i = A_i Phi_{i-1}; the same states as
-        // Phi x_k + Lambda to rounding), written straight to w.e()
-        double ra = 0.0, rc = 0.0, rbb = 0.0;
-        if (l < N) {
-            ra = coef_a11(k, w.rho()[3 * l]);
-            rc = coef_a21(k, w.rho()[3 * l + 1]);
-            rbb = coef_b(k, w.rho()[3 * l + 2]);
-            if constexpr (W::kAB) { w.a11()[l] = ra; w.a21()[l] = rc; }
-        }
-        if constexpr (W::kAB) NTM_WSYNC();
-        const double a0 = gbcast<P>(ra, 0), c0v = gbcast<P>(rc, 0);
-        NTM_T0(tlf);
-        if (l <= N) {
-            const bool gam = l < N;
-            double g0 = gam ? rbb : (a0 * x0 + k.C1);
-            double g1 = gam ? 0.0 : ((c0v * x0 + k.a22 * x1) + k.C2);
-            const double c0 = gam ? 0.0 : k.C1, c1 = gam ? 0.0 : k.C2;
-            double* const rec = gam ? w.Gt() + w.gidx(2 * l, l) - 2 * l : w.e();
-            rec[2 * (gam ? l : 0)] = g0;
-            rec[2 * (gam ? l : 0) + 1] = g1;
-            // stage i's terms of the column sums (lane N holds e_i): the scaling pass's
-            // and free_response's expressions
-            double cs_s = 0.0, cs_f = 0.0;
-            int cs_bad = 0;
-            const OmQ<qi_on<W>()> cq(pb.Q);
-            auto col_terms = [&](int i) {
-                if constexpr (fuse_colsum<W>()) {
-                    const double e0 = gbcast<P>(g0, N), e1 = gbcast<P>(g1, N);
-                    const double d0 = e0 - pb.r[0], d1 = e1 - pb.r[1];
-                    const double ea = cq.o0(d0, d1), eb = cq.o1(d0, d1);
-                    const double o0 = cq.o0(g0, g1), o1 = cq.o1(g0, g1);
-                    const double t = g0 * o0 + g1 * o1;
-                    const double tf = g0 * ea + g1 * eb;
-                    const bool on = gam && i >= l;
-                    if (on) cs_bad |= !isfinite(g0) || !isfinite(g1);
-                    cs_s += on ? t : 0.0;
-                    cs_f += on ? tf : 0.0;
-                }
-            };
-            col_terms(0);
-            constexpr int CH = NTM_CH;
-            if constexpr (lift_lanes_ok<P, CH, W>()) {
-                // stages 1..19 under EXEC narrowed to the lanes that advance (lift_chunk_lanes)
-                const unsigned at = (unsigned)(uintptr_t)(__attribute__((address_space(3))) double*)rec;
-                lift_chunk_at<1, 5>(w, g0, g1, k.a22, c0, c1, at);
-                lift_chunk_at<6, 5>(w, g0, g1, k.a22, c0, c1, at);
-                lift_chunk_at<11, 5>(w, g0, g1, k.a22, c0, c1, at);
-                lift_chunk_at<16, 4>(w, g0, g1, k.a22, c0, c1, at);
-            } else {
-            NTM_CHUNK_PRAGMA
-            for (int i0 = 1; i0 < N; i0 += CH) {
-                double ca[CH], cb[CH];
-#pragma unroll
-                for (int u = 0; u < CH; ++u) {
-                    const int i = i0 + u;
-                    if constexpr (W::kAB) {
-                        ca[u] = i < N ? w.a11()[i] : 0.0;
-                        cb[u] = i < N ? w.a21()[i] : 0.0;
-                    } else {
-                        ca[u] = i < N ? gbcast<P>(ra, i) : 0.0;
-                        cb[u] = i < N ? gbcast<P>(rc, i) : 0.0;
-                    }
-                }
-                if constexpr (W::kAB) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int u = 0; u < CH; ++u) {
-                    const int i = i0 + u;
-                    if (i < N) {
-                        const double n0 = ca[u] * g0 + c0;
-                        const double n1 = (cb[u] * g0 + k.a22 * g1) + c1;
-                        const bool live = !gam || i > l;
-                        g0 = live ? n0 : g0;
-                        g1 = live ? n1 : g1;
-                        const int at = live ? i : l;
-                        rec[2 * at] = g0;
-                        rec[2 * at + 1] = g1;
-                        col_terms(i);
-                    }
-                }
-            }
-            }
-            if (cs) { cs->s = cs_s; cs->f = cs_f; cs->bad = cs_bad; }
-        }
-        NTM_ACC(ST_L_LOOP, tlf);
-        NTM_WSYNC();
-        return;
-    } else {
-    if (l < N) {
-        w.a11()[l] = coef_a11(k, w.rho()[3 * l]);
-        w.a21()[l] = coef_a21(k, w.rho()[3 * l + 1]);
-        w.bb()[l] = coef_b(k, w.rho()[3 * l + 2]);
-    }
-    NTM_WSYNC();
-    if constexpr (W::kNN == 0) {
-        if (pb.flags & (NTM_LITERAL_PHI_RIGHTMUL | NTM_LITERAL_GAMMA_INDEX)) {
-            lift_literal<P>(pb, w, k, l);
-            return;
-        }
-    }
-    NTM_T0(tlf);
-    // Gamma: lane j owns column j: Gamma_jj = B_j, Gamma_ij = A_i Gamma_{i-1,j} (D6).
-    // Lanes N and N+1 run the same 2-vector recursion for the two columns of
-    // Phi_i = A_i Phi_{i-1} (D4), lane N+2 for Lambda_i = A_i Lambda_{i-1} + C,
-    // all in the one loop (the group has the idle lanes for N + 3 <= P).
-    const bool extra = N + 3 <= P;
-    if (l < N || (extra && l < N + 3)) {
-        const bool gam = l < N;
-        const int ph = l - N;                          // 0, 1: Phi column; 2: Lambda
-        double g0, g1;
-        if (gam) { g0 = w.bb()[l]; g1 = 0.0; }
-        else if (ph == 0) { g0 = w.a11()[0]; g1 = w.a21()[0]; }
-        else if (ph == 1) { g0 = 0.0; g1 = k.a22; }
-        else { g0 = k.C1; g1 = k.C2; }
-        const double c0 = (ph == 2) ? k.C1 : 0.0, c1 = (ph == 2) ? k.C2 : 0.0;
-        // this lane's record, stage i at rec[st i]: its Gamma column (col[r], r >= 2l),
-        // its Phi column (stride 4) or Lambda; one address for the three kinds of
-        // lanes, so every step is one pair of stores with no divergent branches
-        double* const rec = gam ? w.Gt() + w.gidx(2 * l, l) - 2 * l : (ph < 2 ? w.Phi() + 2 * ph : w.Lam());
-        const int st = (gam || ph == 2) ? 2 : 4;
-        auto put = [&](int i) {
-            rec[st * i] = g0;
-            rec[st * i + 1] = g1;
-        };
-        put(gam ? l : 0);
-        // fixed trip count (unrolls), branch-free: Gamma rows i <= l keep (B_l, 0) and
-        // rewrite the diagonal.  The coefficients of CH steps are loaded ahead of the
-        // chunk's stores (the stores cannot be proven not to alias them, so per-step
-        // loads would wait for the previous step's stores: one LDS round trip a step)
-        constexpr int CH = NTM_CH;
-        NTM_CHUNK_PRAGMA
-        for (int i0 = 1; i0 < N; i0 += CH) {
-            double ca[CH], cb[CH];
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                const int i = i0 + u;
-                ca[u] = i < N ? w.a11()[i] : 0.0;
-                cb[u] = i < N ? w.a21()[i] : 0.0;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                const int i = i0 + u;
-                if (i < N) {
-                    const double n0 = ca[u] * g0 + c0;
-                    const double n1 = (cb[u] * g0 + k.a22 * g1) + c1;
-                    const bool live = !gam || i > l;
-                    g0 = live ? n0 : g0;
-                    g1 = live ? n1 : g1;
-                    put(live ? i : l);
-                }
-            }
-        }
-    }
-    NTM_ACC(ST_L_LOOP, tlf);
-    // Phi and Lambda on lane 0 when the group has no idle lanes
-    if (!extra && l == 0) {
-        double p00 = w.a11()[0], p10 = w.a21()[0], p01 = 0.0, p11 = k.a22;
-        double l0 = k.C1, l1 = k.C2;
-        w.Phi()[0] = p00; w.Phi()[1] = p10; w.Phi()[2] = p01; w.Phi()[3] = p11;
-        w.Lam()[0] = l0; w.Lam()[1] = l1;
-        for (int i = 1; i < N; ++i) {
-            double a11 = w.a11()[i], a21 = w.a21()[i];
-            double q00 = a11 * p00, q01 = a11 * p01;
-            double q10 = a21 * p00 + k.a22 * p10, q11 = a21 * p01 + k.a22 * p11;
-            p00 = q00; p01 = q01; p10 = q10; p11 = q11;
-            double m0 = a11 * l0 + k.C1;
-            double m1 = (a21 * l0 + k.a22 * l1) + k.C2;
-            l0 = m0; l1 = m1;
-            w.Phi()[4 * i] = p00; w.Phi()[4 * i + 1] = p10; w.Phi()[4 * i + 2] = p01; w.Phi()[4 * i + 3] = p11;
-            w.Lam()[2 * i] = l0; w.Lam()[2 * i + 1] = l1;
-        }
-    }
-    NTM_WSYNC();
-    }
-}
-
-// free response e = Phi x_k + Lambda (the x-dependent part of NTM_MPC_Sim.m:121
-// and of c + W x_k at :97)
-template <int P, class W>
-__device__ __forceinline__ void free_response(const W& w, double x0, double x1, int l, const Prob* pw = nullptr) {
-    for (int i = l; i < w.n(); i += P) {
-        double e0, e1;
-        if constexpr (W::kSlim) {                // the lift wrote e itself
-            e0 = w.e()[2 * i];
-            e1 = w.e()[2 * i + 1];
-        } else {
-            const double* Ph = w.Phi() + 4 * i;
-            e0 = (Ph[0] * x0 + Ph[2] * x1) + w.Lam()[2 * i];
-            e1 = (Ph[1] * x0 + Ph[3] * x1) + w.Lam()[2 * i + 1];
-            w.e()[2 * i] = e0;
-            w.e()[2 * i + 1] = e1;
-        }
-        if (pw) {
-            // Om (e_i - r) per stage for the scaling pass's F (scratch in w.xp(): the
-            // rollout consumed it and rewrites it; the re-solve recomputes it)
-            const double d0 = e0 - pw->r[0], d1 = e1 - pw->r[1];
-            const OmQ<qi_on<W>()> om(pw->Q);
-            w.xp()[2 * i] = om.o0(d0, d1);
-            w.xp()[2 * i + 1] = om.o1(d0, d1);
-        }
-    }
-    NTM_WSYNC();
-}
-
-// sum_{imin <= i < n} a_i' c_i over 2-vectors stored at stride 2 (c = Om b precomputed)
-template <int CH>
-__device__ __forceinline__ double dot_rows2(const double* a, const double* c, int n, int imin) {
-    double s = 0.0;
-    NTM_CHUNK_PRAGMA
-    for (int i0 = 0; i0 < n; i0 += CH) {
-        double a0[CH], a1[CH], c0[CH], c1[CH];
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int i = i0 + u;
-            const bool in = i < n;
-            a0[u] = in ? a[2 * i] : 0.0;
-            a1[u] = in ? a[2 * i + 1] : 0.0;
-            c0[u] = in ? c[2 * i] : 0.0;
-            c1[u] = in ? c[2 * i + 1] : 0.0;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int i = i0 + u;
-            const double t = a0[u] * c0[u] + a1[u] * c1[u];
-            s += (i >= imin && i < n) ? t : 0.0;
-        }
-    }
-    return s;
-}
-// chunk I0 / 5 of column `lane`'s sum: the batched loads at compile-time offsets, the
-// terms formed on every lane, then added on the lanes <= i
-template <int I0>
-__device__ __forceinline__ void dot_rows2_chunk_lanes(const double* a, const double* c, double& s) {
-    double a0[5], a1[5], c0[5], c1[5], t[5];
-#pragma unroll
-    for (int u = 0; u < 5; ++u) {
-        const int i = I0 + u;
-        a0[u] = a[2 * i];
-        a1[u] = a[2 * i + 1];
-        c0[u] = c[2 * i];
-        c1[u] = c[2 * i + 1];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < 5; ++u) t[u] = a0[u] * c0[u] + a1[u] * c1[u];
-    fadd5_lanes_upto<I0>(s, t);
-}
-// dot_rows2 with imin = the caller's lane (column l on lane l < N): the N = 20 far
-// kernel masks the terms by lane (lane_masked_ok)
-template <int CH, int P, class W>
-__device__ __forceinline__ double dot_rows2(const W&, const double* a, const double* c, int n, int imin) {
-    if constexpr (lane_masked_ok<P, CH, W>()) {
-        double s = 0.0;
-        dot_rows2_chunk_lanes<0>(a, c, s);
-        dot_rows2_chunk_lanes<5>(a, c, s);
-        dot_rows2_chunk_lanes<10>(a, c, s);
-        dot_rows2_chunk_lanes<15>(a, c, s);
-        return s;
-    } else {
-        return dot_rows2<CH>(a, c, n, imin);
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Gram of Gamma columns on the matrix cores (long horizons): for the columns
-// j_a = col_of(a), a < nc, S(a, c) = X_a' (I (x) Q) X_c with X_a = Gamma(:, j_a),
-// i.e. S = X' Y with Y = (I (x) Q) X, the (nc x 2N) x (2N x nc) contraction of
-// NTM_MPC_Sim.m:120 restricted to those columns.  V_MFMA_F64_16X16X4F64 on
-// 16 x 16 tiles, K = 4 rows of Gamma per instruction (2N / 4 steps; NN even):
-// lane l holds A = X(r, 16 t + (l & 15)) and B = Y(r, 16 t + (l & 15)) with
-// r = 4 s + (l >> 4), both from the two Gamma rows of stage r / 2 (two LDS
-// loads); the lower tile pairs accumulate in registers and put(a, c, S) takes
-// every entry a >= c (D layout: column l & 15, row (l >> 4) + 4 i).  Same terms
-// as qdot_rows / gram_rows, summed in the matrix core's order.  P = 64 only,
-// called in wave-uniform control flow.
-// ---------------------------------------------------------------------------
-typedef double ntm_d4 __attribute__((ext_vector_type(4)));
-#ifndef NTM_COLL3
-#define NTM_COLL3 1        // k = 2 sets with one collision (three holes) on the null-space path (round 6)
-#endif
-template <int NN, class W, class ColOf, class Put>
-__device__ __forceinline__ void gram_mfma(const Prob& pb, const W& w, int nc, ColOf col_of, Put put, int l) {
-    static_assert(NN > 0 && NN % 2 == 0, "gram_mfma: compile-time even horizon");
-    constexpr int TM = (NN + 15) / 16;                 // tiles of 16 columns
-    constexpr int NP = TM * (TM + 1) / 2;              // lower tile pairs
-    const OmQ<qi_on<W>()> om(pb.Q);
-    const int li = l & 15, lk = l >> 4;
-    const int T = (nc + 15) >> 4;
-    int base[TM], r0[TM];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) {
-        const int a = 16 * t + li;
-        const bool on = a < nc;
-        const int j = on ? col_of(a) : 0;
-        base[t] = w.gidx(2 * j, j) - 2 * j;             // Gamma(r, j) = Gt[base + r], r >= 2j
-        r0[t] = on ? 2 * j : 2 * NN;                    // rows above the block diagonal are zero
-    }
-    ntm_d4 acc[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) acc[p] = ntm_d4{0.0, 0.0, 0.0, 0.0};
-    const double* const G = w.Gt();
-#pragma unroll 1
-    for (int s = 0; s < NN / 2; ++s) {                  // not unrolled: the accumulators stay the only long-lived registers
-        const int re = 4 * s + (lk & ~1);               // the even row of this lane's stage
-        double xa[TM], yb[TM];
-#pragma unroll
-        for (int t = 0; t < TM; ++t) {
-            const bool in = re >= r0[t];
-            const double x0 = in ? G[base[t] + re] : 0.0, x1 = in ? G[base[t] + re + 1] : 0.0;
-            xa[t] = (lk & 1) ? x1 : x0;
-            yb[t] = (lk & 1) ? om.o1(x0, x1) : om.o0(x0, x1);
-        }
-        int p = 0;
-#pragma unroll
-        for (int ta = 0; ta < TM; ++ta)
-#pragma unroll
-            for (int tc = 0; tc <= ta; ++tc, ++p)
-                if (ta < T) acc[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[ta], yb[tc], acc[p], 0, 0, 0);
-    }
-    int p = 0;
-#pragma unroll
-    for (int ta = 0; ta < TM; ++ta)
-#pragma unroll
-        for (int tc = 0; tc <= ta; ++tc, ++p) {
-            if (ta >= T) continue;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int a = 16 * ta + lk + 4 * i, c = 16 * tc + li;
-                if (a < nc && c <= a) put(a, c, acc[p][i]);
-            }
-        }
-}
-
-// ---------------------------------------------------------------------------
-// condensed cost G = 2 Gamma' Om Gamma (lower triangle into dst, col-major),
-// F = 2 Gamma' Om (e - R)      NTM_MPC_Sim.m:120-121 (CANON D8, D12)
-// ---------------------------------------------------------------------------
-template <int P, class W, class Put>
-__device__ __forceinline__ void gram_rows_put(const Prob& pb, const W& w, Put put, int l) {
-    const int N = w.n();
-    if constexpr (W::kNN > 32 && P == 64) {   // the matrix cores (gram_mfma)
-        gram_mfma<W::kNN>(pb, w, N, [](int a) { return a; }, [&](int j, int kk, double sg) { put(j, kk, 2 * sg); },
-                          l);
-        return;
-    }
-    const OmQ<qi_on<W>()> om(pb.Q);
-    // one (j, kk) entry per lane; fixed-trip masked dot (column reads below the
-    // packed column start stay inside Gt, see StructRows::check)
-    const int npair = N * (N + 1) / 2;
-    for (int idx = l; idx < npair; idx += P) {
-        int j = (int)((sqrt(8.0 * idx + 1.0) - 1.0) * 0.5);
-        if ((j + 1) * (j + 2) / 2 <= idx) ++j;
-        if (j * (j + 1) / 2 > idx) --j;
-        const int kk = idx - j * (j + 1) / 2;
-        const double* cj = w.Gt() + w.gidx(2 * j, j) - 2 * j;
-        const double* ck = w.Gt() + w.gidx(2 * kk, kk) - 2 * kk;
-        double s = 0.0;
-        for (int i = 0; i < N; ++i) {
-            const double g0 = ck[2 * i], g1 = ck[2 * i + 1];
-            const double o0 = om.o0(g0, g1);
-            const double o1 = om.o1(g0, g1);
-            const double t = cj[2 * i] * o0 + cj[2 * i + 1] * o1;
-            s += (i >= j) ? t : 0.0;
-        }
-        double gv = 2 * s;
-        if constexpr (ru_on<W>()) gv = (j == kk) ? gv + 2 * pb.Ru : gv;   // + 2 Ru I (ABI v5)
-        put(j, kk, gv);             // G(j, kk), j >= kk
-    }
-}
-template <int P, class W>
-__device__ __forceinline__ void gram_rows(const Prob& pb, const W& w, double* dst, int l) {
-    const int LD = w.ldj();
-    gram_rows_put<P>(pb, w, [&](int j, int kk, double v) { dst[j + kk * LD] = v; }, l);
-}
-
-template <int P, class W>
-__device__ __forceinline__ void cost_phase(const Prob& pb, const W& w, int l) {
-    const int N = w.n();
-    const double q00 = pb.Q[0], q01 = pb.Q[1], q10 = pb.Q[2], q11 = pb.Q[3];
-    gram_rows<P>(pb, w, w.R(), l);
-    if (l < N) {
-        const double* cj = w.Gt() + w.gidx(2 * l, l) - 2 * l;
-        double f = 0.0;
-        for (int i = l; i < N; ++i) {
-            double e0 = w.e()[2 * i] - pb.r[0], e1 = w.e()[2 * i + 1] - pb.r[1];
-            double o0 = q00 * e0 + q01 * e1;
-            double o1 = q10 * e0 + q11 * e1;
-            f += cj[2 * i] * o0 + cj[2 * i + 1] * o1;
-        }
-        w.F()[l] = 2 * f;
-    }
-    NTM_WSYNC();
-}
-
-// G~ = D G D in place (lower triangle, col-major); the same expression order
-// is used when the polish recomputes G~ (so both copies are bit-identical).
-template <int P, class W>
-__device__ __forceinline__ int scale_gram(const W& w, double* G, int l) {
-    int bad = 0;
-    if (l < w.n()) {
-        double Dl = w.D()[l];
-        for (int kk = 0; kk <= l; ++kk) {
-            double v = G[l + kk * w.ldj()] * Dl * w.D()[kk];
-            bad |= !isfinite(v);
-            G[l + kk * w.ldj()] = v;
-        }
-    }
-    return bad;
-}
-
-// ---------------------------------------------------------------------------
-// Jacobi scaling U = D V with D = diag(G)^{-1/2}, computed from the Gram
-// diagonal only (same summation order as gram_rows, so D is bit-identical to
-// what the full G would give); F~ = D F; norms of the scaled state rows
-// ||Gamma_r D||.  Gamma stays unscaled (D is applied on the fly).  The full
-// G~ is only formed when the Goldfarb-Idnani fallback runs (full_gram).
-// Returns (group-uniform) 2 if any datum is non-finite, else 1 if a constant
-// row is violated (the x_0 rows and state rows Gamma does not reach: D15, D22,
-// StructRows::feasible_const's test, folded into the row pass that finds them
-// and into the one reduction, round 6), else 0.
-// ---------------------------------------------------------------------------
-// The far N = 20 build keeps the separate test (qp_phase calls feasible_const):
-// folded in, it cost that kernel 1.3% through register allocation (6.30 -> 6.38 ms)
-// while config 2 (0.201 -> 0.199 ms) and config 5 (74.2 -> 73.7 ms) gained.
-template <class W>
-__device__ __forceinline__ constexpr bool fold_const() { return !(W::kFar && W::kNN == 20); }
-// Lane-masked chunk of the scaling pass's column pass (lane_masked_ok: column l on lane l),
-// stages I0..I0+4 of column `lane`: the terms of G_ll and F_l formed on every lane, added
-// on the lanes <= i, the non-finite Gamma entries of those lanes into nf
-template <int I0, class OM>
-__device__ __forceinline__ void scale_col_chunk_lanes(const OM& qw, const double* cj, const double* om, double& s,
-                                                      double& fs, unsigned long long& nf) {
-    double ga[5], gb[5], ea[5], eb[5], t[5], tf[5];
-#pragma unroll
-    for (int u = 0; u < 5; ++u) {
-        const int i = I0 + u;
-        ga[u] = cj[2 * i];
-        gb[u] = cj[2 * i + 1];
-        ea[u] = om[2 * i];
-        eb[u] = om[2 * i + 1];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < 5; ++u) {
-        const double g0 = ga[u], g1 = gb[u];
-        const double o0 = qw.o0(g0, g1);
-        const double o1 = qw.o1(g0, g1);
-        t[u] = g0 * o0 + g1 * o1;
-        tf[u] = g0 * ea[u] + g1 * eb[u];
-    }
-    fadd5x2_class_lanes_upto<I0>(s, fs, nf, t, tf, ga, gb);
-}
-template <int P, class W>
-__device__ __forceinline__ int diag_scale_phase(const Prob& pb, const W& w, int l, bool with_state_rows,
-                                                double x0 = 0.0, double x1 = 0.0, const ColSums* cs = nullptr) {
-    const int N = w.n();
-    const OmQ<qi_on<W>()> qw(pb.Q);
-    int bad = 0, infe = 0;
-    auto const_row = [&](int r) {                         // 0 <= b on a constant state row, to kConstTol
-        if constexpr (!fold_const<W>()) return;
-        const int c = r & 1;
-        const double er = w.e()[r];
-        infe |= (er - pb.xmin[c]) < -kConstTol;
-        infe |= (pb.xmax[c] - er) < -kConstTol;
-    };
-    if (fold_const<W>() && with_state_rows && l == 0) {   // the x_0 rows (D15)
-        infe |= (x0 - pb.xmin[0]) < -kConstTol;
-        infe |= (x1 - pb.xmin[1]) < -kConstTol;
-        infe |= (pb.xmax[0] - x0) < -kConstTol;
-        infe |= (pb.xmax[1] - x1) < -kConstTol;
-    }
-    NTM_T0(tsc);
-    // Short horizons (2N <= 64, N = 20): the column pass and the row pass each split
-    // their sums in two halves at H = ceil(N/2) on otherwise idle lanes, so the wave
-    // runs H trips instead of N (lanes N..2N-1 take the columns' i >= H terms; lanes
-    // 2N.. the j >= H terms of rows with r >= 2H).  The sums are then (first half) +
-    // (second half) instead of one sequential pass.  The all-LDS build only (config 2,
-    // B = 1024: 0.208 -> 0.199 ms; mode 2 at B = 1024: 0.545 -> 0.526 ms).  The far
-    // build's register allocation does not absorb it: 6.36 -> 7.98 ms per step-batch
-    // at B = 1e5 with the chunk unroll, 6.41 ms without; the column pass alone 7.11 ms,
-    // the row pass alone 9.66 ms (A/B on one box)
-    constexpr int NNs = W::kNN, Hs = (NNs + 1) / 2;
-    constexpr bool kSplit = !W::kFar && P == 64 && NNs > 0 && 4 * NNs - 2 * Hs <= 64;
-    if constexpr (kSplit) {
-        double s = 0.0, fs = 0.0;
-        const int col = l < N ? l : l - N;
-        const int base = l < N ? 0 : Hs;
-        if (l < 2 * N) {
-            const double* cj = w.Gt() + w.gidx(2 * col, col) - 2 * col;
-            const double* om = w.xp();
-            constexpr int CH = NTM_CH;
-            NTM_CHUNK_PRAGMA
-            for (int u0 = 0; u0 < Hs; u0 += CH) {
-                double ga[CH], gb[CH], ea[CH], eb[CH];
-#pragma unroll
-                for (int u = 0; u < CH; ++u) {
-                    const int i = base + u0 + u;
-                    const bool in = u0 + u < Hs && i < N;
-                    ga[u] = in ? cj[2 * i] : 0.0;
-                    gb[u] = in ? cj[2 * i + 1] : 0.0;
-                    ea[u] = in ? om[2 * i] : 0.0;
-                    eb[u] = in ? om[2 * i + 1] : 0.0;
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int u = 0; u < CH; ++u) {
-                    const int i = base + u0 + u;
-                    const double g0 = ga[u], g1 = gb[u];
-                    const double o0 = qw.o0(g0, g1);
-                    const double o1 = qw.o1(g0, g1);
-                    const double t = g0 * o0 + g1 * o1;
-                    const double tf = g0 * ea[u] + g1 * eb[u];
-                    const bool on = u0 + u < Hs && i >= col && i < N;
-                    if (on) bad |= !isfinite(g0) || !isfinite(g1);
-                    s += on ? t : 0.0;
-                    fs += on ? tf : 0.0;
-                }
-            }
-        }
-        const double s2 = __shfl(s, (l + N) & 63, 64);
-        const double f2 = __shfl(fs, (l + N) & 63, 64);
-        if (l < N) {
-            double g = 2 * (s + s2);
-            if constexpr (ru_on<W>()) g = g + 2 * pb.Ru;   // G_ll + 2 Ru (ABI v5)
-            const double Dl = (g > 0.0 && g < kInf) ? rsqrt_nr(g) : 1.0;
-            w.D()[l] = Dl;
-            const double f = (2 * (fs + f2)) * Dl;
-            bad |= !isfinite(f) || !isfinite(Dl);
-            w.F()[l] = f;
-            if constexpr (!W::kSlim) {
-                w.vlo()[l] = -((-pb.umin) / Dl);
-                w.vhi()[l] = pb.umax / Dl;
-            }
-        }
-        NTM_WSYNC();
-        NTM_ACC(ST_SC_COL, tsc);
-        if (pb.mode == NTM_MODE_FULL_DU && l >= 1 && l < N) {
-            const double a = w.D()[l], b = w.D()[l - 1];
-            w.idun()[l] = 1.0 / sqrt(a * a + b * b);
-        }
-        if (with_state_rows) {
-            const bool lo = l < 2 * N, hi = !lo && l < 4 * N - 2 * Hs;
-            const int r = lo ? l : (hi ? l - 2 * N + 2 * Hs : 0);
-            const int jb = lo ? 0 : Hs;
-            const int jmax = r >> 1;
-            double rs = 0.0;
-            int last = -1, cnt = 0;
-            if (lo || hi) {
-                constexpr int CH = NTM_CH;
-                NTM_CHUNK_PRAGMA
-                for (int u0 = 0; u0 < Hs; u0 += CH) {
-                    double g[CH], dd[CH];
-#pragma unroll
-                    for (int u = 0; u < CH; ++u) {
-                        const int j = jb + u0 + u;
-                        const bool in = u0 + u < Hs && j < N;
-                        g[u] = in ? w.gt(r, j) : 0.0;
-                        dd[u] = in ? w.D()[j] : 0.0;
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int u = 0; u < CH; ++u) {
-                        const int j = jb + u0 + u;
-                        const double v = g[u] * dd[u];
-                        const bool in = u0 + u < Hs && j <= jmax;
-                        rs += in ? v * v : 0.0;
-                        if (in && g[u] != 0.0) { last = j; ++cnt; }
-                    }
-                }
-            }
-            // the row's second half sits on lane 2N + r - 2H (rows r >= 2H)
-            const int src = (l >= 2 * Hs && l < 2 * N) ? l + 2 * N - 2 * Hs : l;
-            const double rs2 = __shfl(rs, src & 63, 64);
-            const int last2 = __shfl(last, src & 63, 64);
-            const int cnt2 = __shfl(cnt, src & 63, 64);
-            if (lo) {
-                const bool two = src != l;
-                const double sr = two ? rs + rs2 : rs;
-                const int lr = (two && last2 >= 0) ? last2 : last;
-                const int cr = two ? cnt + cnt2 : cnt;
-                bad |= !isfinite(sr) || !isfinite(w.e()[r]);
-                const double ir = (sr > 0.0 && sr < kInf) ? rsqrt_nr(sr) : 0.0;
-                w.irn()[r] = ir;
-                w.rinfo()[r] = (lr + 1) | (cr > 1 ? kRowMulti : 0);
-                if (ir == 0.0) const_row(r);
-            }
-            NTM_WSYNC();
-        }
-        NTM_ACC(ST_SC_ROW, tsc);
-        const int code = gany<P>(bad != 0) ? 2 : ((fold_const<W>() && gany<P>(infe != 0)) ? 1 : 0);
-        NTM_ACC(ST_SC_END, tsc);
-        return code;
-    }
-    if (l < N) {
-        // one pass over Gamma's column l: the Gram diagonal G_ll and F_l = 2 Gamma_l' Om (e - r)
-        const double* cj = w.Gt() + w.gidx(2 * l, l) - 2 * l;
-        const double* om = w.xp();               // Om (e_i - r), from free_response
-        double s = 0.0, fs = 0.0;
-        constexpr int CH = NTM_CH;
-        if (fuse_colsum<W>() && cs) {           // summed by the lift
-            s = cs->s;
-            fs = cs->f;
-            bad |= cs->bad;
-        } else if constexpr (lane_masked_ok<P, CH, W>()) {   // terms i < l masked by lane
-            unsigned long long nf = 0ull;
-            scale_col_chunk_lanes<0>(qw, cj, om, s, fs, nf);
-            scale_col_chunk_lanes<5>(qw, cj, om, s, fs, nf);
-            scale_col_chunk_lanes<10>(qw, cj, om, s, fs, nf);
-            scale_col_chunk_lanes<15>(qw, cj, om, s, fs, nf);
-            bad |= (int)((nf >> l) & 1ull);
-        } else {
-        NTM_CHUNK_PRAGMA
-        for (int i0 = 0; i0 < N; i0 += CH) {     // fixed trip count, terms i < l masked; batched loads
-            double ga[CH], gb[CH], ea[CH], eb[CH];
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                const int i = i0 + u;
-                const bool in = i < N;
-                ga[u] = in ? cj[2 * i] : 0.0;
-                gb[u] = in ? cj[2 * i + 1] : 0.0;
-                ea[u] = in ? om[2 * i] : 0.0;
-                eb[u] = in ? om[2 * i + 1] : 0.0;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                const int i = i0 + u;
-                const double g0 = ga[u], g1 = gb[u];
-                const double o0 = qw.o0(g0, g1);
-                const double o1 = qw.o1(g0, g1);
-                const double t = g0 * o0 + g1 * o1;
-                const double tf = g0 * ea[u] + g1 * eb[u];
-                const bool on = i >= l && i < N;
-                if (on) bad |= !isfinite(g0) || !isfinite(g1);
-                s += on ? t : 0.0;
-                fs += on ? tf : 0.0;
-            }
-        }
-        }
-        double g = 2 * s;
-        if constexpr (ru_on<W>()) g = g + 2 * pb.Ru;   // G_ll + 2 Ru (ABI v5)
-        double Dl = (g > 0.0 && g < kInf) ? rsqrt_nr(g) : 1.0;
-        w.D()[l] = Dl;
-        double f = (2 * fs) * Dl;
-        bad |= !isfinite(f) || !isfinite(Dl);
-        w.F()[l] = f;
-        // V-space box of u_l (bc of the two u rows; same expressions as the oracle's b/rn)
-        if constexpr (!W::kSlim) {
-            w.vlo()[l] = -((-pb.umin) / Dl);
-            w.vhi()[l] = pb.umax / Dl;
-        }
-    }
-    NTM_WSYNC();
-    NTM_ACC(ST_SC_COL, tsc);
-    if (pb.mode == NTM_MODE_FULL_DU && l >= 1 && l < N) {      // rate-row norms |D (e_l - e_{l-1})|
-        const double a = w.D()[l], b = w.D()[l - 1];
-        w.idun()[l] = 1.0 / sqrt(a * a + b * b);
-    }
-    if (with_state_rows) {
-        for (int r = l; r < 2 * N; r += P) {
-            double s = 0.0;
-            const int jmax = r >> 1;
-            int last = -1, cnt = 0;
-            constexpr int CH = NTM_CH;
-            NTM_CHUNK_PRAGMA
-            for (int j0 = 0; j0 < N; j0 += CH) { // fixed trip count, j > jmax masked; batched loads
-                double g[CH], dd[CH];
-#pragma unroll
-                for (int u = 0; u < CH; ++u) {
-                    const int j = j0 + u;
-                    g[u] = j < N ? w.gt(r, j) : 0.0;
-                    dd[u] = j < N ? w.D()[j] : 0.0;
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int u = 0; u < CH; ++u) {
-                    const double v = g[u] * dd[u];
-                    const bool in = j0 + u <= jmax;
-                    s += in ? v * v : 0.0;
-                    if (in && g[u] != 0.0) { last = j0 + u; ++cnt; }
-                }
-            }
-            bad |= !isfinite(s) || !isfinite(w.e()[r]);
-            const double ir = (s > 0.0 && s < kInf) ? rsqrt_nr(s) : 0.0;
-            w.irn()[r] = ir;                     // 1/|Gamma_r D| (0: constant row)
-            w.rinfo()[r] = (last + 1) | (cnt > 1 ? kRowMulti : 0);
-            if (ir == 0.0) const_row(r);
-        }
-        NTM_WSYNC();
-    }
-    NTM_ACC(ST_SC_ROW, tsc);
-    const int code = gany<P>(bad != 0) ? 2 : ((fold_const<W>() && gany<P>(infe != 0)) ? 1 : 0);
-    NTM_ACC(ST_SC_END, tsc);
-    return code;
-}
-
-// the full scaled Hessian G~ (lower triangle, WS::gr) for the GI fallback
-template <int P, class W>
-__device__ __forceinline__ bool full_gram(const Prob& pb, const W& w, int l) {
-    int bad = 0;
-    if constexpr (W::kGiLdsL) {
-        gram_rows_put<P>(pb, w, [&](int j, int kk, double v) { w.grL(j, kk) = v; }, l);
-        NTM_WSYNC();
-        if (l < w.n()) {                      // scale_gram's expression order
-            const double Dl = w.D()[l];
-            for (int kk = 0; kk <= l; ++kk) {
-                const double v = w.grL(l, kk) * Dl * w.D()[kk];
-                bad |= !isfinite(v);
-                w.grL(l, kk) = v;
-            }
-        }
-    } else {
-        gram_rows<P>(pb, w, w.R(), l);
-        NTM_WSYNC();
-        bad = scale_gram<P>(w, w.R(), l);
-    }
-    NTM_WSYNC();
-    return !gany<P>(bad != 0);
-}
-
-// kept for the dense-row entry point (ntm_qp_device): G~ = D G D in place,
-// F~ = D F (G given in w.R()); no state rows
-template <int P, class W>
-__device__ __forceinline__ bool scale_phase(const W& w, int l, bool /*with_state_rows*/) {
-    const int N = w.n(), LD = w.ldj();
-    if (l < N) {
-        double g = w.R()[l + l * LD];
-        w.D()[l] = (g > 0.0) ? 1.0 / sqrt(g) : 1.0;
-    }
-    NTM_WSYNC();
-    int bad = scale_gram<P>(w, w.R(), l);
-    if (l < N) {
-        double f = w.F()[l] * w.D()[l];
-        bad |= !isfinite(f);
-        w.F()[l] = f;
-    }
-    NTM_WSYNC();
-    return !gany<P>(bad != 0);
-}
 
 // ---------------------------------------------------------------------------
 // Constraint-row providers (Lin U <= b form, getWLc.m row convention).  Row

@@ -634,7 +634,7 @@ bool force_generic() {
 // act almost alike) and sat up to ~1e-8 umax off the exact optimum; compiled into
 // the N = 20 kernel the paths cost mode 2 ~1% through register allocation.
 // The input weight Ru (ABI v5) is compiled into the generic kernels only (ru_on in
-// ntm_device.h), like D4 / D6: the reference's cost has none (Ru = 0).  So is a
+// ntm_ws.h), like D4 / D6: the reference's cost has none (Ru = 0).  So is a
 // stage weight other than the reference's Q = I (NTM_MPC_Sim.m:59; qi_on): the
 // specialised kernels up to NTM_QI_MAXN (N = 10, 20) take the identity for Om; the
 // N = 50 kernel keeps a general Om and runs any Q itself.
@@ -862,7 +862,7 @@ int ntm_ctx_set_scenarios(ntm_ctx* ctx, const ntm_scenario_gen* gen) {
 }
 
 void ntm_scenario_sample(const ntm_scenario_gen* gen, int64_t B, int32_t k, double* out4) {
-    // the device's own generator code (ntm_device.h), compiled for the host
+    // the device's own generator code (ntm_prob.h), compiled for the host
     for (int64_t s = 0; s < B; ++s) {
         const int64_t id = gen->first_id + s;
         out4[4 * s] = gen_factor(gen->seed, id, 0, gen->jbs_spread);

@@ -1,0 +1,479 @@
+// ntm_lanes.h — the inline-assembly helpers that run under a narrowed EXEC.  Three
+// families, all for the far N = 20 kernels (one scenario per wave, a row, a column
+// or a substitution step's unknown on its own lane): the lane-masked accumulation
+// of the triangular Gamma passes, the lane-masked lift recursion, and the
+// triangular substitutions of the echelon re-solve.  In each the lanes an
+// instruction belongs to are known at compile time, so the instruction runs with
+// EXEC narrowed to them where the plain form computes on every lane and selects.
+//
+// Rules every block (one asm statement) below follows.  The families' comments
+// add only what is their own: which lanes own what, why the result has the plain
+// form's bits, and what was measured.
+//
+// 1. EXEC is saved, ANDed into every mask, restored.  The entry EXEC is copied to
+//    an SGPR pair (s_mov_b64 at the head of a block; the echelon family saves it
+//    once per chain, esub_enter, and hands it to every statement).  Every mask a
+//    block installs is ANDed with the saved value, so lanes off on entry stay off
+//    whatever the mask says, and EXEC is restored before the statement ends: the
+//    compiler never sees it changed.  Only SALU builds the masks (compile-time
+//    shifts of -1, literals, an AND with a gate).
+// 2. A SALU write of EXEC needs no wait state before a VALU or an LDS instruction:
+//    s_and_saveexec followed by a VALU is what the compiler emits for every
+//    divergent branch, followed by a ds_write for every predicated store.  The
+//    cases for which the ISA lists wait states behind an EXEC write or a
+//    VALU-written SGPR (DPP, lane access, v_div_fmas, an EXECZ / VCCZ read) occur
+//    in no block: the lane reads of the echelon family are the compiler's, between
+//    two statements.  The one exception, a VALU that reads a VALU-written SGPR as
+//    a source, is rule 4.
+// 3. The end of a block: s_mov_b64 plus s_nop 0.  The compiler's hazard pass does
+//    not look into a statement, so it does not see the block's last VALU write.  A
+//    DPP read of that VGPR needs two wait states, a v_readlane_b32 one.  The
+//    restoring s_mov_b64 is one and the s_nop 0 behind it the second, so whatever
+//    the scheduler places next (a DPP or lane read of the result included) is
+//    covered.  The echelon statements end with the s_mov_b64 alone; their comment
+//    says why one wait state is enough there.
+// 4. A VALU-written SGPR.  A VALU write of an SGPR pair needs no wait state before
+//    the SALU that reads it (v_cmp then s_and / s_or), but a VALU that reads it as a
+//    source needs two, and the compiler does not count them into a statement.  So
+//    a block whose VALU takes an SGPR source that a VALU may have written directly
+//    ahead of the statement (the v_readlane_b32 broadcast of the echelon steps)
+//    opens with its s_and_b64 of EXEC and an s_nop 0 in front of that VALU.
+// 5. Memory.  A block that holds an LDS instruction clobbers "memory", which keeps
+//    the compiler's own accesses on their side of it; a block of VALU and SALU
+//    only does not.  The compiler's wait counts do not include a block's LDS
+//    operations.  Stores: LDS operations of one wave complete in order, so a
+//    compiler wait for a load issued before or after such a store only waits
+//    longer, never too little, and the last storing block of a phase ends with
+//    s_waitcnt lgkmcnt(0), so nothing uncounted is in flight behind it.  A VALU
+//    write of a VGPR needs no wait state before the LDS store that reads it as
+//    data (the interlock the compiler's own v_add, ds_write2 pairs rely on), and a
+//    store's data registers may be rewritten at once: the ISA asks for wait states
+//    there only after a vector-memory store of more than 64 bits (one or two), LDS
+//    stores are not in that list, and the compiler itself rewrites a ds_write2's
+//    data one instruction later.  Loads: they and their s_waitcnt lgkmcnt(0) stand
+//    in one statement, so no loaded register is visible to the compiler before it
+//    has landed.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "ntm_collectives.h"
+
+namespace ntm {
+
+// ---------------------------------------------------------------------------
+// Lane-masked accumulation (N = 20, one scenario per wave, row or column =
+// lane).  The triangular passes over the packed Gamma sum N fixed terms per
+// lane and zero the ones outside the lane's row or column with a select (two
+// v_cndmask and a v_cmp per fp64 term).  The lanes a term belongs to are
+// contiguous and known at compile time (lanes >= 2j for the term j of a row
+// pass, lanes <= i for the term i of a column pass), so the one accumulating
+// instruction runs with EXEC narrowed to them instead: a lane that is off keeps
+// its accumulator, which is what y + (+-0) leaves for any y other than -0.0.
+//   Row dots (v_fmac_f64; a row's own terms come first, the masked ones after):
+// the two forms differ on a lane the term does not belong to when x is not
+// finite (NaN from 0 x against y untouched) and when y is -0.0 there (+0.0 from
+// -0.0 + 0 against -0.0); never on a lane the term belongs to.
+//   Column passes (v_add_f64 of a term formed on every lane; the select form adds
+// +0.0, never a product with 0): a column's masked terms come first, onto the
+// +0.0 the sum starts from, so no accumulator is -0.0 where a term is masked
+// and the two forms are identical, whatever the data.
+//   One block per chunk of five terms, the masks s_lshl_b64 / s_lshr_b64 of -1 by
+// compile-time shifts (rule 1).  The blocks hold no memory instruction (rule 5);
+// the scaling pass's v_cmp_class writes an SGPR pair that only an s_or_b64 reads
+// (rule 4).
+//   Measured on the far N = 20 kernel at B = 1e5 (A/B on one box, three runs
+// each): the row dots 6.057 -> 5.962 ms per step-batch, the certificate's
+// gradient and the scaling pass's column pass on top 5.949 -> 5.772 ms; the
+// scaling pass's row pass (masked adds of the squares, the last / cnt tracking
+// left select-based) 5.762 -> 5.792 ms: not kept.  qdot_rows' callers take the
+// column from fidx[], not from the lane, so it keeps its selects.
+// ---------------------------------------------------------------------------
+template <int P, int CH, class W>
+__device__ __forceinline__ constexpr bool lane_masked_ok() {
+    // row r / column l sits on lane r / l: one scenario per wave, 2N <= 64, one trip of `r += P`.
+    // The far build only: its chunks hold five terms, which is what the asm blocks are written
+    // for; the all-LDS builds batch four terms per round trip (ntm_n20near.hip) and run their
+    // scaling pass split over idle lanes
+    return P == 64 && CH == 5 && W::kNN == 20 && W::kFar;
+}
+// EXEC = entry EXEC & (lanes >= s<k>) / (lanes <= 63 - s<k>), s<k> a compile-time shift
+#define NTM_LANES_FROM(k) "s_lshl_b64 %[m], -1, %[s" #k "]\n\ts_and_b64 exec, %[sv], %[m]\n\t"
+#define NTM_LANES_UPTO(k) "s_lshr_b64 %[m], -1, %[s" #k "]\n\ts_and_b64 exec, %[sv], %[m]\n\t"
+#define NTM_SHIFTS_FROM(J0) \
+    [s0] "n"(2 * (J0)), [s1] "n"(2 * (J0) + 2), [s2] "n"(2 * (J0) + 4), [s3] "n"(2 * (J0) + 6), [s4] "n"(2 * (J0) + 8)
+#define NTM_SHIFTS_UPTO(I0) \
+    [s0] "n"(63 - (I0)), [s1] "n"(62 - (I0)), [s2] "n"(61 - (I0)), [s3] "n"(60 - (I0)), [s4] "n"(59 - (I0))
+#define NTM_V5(n, a) [n##0] "v"(a[0]), [n##1] "v"(a[1]), [n##2] "v"(a[2]), [n##3] "v"(a[3]), [n##4] "v"(a[4])
+// y += g[u] x[u] on lanes >= 2 (J0 + u), u = 0..4 in order, one v_fmac_f64 each
+template <int J0>
+__device__ __forceinline__ void fmac5_lanes_from(double& y, const double (&g)[5], const double (&x)[5]) {
+    unsigned long long sv, m;
+#define NTM_TERM(k) NTM_LANES_FROM(k) "v_fmac_f64_e32 %[y], %[g" #k "], %[x" #k "]\n\t"
+    asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_TERM(0) NTM_TERM(1) NTM_TERM(2) NTM_TERM(3) NTM_TERM(4)
+                 "s_mov_b64 exec, %[sv]\n\ts_nop 0"
+                 : [y] "+v"(y), [sv] "=&s"(sv), [m] "=&s"(m)
+                 : NTM_V5(g, g), NTM_V5(x, x), NTM_SHIFTS_FROM(J0)
+                 : "scc");
+#undef NTM_TERM
+}
+// the same for two accumulators that share g and the masks: y1 += g x1, then y2 += g x2, per term
+template <int J0>
+__device__ __forceinline__ void fmac5x2_lanes_from(double& y1, double& y2, const double (&g)[5],
+                                                   const double (&x1)[5], const double (&x2)[5]) {
+    unsigned long long sv, m;
+#define NTM_TERM(k) \
+    NTM_LANES_FROM(k) "v_fmac_f64_e32 %[y1], %[g" #k "], %[a" #k "]\n\tv_fmac_f64_e32 %[y2], %[g" #k "], %[b" #k "]\n\t"
+    asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_TERM(0) NTM_TERM(1) NTM_TERM(2) NTM_TERM(3) NTM_TERM(4)
+                 "s_mov_b64 exec, %[sv]\n\ts_nop 0"
+                 : [y1] "+v"(y1), [y2] "+v"(y2), [sv] "=&s"(sv), [m] "=&s"(m)
+                 : NTM_V5(g, g), NTM_V5(a, x1), NTM_V5(b, x2), NTM_SHIFTS_FROM(J0)
+                 : "scc");
+#undef NTM_TERM
+}
+// s += t[u] on lanes <= I0 + u (column pass), one v_add_f64 each
+template <int I0>
+__device__ __forceinline__ void fadd5_lanes_upto(double& s, const double (&t)[5]) {
+    unsigned long long sv, m;
+#define NTM_TERM(k) NTM_LANES_UPTO(k) "v_add_f64 %[y], %[y], %[t" #k "]\n\t"
+    asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_TERM(0) NTM_TERM(1) NTM_TERM(2) NTM_TERM(3) NTM_TERM(4)
+                 "s_mov_b64 exec, %[sv]\n\ts_nop 0"
+                 : [y] "+v"(s), [sv] "=&s"(sv), [m] "=&s"(m)
+                 : NTM_V5(t, t), NTM_SHIFTS_UPTO(I0)
+                 : "scc");
+#undef NTM_TERM
+}
+// The scaling pass's column terms on lanes <= I0 + u: s += t[u], fs += tf[u], and the
+// lanes on which g0[u] or g1[u] is an infinity or a NaN ORed into the lane mask nf
+// (v_cmp_class under the narrowed EXEC writes zeros for the lanes that are off)
+template <int I0>
+__device__ __forceinline__ void fadd5x2_class_lanes_upto(double& s, double& fs, unsigned long long& nf,
+                                                         const double (&t)[5], const double (&tf)[5],
+                                                         const double (&g0)[5], const double (&g1)[5]) {
+    unsigned long long sv, m, c;
+    const int cls = 0x207;                                // signalling / quiet NaN, -inf, +inf
+#define NTM_TERM(k)                                                                                       \
+    NTM_LANES_UPTO(k) "v_cmp_class_f64_e64 %[c], %[p" #k "], %[cls]\n\ts_or_b64 %[nf], %[nf], %[c]\n\t" \
+                      "v_cmp_class_f64_e64 %[c], %[q" #k "], %[cls]\n\ts_or_b64 %[nf], %[nf], %[c]\n\t" \
+                      "v_add_f64 %[y], %[y], %[t" #k "]\n\tv_add_f64 %[z], %[z], %[u" #k "]\n\t"
+    asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_TERM(0) NTM_TERM(1) NTM_TERM(2) NTM_TERM(3) NTM_TERM(4)
+                 "s_mov_b64 exec, %[sv]\n\ts_nop 0"
+                 : [y] "+v"(s), [z] "+v"(fs), [nf] "+s"(nf), [sv] "=&s"(sv), [m] "=&s"(m), [c] "=&s"(c)
+                 : NTM_V5(t, t), NTM_V5(u, tf), NTM_V5(p, g0), NTM_V5(q, g1), [cls] "s"(cls), NTM_SHIFTS_UPTO(I0)
+                 : "scc");
+#undef NTM_TERM
+}
+#undef NTM_LANES_FROM
+#undef NTM_LANES_UPTO
+#undef NTM_SHIFTS_FROM
+#undef NTM_SHIFTS_UPTO
+#undef NTM_V5
+
+// ---------------------------------------------------------------------------
+// Lane-masked lift recursion (the slim far N = 20 lift: Gamma's column l on lane
+// l < N, the free response on lane N).  At stage i the lanes that advance are
+// known at compile time: columns 0..i-1 (their diagonal lies above row i) and
+// lane N, the mask ((1 << i) - 1) | (1 << N).  The select form computes the next
+// 2-vector on every lane, selects it or the old one, selects the store index
+// (i, or the lane's own diagonal again) and builds the address: a v_cmp, five
+// v_cndmask, a v_mov and a v_lshl_add per stage around four fp64 instructions,
+// the selects on the chain to the next stage.  Here the four instructions and the
+// pair store run with EXEC narrowed to that mask: a lane that is off keeps g0 /
+// g1 and stores nothing, where the select form re-stored the same bits to the
+// same place, so registers and LDS hold the same bits whatever the data.
+//   The arithmetic is the select form's as the production build compiles it, which
+// is not one form: the compiler contracts (a21 g0 + a22 g1) + c1 from either
+// product, and it does so by the stage's place in its chunk of five.  First and
+// last stage of a chunk (form A): t = g0 a21; t = fma(a22, g1, t); g0 = fma(g0,
+// a11, c0).  The three between (form B): t = a22 g1; t = fma(a21, g0, t); g0 =
+// fma(a11, g0, c0).  Both end g1 = c1 + t.  The two round differently, so each
+// stage keeps the form, and the operand order, it had.
+//   One block per chunk, the masks literals (rule 1).  a22 is wave-uniform in
+// every kernel (an SGPR pair, src0 of the v_fmac / v_mul); c0 / c1 differ between
+// the Gamma lanes and lane N: VGPRs.  The stores are in the block (ds_write2_b64
+// at rec + 16 i: immediate offsets), so rule 5's store half applies: the last
+// chunk is the one that ends with s_waitcnt lgkmcnt(0), and a store's data
+// registers are next written by the following stage's v_fma / v_add, three or
+// more instructions behind it (s_and, v_mul, v_fmac), or behind the restoring
+// s_mov, the s_nop and the next block's s_mov / s_and.  After the block (rule 3):
+// the last VALU write (g1) is followed by the store, the restoring s_mov and the
+// s_nop 0, more than the two wait states a DPP or lane read of it needs.
+//   Measured on the far N = 20 kernel at B = 1e5 (A/B on one box, three runs
+// each): 5.804 -> 5.602 ms per step-batch, outputs byte-equal; VALU instructions
+// per wave-step 25,977 -> 24,475, the fp64 ones unchanged.
+// ---------------------------------------------------------------------------
+#define NTM_V5(n, a) [n##0] "v"(a[0]), [n##1] "v"(a[1]), [n##2] "v"(a[2]), [n##3] "v"(a[3]), [n##4] "v"(a[4])
+#define NTM_LIFT_MASK(k) "s_and_b64 exec, %[sv], %[m" #k "]\n\t"
+#define NTM_LIFT_PUT(k) "ds_write2_b64 %[rec], %[g0], %[g1] offset0:%[o" #k "] offset1:%[p" #k "]\n\t"
+#define NTM_LIFT_A(k)                                                                                    \
+    NTM_LIFT_MASK(k) "v_mul_f64 %[t], %[g0], %[b" #k "]\n\tv_fmac_f64_e32 %[t], %[a22], %[g1]\n\t"       \
+                     "v_fma_f64 %[g0], %[g0], %[a" #k "], %[c0]\n\tv_add_f64 %[g1], %[c1], %[t]\n\t" NTM_LIFT_PUT(k)
+#define NTM_LIFT_B(k)                                                                                    \
+    NTM_LIFT_MASK(k) "v_mul_f64 %[t], %[a22], %[g1]\n\tv_fmac_f64_e32 %[t], %[b" #k "], %[g0]\n\t"       \
+                     "v_fma_f64 %[g0], %[a" #k "], %[g0], %[c0]\n\tv_add_f64 %[g1], %[c1], %[t]\n\t" NTM_LIFT_PUT(k)
+#define NTM_LIFT_N(k, I0) \
+    [m##k] "n"(((1 << ((I0) + k)) - 1) | (1 << 20)), [o##k] "n"(2 * ((I0) + k)), [p##k] "n"(2 * ((I0) + k) + 1)
+// stages I0 .. I0 + NS - 1 (NS = 5, or 4 in the last chunk, which also drains the stores) of
+// g <- A_i g + c on the lanes < i and lane 20, each stage's pair stored at rec + 16 i bytes
+// (rec: the lane's LDS byte address).  ca / cb: a11 / a21 of the chunk's stages
+template <int I0, int NS>
+__device__ __forceinline__ void lift_chunk_lanes(double& g0, double& g1, const double (&ca)[5], const double (&cb)[5],
+                                                 double a22, double c0, double c1, unsigned rec) {
+    static_assert(I0 >= 1 && (NS == 4 || NS == 5) && I0 + NS <= 20, "stages 1..19 of the N = 20 lift");
+    unsigned long long sv;
+    double t;
+    if constexpr (NS == 5) {
+        asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_LIFT_A(0) NTM_LIFT_B(1) NTM_LIFT_B(2) NTM_LIFT_B(3) NTM_LIFT_A(4)
+                     "s_mov_b64 exec, %[sv]\n\ts_nop 0"
+                     : [g0] "+v"(g0), [g1] "+v"(g1), [t] "=&v"(t), [sv] "=&s"(sv)
+                     : NTM_V5(a, ca), NTM_V5(b, cb), [a22] "s"(a22), [c0] "v"(c0), [c1] "v"(c1), [rec] "v"(rec),
+                       NTM_LIFT_N(0, I0), NTM_LIFT_N(1, I0), NTM_LIFT_N(2, I0), NTM_LIFT_N(3, I0), NTM_LIFT_N(4, I0)
+                     : "scc", "memory");
+    } else {
+        asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_LIFT_A(0) NTM_LIFT_B(1) NTM_LIFT_B(2) NTM_LIFT_B(3)
+                     "s_mov_b64 exec, %[sv]\n\ts_waitcnt lgkmcnt(0)"
+                     : [g0] "+v"(g0), [g1] "+v"(g1), [t] "=&v"(t), [sv] "=&s"(sv)
+                     : [a0] "v"(ca[0]), [a1] "v"(ca[1]), [a2] "v"(ca[2]), [a3] "v"(ca[3]), [b0] "v"(cb[0]),
+                       [b1] "v"(cb[1]), [b2] "v"(cb[2]), [b3] "v"(cb[3]), [a22] "s"(a22), [c0] "v"(c0), [c1] "v"(c1),
+                       [rec] "v"(rec), NTM_LIFT_N(0, I0), NTM_LIFT_N(1, I0), NTM_LIFT_N(2, I0), NTM_LIFT_N(3, I0)
+                     : "scc", "memory");
+    }
+}
+#undef NTM_LIFT_MASK
+#undef NTM_LIFT_PUT
+#undef NTM_LIFT_A
+#undef NTM_LIFT_B
+#undef NTM_LIFT_N
+#undef NTM_V5
+
+// ---------------------------------------------------------------------------
+// Lane-masked triangular substitutions of the echelon re-solve (the slim far
+// N = 20 kernels: the sorted E packed in LDS, row t at Ep + t(t+1)/2, n <= 20
+// rows, one scenario per wave).  Forward (E V = h, and E Z = -e_c with it when
+// k = 1): lane l owns row l, step t forms x_t = acc_t / E_tt on lane t, takes it
+// by two v_readlane_b32 and subtracts E_lt x_t on the rows below.  Backward (E'
+// mu = grad): lane l owns column l, the steps descend from u = n - 1 and update
+// the columns l < u.  The loop form does every step on every lane: a select
+// captures x on the lane l == t (a v_cmp, two v_mov, two v_cndmask per right-hand
+// side), the element load sits under a saved EXEC with a branch and its wait
+// directly in front of the fma, the address is rebuilt per step.  Here the steps
+// are unrolled over the compile-time t in batches of five: a batch's five
+// elements are loaded first (ds_read_b64 at immediate offsets from one per-lane
+// address, each under EXEC = the lanes that will use it: t < l < n forward, l < u
+// backward, so nothing past a row's diagonal is read), waited for once, and
+// the five chain steps follow without an LDS wait.  Per step and right-hand
+// side: one v_mul_f64 (acc sq_id, written straight into x under EXEC = lanes t <=
+// l < n: lane t's x is final after step t because the later steps exclude it, so
+// there is no select), the two v_readlane_b32 (the compiler's, between two
+// statements: v_readlane ignores EXEC, and a statement cannot name the halves of
+// a 64-bit operand), one v_fma_f64 under EXEC = lanes t < l < n.
+//   Bit-equality with the loop form, whatever the data: a lane l <= t there goes
+// on computing acc -= 0 x_t after its x was captured, and a lane >= n does so from
+// the start; neither acc is read again, by the loop or behind it.  x (zz, mu) of a
+// lane < n is the same product acc sq_id of the same chain (v_mul_f64 with sq_id as
+// src0; v_fma_f64 with the negated element as src0, the broadcast as src1: the
+// operands, and so the NaN a non-finite step propagates, as the loop form was
+// compiled); lanes >= n and lanes off on entry keep what they held (0.0 in the
+// kernel).  A step t >= n inside a batch runs with an empty EXEC (the masks are ANDed
+// with the lanes < n); backward a step u >= n would pass `lanes <= u`, so each
+// step's masks are ANDed with a gate that is the entry EXEC if u < n and 0 if not
+// (SALU, only in the batch the chain enters through).
+//   The masks are 32-bit literals with bit 31 clear (n <= 20), ANDed with the
+// entry EXEC that esub_enter saved, which every statement restores before it ends
+// (rule 1).  v_mul_f64's result is read by v_readlane_b32 (one wait state): the
+// restoring s_mov_b64 stands between them in every statement (rule 3).  The
+// v_readlane's SGPR result feeds the v_fma_f64 as a source, and the v_readlane_b32
+// may be the last thing ahead of the statement, so each step's s_and_b64 is
+// followed by an s_nop 0 (rule 4).  A batch's loads and their wait are one
+// statement (rule 5); the steps hold no memory instruction.
+//   Measured on the far N = 20 kernel at B = 1e5 (A/B on one box, three runs
+// each): the forward substitution 5.592 -> 5.495 ms per step-batch, the backward
+// one on top 5.490 -> 5.405 ms, outputs byte-equal; VALU instructions per wave-
+// step 24,475 -> 23,419.
+// ---------------------------------------------------------------------------
+template <int P, int CH, class W>
+__device__ __forceinline__ constexpr bool esub_lanes_ok() {
+    if constexpr (W::kSlim) return lane_masked_ok<P, CH, W>();
+    else return false;
+}
+struct LaneExec {
+    unsigned long long sv;                                // EXEC on entry
+    unsigned long long mb;                                // its lanes below n
+};
+__device__ __forceinline__ LaneExec esub_enter(int n) {   // n wave-uniform, 0..20
+    LaneExec x;
+    const unsigned long long low = (1ull << n) - 1ull;
+    asm volatile("s_mov_b64 %[sv], exec\n\ts_and_b64 %[mb], exec, %[lo]"
+                 : [sv] "=&s"(x.sv), [mb] "=&s"(x.mb)
+                 : [lo] "s"(low)
+                 : "scc");
+    return x;
+}
+constexpr unsigned esub_ge(int t) { return 0xFFFFFu & ~((1u << t) - 1u); }   // lanes t..19
+constexpr unsigned esub_gt(int t) { return 0xFFFFFu & ~((2u << t) - 1u); }   // lanes t+1..19
+constexpr unsigned esub_le(int u) { return (2u << u) - 1u; }                 // lanes 0..u
+constexpr unsigned esub_lt(int u) { return (1u << u) - 1u; }                 // lanes 0..u-1
+#define NTM_ESUB_LD(k) "s_and_b64 exec, %[mk], %[m" #k "]\n\tds_read_b64 %[e" #k "], %[at] offset:%[o" #k "]\n\t"
+// forward batch T0..T0+4: the five loads E[l][T0 + k] (lanes > T0 + k below n), step T0's product(s), one wait
+template <int T0, bool TWO>
+__device__ __forceinline__ void fsub_open(double (&e)[5], double acc, double& x, double acz, double& zz, double sq,
+                                          unsigned row, const LaneExec& c) {
+    static_assert(T0 >= 0 && T0 + 5 <= 20, "steps 0..19");
+    if constexpr (TWO) {
+        asm volatile(NTM_ESUB_LD(0) NTM_ESUB_LD(1) NTM_ESUB_LD(2) NTM_ESUB_LD(3) NTM_ESUB_LD(4)
+                     "s_and_b64 exec, %[mk], %[ge]\n\tv_mul_f64 %[x], %[sq], %[acc]\n\tv_mul_f64 %[z], %[sq], %[acz]\n\t"
+                     "s_waitcnt lgkmcnt(0)\n\ts_mov_b64 exec, %[sv]"
+                     : [e0] "=&v"(e[0]), [e1] "=&v"(e[1]), [e2] "=&v"(e[2]), [e3] "=&v"(e[3]), [e4] "=&v"(e[4]),
+                       [x] "+v"(x), [z] "+v"(zz)
+                     : [acc] "v"(acc), [acz] "v"(acz), [sq] "v"(sq), [at] "v"(row), [mk] "s"(c.mb), [sv] "s"(c.sv),
+                       [ge] "n"(esub_ge(T0)), [m0] "n"(esub_gt(T0)), [m1] "n"(esub_gt(T0 + 1)), [m2] "n"(esub_gt(T0 + 2)),
+                       [m3] "n"(esub_gt(T0 + 3)), [m4] "n"(esub_gt(T0 + 4)), [o0] "n"(8 * T0), [o1] "n"(8 * (T0 + 1)),
+                       [o2] "n"(8 * (T0 + 2)), [o3] "n"(8 * (T0 + 3)), [o4] "n"(8 * (T0 + 4))
+                     : "scc", "memory");
+    } else {
+        asm volatile(NTM_ESUB_LD(0) NTM_ESUB_LD(1) NTM_ESUB_LD(2) NTM_ESUB_LD(3) NTM_ESUB_LD(4)
+                     "s_and_b64 exec, %[mk], %[ge]\n\tv_mul_f64 %[x], %[sq], %[acc]\n\t"
+                     "s_waitcnt lgkmcnt(0)\n\ts_mov_b64 exec, %[sv]"
+                     : [e0] "=&v"(e[0]), [e1] "=&v"(e[1]), [e2] "=&v"(e[2]), [e3] "=&v"(e[3]), [e4] "=&v"(e[4]),
+                       [x] "+v"(x)
+                     : [acc] "v"(acc), [sq] "v"(sq), [at] "v"(row), [mk] "s"(c.mb), [sv] "s"(c.sv),
+                       [ge] "n"(esub_ge(T0)), [m0] "n"(esub_gt(T0)), [m1] "n"(esub_gt(T0 + 1)), [m2] "n"(esub_gt(T0 + 2)),
+                       [m3] "n"(esub_gt(T0 + 3)), [m4] "n"(esub_gt(T0 + 4)), [o0] "n"(8 * T0), [o1] "n"(8 * (T0 + 1)),
+                       [o2] "n"(8 * (T0 + 2)), [o3] "n"(8 * (T0 + 3)), [o4] "n"(8 * (T0 + 4))
+                     : "scc", "memory");
+    }
+}
+// forward step T: acc -= E[l][T] x_T on lanes > T, then (NEXT) step T + 1's product(s) on lanes >= T + 1,
+// the same lanes: one mask
+template <int T, bool TWO, bool NEXT>
+__device__ __forceinline__ void fsub_step(double et, double& acc, double& x, double& acz, double& zz, double sq,
+                                          const LaneExec& c) {
+    const double xt = gbcast<64>(x, T);
+    if constexpr (TWO) {
+        const double zt = gbcast<64>(zz, T);
+        if constexpr (NEXT)
+            asm volatile("s_and_b64 exec, %[mk], %[gt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
+                         "v_fma_f64 %[acz], -%[e], %[zt], %[acz]\n\t"
+                         "v_mul_f64 %[x], %[sq], %[acc]\n\tv_mul_f64 %[z], %[sq], %[acz]\n\ts_mov_b64 exec, %[sv]"
+                         : [acc] "+v"(acc), [acz] "+v"(acz), [x] "+v"(x), [z] "+v"(zz)
+                         : [e] "v"(et), [xt] "s"(xt), [zt] "s"(zt), [sq] "v"(sq), [mk] "s"(c.mb), [sv] "s"(c.sv),
+                           [gt] "n"(esub_gt(T))
+                         : "scc");
+        else if constexpr (esub_gt(T) != 0)
+            asm volatile("s_and_b64 exec, %[mk], %[gt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
+                         "v_fma_f64 %[acz], -%[e], %[zt], %[acz]\n\ts_mov_b64 exec, %[sv]"
+                         : [acc] "+v"(acc), [acz] "+v"(acz)
+                         : [e] "v"(et), [xt] "s"(xt), [zt] "s"(zt), [mk] "s"(c.mb), [sv] "s"(c.sv), [gt] "n"(esub_gt(T))
+                         : "scc");
+    } else {
+        if constexpr (NEXT)
+            asm volatile("s_and_b64 exec, %[mk], %[gt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
+                         "v_mul_f64 %[x], %[sq], %[acc]\n\ts_mov_b64 exec, %[sv]"
+                         : [acc] "+v"(acc), [x] "+v"(x)
+                         : [e] "v"(et), [xt] "s"(xt), [sq] "v"(sq), [mk] "s"(c.mb), [sv] "s"(c.sv),
+                           [gt] "n"(esub_gt(T))
+                         : "scc");
+        else if constexpr (esub_gt(T) != 0)
+            asm volatile("s_and_b64 exec, %[mk], %[gt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
+                         "s_mov_b64 exec, %[sv]"
+                         : [acc] "+v"(acc)
+                         : [e] "v"(et), [xt] "s"(xt), [mk] "s"(c.mb), [sv] "s"(c.sv), [gt] "n"(esub_gt(T))
+                         : "scc");
+    }
+}
+template <int T0, bool TWO>
+__device__ __forceinline__ void fsub_batch(double& acc, double& x, double& acz, double& zz, double sq, unsigned row,
+                                           const LaneExec& c) {
+    double e[5];
+    fsub_open<T0, TWO>(e, acc, x, acz, zz, sq, row, c);
+    fsub_step<T0, TWO, true>(e[0], acc, x, acz, zz, sq, c);
+    fsub_step<T0 + 1, TWO, true>(e[1], acc, x, acz, zz, sq, c);
+    fsub_step<T0 + 2, TWO, true>(e[2], acc, x, acz, zz, sq, c);
+    fsub_step<T0 + 3, TWO, true>(e[3], acc, x, acz, zz, sq, c);
+    fsub_step<T0 + 4, TWO, false>(e[4], acc, x, acz, zz, sq, c);
+}
+// E x = acc (TWO: and E zz = acz) for the lanes < n of the entry EXEC; row: the LDS byte address of
+// the lane's row of the packed E, sq: 1 / E[l][l].  n wave-uniform; the chain leaves at a batch boundary
+template <bool TWO>
+__device__ __forceinline__ void fsub_lanes(int n, double& acc, double& x, double& acz, double& zz, double sq,
+                                           unsigned row) {
+    const LaneExec c = esub_enter(n);
+    if (n > 0) fsub_batch<0, TWO>(acc, x, acz, zz, sq, row, c);
+    if (n > 5) fsub_batch<5, TWO>(acc, x, acz, zz, sq, row, c);
+    if (n > 10) fsub_batch<10, TWO>(acc, x, acz, zz, sq, row, c);
+    if (n > 15) fsub_batch<15, TWO>(acc, x, acz, zz, sq, row, c);
+}
+// backward batch U0+4 .. U0 (descending): the loads E[u][l] (lanes < u), step U0 + 4's product, one wait.
+// g: the gate of step U0 + 4 (the entry EXEC, or 0 if the step lies at or above n)
+template <int U0>
+__device__ __forceinline__ void bsub_open(double (&e)[5], double acc, double& mu, double sq, unsigned col,
+                                          unsigned long long g, const LaneExec& c) {
+    static_assert(U0 >= 0 && U0 + 5 <= 20, "steps 19..0");
+    constexpr int o0 = 4 * (U0 + 4) * (U0 + 5), o1 = 4 * (U0 + 3) * (U0 + 4), o2 = 4 * (U0 + 2) * (U0 + 3),
+                  o3 = 4 * (U0 + 1) * (U0 + 2), o4 = 4 * U0 * (U0 + 1);           // 8 u (u + 1) / 2 bytes
+    asm volatile(NTM_ESUB_LD(0) NTM_ESUB_LD(1) NTM_ESUB_LD(2) NTM_ESUB_LD(3) NTM_ESUB_LD(4)
+                 "s_and_b64 exec, %[g], %[le]\n\tv_mul_f64 %[x], %[sq], %[acc]\n\t"
+                 "s_waitcnt lgkmcnt(0)\n\ts_mov_b64 exec, %[sv]"
+                 : [e0] "=&v"(e[0]), [e1] "=&v"(e[1]), [e2] "=&v"(e[2]), [e3] "=&v"(e[3]), [e4] "=&v"(e[4]), [x] "+v"(mu)
+                 : [acc] "v"(acc), [sq] "v"(sq), [at] "v"(col), [mk] "s"(c.sv), [sv] "s"(c.sv), [g] "s"(g),
+                   [le] "n"(esub_le(U0 + 4)), [m0] "n"(esub_lt(U0 + 4)), [m1] "n"(esub_lt(U0 + 3)),
+                   [m2] "n"(esub_lt(U0 + 2)), [m3] "n"(esub_lt(U0 + 1)), [m4] "n"(esub_lt(U0)), [o0] "n"(o0),
+                   [o1] "n"(o1), [o2] "n"(o2), [o3] "n"(o3), [o4] "n"(o4)
+                 : "scc", "memory");
+}
+#undef NTM_ESUB_LD
+// backward step U: acc -= E[U][l] mu_U on lanes < U under the step's gate g, then (NEXT) step U - 1's product
+// on lanes <= U - 1 (the same lanes) under its gate gn
+template <int U, bool NEXT, bool GATED>
+__device__ __forceinline__ void bsub_step(double eu, double& acc, double& mu, double sq, unsigned long long g,
+                                          unsigned long long gn, const LaneExec& c) {
+    const double mu_u = gbcast<64>(mu, U);
+    if constexpr (NEXT && U > 0 && !GATED)               // both gates are the entry EXEC: one mask
+        asm volatile("s_and_b64 exec, %[g], %[lt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
+                     "v_mul_f64 %[x], %[sq], %[acc]\n\ts_mov_b64 exec, %[sv]"
+                     : [acc] "+v"(acc), [x] "+v"(mu)
+                     : [e] "v"(eu), [xt] "s"(mu_u), [sq] "v"(sq), [g] "s"(g), [sv] "s"(c.sv), [lt] "n"(esub_lt(U))
+                     : "scc");
+    else if constexpr (NEXT && U > 0)
+        asm volatile("s_and_b64 exec, %[g], %[lt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
+                     "s_and_b64 exec, %[gn], %[le]\n\tv_mul_f64 %[x], %[sq], %[acc]\n\t"
+                     "s_mov_b64 exec, %[sv]"
+                     : [acc] "+v"(acc), [x] "+v"(mu)
+                     : [e] "v"(eu), [xt] "s"(mu_u), [sq] "v"(sq), [g] "s"(g), [gn] "s"(gn), [sv] "s"(c.sv),
+                       [lt] "n"(esub_lt(U)), [le] "n"(esub_le(U > 0 ? U - 1 : 0))
+                     : "scc");
+    else if constexpr (U > 0)
+        asm volatile("s_and_b64 exec, %[g], %[lt]\n\ts_nop 0\n\tv_fma_f64 %[acc], -%[e], %[xt], %[acc]\n\t"
+                     "s_mov_b64 exec, %[sv]"
+                     : [acc] "+v"(acc)
+                     : [e] "v"(eu), [xt] "s"(mu_u), [g] "s"(g), [sv] "s"(c.sv), [lt] "n"(esub_lt(U))
+                     : "scc");
+}
+template <int U0, bool GATED>
+__device__ __forceinline__ void bsub_batch(int n, double& acc, double& mu, double sq, unsigned col, const LaneExec& c) {
+    double e[5];
+    auto gate = [&](int u) -> unsigned long long { return (!GATED || u < n) ? c.sv : 0ull; };
+    bsub_open<U0>(e, acc, mu, sq, col, gate(U0 + 4), c);
+    bsub_step<U0 + 4, true, GATED>(e[0], acc, mu, sq, gate(U0 + 4), gate(U0 + 3), c);
+    bsub_step<U0 + 3, true, GATED>(e[1], acc, mu, sq, gate(U0 + 3), gate(U0 + 2), c);
+    bsub_step<U0 + 2, true, GATED>(e[2], acc, mu, sq, gate(U0 + 2), gate(U0 + 1), c);
+    bsub_step<U0 + 1, true, GATED>(e[3], acc, mu, sq, gate(U0 + 1), gate(U0), c);
+    bsub_step<U0, false, GATED>(e[4], acc, mu, sq, gate(U0), 0ull, c);
+}
+// E' mu = acc for the lanes < n of the entry EXEC; col: the LDS byte address of E[0][l] (Ep + l), sq: 1 /
+// E[l][l].  The batch that holds step n - 1 is gated per step, the ones below it are not
+template <int U0>
+__device__ __forceinline__ void bsub_from(int n, double& acc, double& mu, double sq, unsigned col, const LaneExec& c) {
+    if (n > U0) {
+        if (n >= U0 + 5) bsub_batch<U0, false>(n, acc, mu, sq, col, c);
+        else bsub_batch<U0, true>(n, acc, mu, sq, col, c);
+    }
+}
+__device__ __forceinline__ void bsub_lanes(int n, double& acc, double& mu, double sq, unsigned col) {
+    const LaneExec c = esub_enter(n);
+    bsub_from<15>(n, acc, mu, sq, col, c);
+    bsub_from<10>(n, acc, mu, sq, col, c);
+    bsub_from<5>(n, acc, mu, sq, col, c);
+    bsub_from<0>(n, acc, mu, sq, col, c);
+}
+
+}  // namespace ntm

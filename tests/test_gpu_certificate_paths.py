@@ -1,5 +1,6 @@
 """The certified re-solve's predicate collectives and exact-division shortcuts
-(polish_compact, csrc/ntm_device.h): the stand-alone collectives check, the drop
+(polish_compact in csrc/ntm_device.h, gany / gall / gargmin in csrc/ntm_collectives.h): the
+stand-alone collectives check, the drop
 position of a dual-infeasible candidate against the NumPy oracle's multipliers, a
 candidate set holding a single-entry state row (the one case that still takes
 the IEEE division for a fixed variable's multiplier), and the rejected
@@ -9,15 +10,12 @@ test_gpu_parity.py documents.
 Tolerance: max |U_gpu - U_oracle| / umax <= 1e-10, the step tests' bound
 (test_gpu_parity.py).
 """
-import os
-import shutil
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 import torch
 
+from checkprog import build_and_run
 from oracle import cbind
 from oracle import ntm_oracle as O
 
@@ -25,7 +23,6 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 U_TOL = 1e-10
-ROOT = Path(__file__).resolve().parent.parent
 
 
 def T(a):
@@ -45,13 +42,7 @@ def cfgs(N, mode):
 def test_collectives_check(tmp_path):
     """tools/collectives_check.hip: gany / gall and the payload-free gargmin against
     the DPP forms, P = 16, 32 and 64, one PASS line."""
-    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    exe = tmp_path / "collectives_check"
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O2", "-o", str(exe), str(ROOT / "tools" / "collectives_check.hip")],
-                   check=True, timeout=300)
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
-    print(p.stdout)
-    assert p.returncode == 0 and p.stdout.startswith("PASS"), p.stdout + p.stderr
+    build_and_run("collectives_check", tmp_path, "-O2")
 
 
 def _workspace(N, B, sets):

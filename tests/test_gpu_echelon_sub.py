@@ -1,5 +1,5 @@
 """The lane-masked triangular substitutions of the N = 20 far kernels' echelon re-solve
-(csrc/ntm_device.h: fsub_lanes / bsub_lanes under polish_compact): the forward
+(csrc/ntm_lanes.h: fsub_lanes / bsub_lanes; under polish_compact, csrc/ntm_device.h): the forward
 substitution E V = h (with E Z = -e_c when k = 1) and the certificate's back
 substitution E' mu = grad run unrolled in batches of five steps with EXEC narrowed
 to the lanes a step touches, where they used to compute on every lane and select.
@@ -13,22 +13,17 @@ and more (a second batch of steps), square sets (k = 0, one right-hand side) and
 sets with a spare column (k = 1, two)."""
 from __future__ import annotations
 
-import os
-import shutil
-import subprocess
-from pathlib import Path
-
 import numpy as np
 import pytest
 import torch
 
+from checkprog import build_and_run
 from oracle import cbind
 from oracle import ntm_oracle as O
 from test_gpu_parity import DEV, H, RUN_TOL, T, U_TOL, X_TOL, _assert_run_close, _teacher_forced, _teacher_forced_loop, cfgs
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parent.parent
 FAR_NAME = "k_mpc_step<P=64,NN=20,far>"
 N, B = 20, 8
 # The scenarios are ids 0..7 of the seeded set (O.scenario_x0).  The oracle's own optimal
@@ -52,13 +47,7 @@ def test_echelon_sub_check(tmp_path):
     form for every n = 0..20 and nc = -1..n, random lower-triangular E with exact zeros,
     -0.0 right-hand sides, an infinity and a NaN in h, in an element and in a diagonal
     reciprocal, three entry EXECs, a signalling NaN past the triangle; one PASS line."""
-    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    exe = tmp_path / "echelon_sub_check"
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-o", str(exe), str(ROOT / "tools" / "echelon_sub_check.hip")],
-                   check=True, timeout=300)
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
-    print(p.stdout)
-    assert p.returncode == 0 and p.stdout.startswith("PASS"), p.stdout + p.stderr
+    build_and_run("echelon_sub_check", tmp_path, "-O3")
 
 
 @pytest.mark.parametrize("mode", [1, 2])

@@ -1,5 +1,5 @@
-"""The lane-masked lift recursion of the N = 20 far kernels (csrc/ntm_device.h:
-lift_chunk_lanes / lift_chunk_at under lift_phase's slim branch): stage i of
+"""The lane-masked lift recursion of the N = 20 far kernels (csrc/ntm_lanes.h:
+lift_chunk_lanes; csrc/ntm_lift.h: lift_chunk_at under lift_phase's slim branch): stage i of
 Gamma's columns and of the free response runs with EXEC narrowed to the lanes
 that advance at that stage, where it used to compute on every lane and select.
 
@@ -11,21 +11,17 @@ against the C oracle at the step and closed-loop tests' tolerances."""
 from __future__ import annotations
 
 import math
-import os
-import shutil
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+from checkprog import build_and_run
 from oracle import cbind
 from oracle import ntm_oracle as O
 from test_gpu_parity import H, RUN_TOL, T, U_TOL, X_TOL, _assert_run_close, _teacher_forced, cfgs
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parent.parent
 FAR_NAME = "k_mpc_step<P=64,NN=20,far>"
 # plasma spread and w disturbance, as tests/test_gpu_scenarios.py sets them
 GEN = O.ScenarioGen(seed=20241220, first_id=0, k0=0, sigma_w=1e-3, sigma_omega=0.0, jbs_spread=0.1,
@@ -39,13 +35,7 @@ def test_lift_lanes_check(tmp_path):
     unchanged), the chunk helpers under the kernel's entry EXEC, all 64 lanes on and an
     irregular subset (lanes above N and lanes off on entry write nothing), EXEC after the
     helpers; one PASS line."""
-    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    exe = tmp_path / "lift_lanes_check"
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-o", str(exe), str(ROOT / "tools" / "lift_lanes_check.hip")],
-                   check=True, timeout=300)
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
-    print(p.stdout)
-    assert p.returncode == 0 and p.stdout.startswith("PASS"), p.stdout + p.stderr
+    build_and_run("lift_lanes_check", tmp_path, "-O3")
 
 
 @pytest.mark.parametrize("mode", [0, 1, 2])

@@ -1,4 +1,4 @@
-"""The lane-masked triangular Gamma passes of the N = 20 far kernel (csrc/ntm_device.h):
+"""The lane-masked triangular Gamma passes of the N = 20 far kernel (csrc/ntm_lanes.h, ntm_dots.h):
 the row dots (fmac5_lanes_from / fmac5x2_lanes_from under gamma_row_dot /
 gamma_row_dot2), the certificate's gradient (fadd5_lanes_upto under dot_rows2) and
 the scaling pass's column pass (fadd5x2_class_lanes_upto, with its non-finite flag).
@@ -9,22 +9,17 @@ far build, forced at a small batch, through all of these passes against the C or
 at the step tests' tolerance with the exit flags exact."""
 from __future__ import annotations
 
-import os
-import shutil
-import subprocess
-from pathlib import Path
-
 import numpy as np
 import pytest
 import torch
 
+from checkprog import build_and_run
 from oracle import cbind
 from oracle import ntm_oracle as O
 from test_gpu_parity import H, T, U_TOL, X_TOL, _teacher_forced, cfgs
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parent.parent
 FAR_NAME = "k_mpc_step<P=64,NN=20,far>"
 
 
@@ -34,13 +29,7 @@ def test_masked_dot_check(tmp_path):
     accumulators through -0.0, entry EXEC with the lanes >= 40 off and with an irregular
     pattern off (off lanes write nothing, keep their sums, set no non-finite bit), EXEC
     after the helper, non-finite data; one PASS line."""
-    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    exe = tmp_path / "masked_dot_check"
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-o", str(exe), str(ROOT / "tools" / "masked_dot_check.hip")],
-                   check=True, timeout=300)
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
-    print(p.stdout)
-    assert p.returncode == 0 and p.stdout.startswith("PASS"), p.stdout + p.stderr
+    build_and_run("masked_dot_check", tmp_path, "-O3")
 
 
 def test_far_build_two_teacher_forced_steps(ctl):

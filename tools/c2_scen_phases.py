@@ -16,7 +16,7 @@ WARM = int(sys.argv[3]) if len(sys.argv) > 3 else 5
 picks = [int(s) for s in sys.argv[4:]] or [1023, 386]
 ctl = NtmMpc(config=cfg)
 lib = ntm_mpc.load()
-buf = (C.c_ulonglong * 104)()
+buf = (C.c_ulonglong * 104)()   # NTM_NSTAMPS of csrc/ntm_diag.h (the library exports no size)
 x = ntm_mpc.device_tensor(ntm_mpc.scenarios_x0(0, B))
 rho, uo = ctl.initial_state(x, cfg)
 ws = ctl.new_active_ws(B, cfg)

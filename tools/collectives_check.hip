@@ -1,5 +1,5 @@
 // Stand-alone check of the predicate collectives (gany / gall) and the
-// payload-free two-argument gargmin of csrc/ntm_device.h against the DPP forms
+// payload-free two-argument gargmin of csrc/ntm_collectives.h against the DPP forms
 // they replace: gmaxi of a 0/1 flag, and the four-argument gargmin carrying two
 // dummy payloads.  One wave, P = 16, 32 and 64; at P < 64 every group of the wave
 // gets its own rotation of the pattern, and one round runs with the even groups
@@ -22,7 +22,8 @@
 #include <limits>
 #include <vector>
 
-#include "../mpc-ntm-control_amd/csrc/ntm_device.h"
+#include "../mpc-ntm-control_amd/csrc/ntm_collectives.h"
+#include "check_common.h"
 
 struct Rec {
     int any_new, any_old, all_new, all_old;
@@ -97,14 +98,12 @@ __global__ void k_check(Rec* out) {
     }
 }
 
-static bool same_bits(double a, double b) { return std::memcmp(&a, &b, sizeof a) == 0; }
-
 template <int P>
 static int run(Rec* d_out, std::vector<Rec>& h) {
     const int nc = n_cases(P), rounds = P < 64 ? 2 : 1;
     const size_t n = (size_t)rounds * nc * 64;
     Rec fill;
-    std::memset(&fill, 0xEE, sizeof fill);
+    std::memset(&fill, kPoisonByte, sizeof fill);
     h.assign(n, fill);
     if (hipMemcpy(d_out, h.data(), n * sizeof(Rec), hipMemcpyHostToDevice) != hipSuccess) return 1000000;
     hipLaunchKernelGGL(k_check<P>, dim3(1), dim3(64), 0, 0, d_out);

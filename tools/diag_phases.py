@@ -13,7 +13,7 @@ N = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 cfg = Config(N=N, mode=int(sys.argv[3]) if len(sys.argv) > 3 else 2)
 ctl = NtmMpc(config=cfg)
 lib = ntm_mpc.load()
-buf = (C.c_ulonglong * 104)()
+buf = (C.c_ulonglong * 104)()   # NTM_NSTAMPS of csrc/ntm_diag.h (the library exports no size)
 x = ntm_mpc.device_tensor(ntm_mpc.scenarios_x0(0, B))
 rho, uo = ctl.initial_state(x, cfg)
 ws = ctl.new_active_ws(B, cfg)

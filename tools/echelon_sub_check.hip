@@ -1,4 +1,4 @@
-// Stand-alone check of the lane-masked triangular substitutions of csrc/ntm_device.h
+// Stand-alone check of the lane-masked triangular substitutions of csrc/ntm_lanes.h
 // (fsub_lanes / bsub_lanes, the echelon re-solve of the slim far N = 20 kernels)
 // against the loop form they replace, bit for bit.  One 64-lane block per case.
 //
@@ -33,7 +33,9 @@
 #include <vector>
 
 #define NTM_CH 5                               // the far N = 20 unit's chunk (csrc/ntm_n20.hip)
-#include "../mpc-ntm-control_amd/csrc/ntm_device.h"
+#include "../mpc-ntm-control_amd/csrc/ntm_lanes.h"
+#include "../mpc-ntm-control_amd/csrc/ntm_ws.h"
+#include "check_common.h"
 
 using W20 = ntm::WS<20, false, true>;
 constexpr int kN = 20, kTri = kN * (kN + 1) / 2;
@@ -130,17 +132,8 @@ __global__ void k_cases(Case* cases) {
     for (int i = lane; i < kImg; i += 64) c.after[i] = lds[i];
 }
 
-static bool same_bits(double a, double b) { return std::memcmp(&a, &b, sizeof a) == 0; }
-static double poison() {
-    double d;
-    std::memcpy(&d, &kPoison, 8);
-    return d;
-}
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static uint64_t rnd_u() {
-    rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
-    return rng_state >> 11;
-}
+static double poison() { return from_bits(kPoison); }
+static uint64_t rnd_u() { return rng_step() >> 11; }
 static double rnd() {                                   // finite, both signs, 2^-2 .. 2^2
     const double u = (double)rnd_u() / 9007199254740992.0;
     const int e = (int)(rnd_u() % 5u) - 2;
@@ -176,7 +169,7 @@ static void make_case(Case& c, int n, int nc, unsigned long long entry, int kind
         c.h[l] = in ? (rnd_u() % 6u == 0 ? -0.0 : rnd()) : 0.0;
         c.z[l] = (in && nc >= 0 && l >= nc) ? (rnd_u() % 6u == 0 ? -0.0 : rnd()) : 0.0;   // -e_c: rows from the hole on
         c.g[l] = in ? (rnd_u() % 6u == 0 ? -0.0 : rnd()) : 0.0;
-        c.sent[l] = 0xEEEEEEEEu;
+        c.sent[l] = kPoison32;
     }
     if (n > 0 && kind != kFinite) {
         const double special = (kind == kInfH || kind == kInfE || kind == kInfD) ? __builtin_huge_val() : __builtin_nan("");
@@ -204,7 +197,7 @@ static void check_case(int ci, const Case& c) {
     while (bclean > 0 && ((c.entry >> (bclean - 1)) & 1ull)) --bclean;
     for (int l = 0; l < 64; ++l) {
         const bool on = (c.entry >> l) & 1ull;
-        if (on ? c.sent[l] != 0x5A010000u + l : c.sent[l] != 0xEEEEEEEEu)
+        if (on ? c.sent[l] != 0x5A010000u + l : c.sent[l] != kPoison32)
             fail(on ? "EXEC not restored (sentinel missing)" : "an off lane ran", ci, c, l, 0, 0);
         if (!on || l >= n) {
             if (!same_bits(c.mx[l], h_sentinel(l, 0))) fail("x of a lane that is off or >= n written", ci, c, l, 0, c.mx[l]);

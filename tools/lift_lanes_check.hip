@@ -1,4 +1,4 @@
-// Stand-alone check of the lane-masked lift recursion of csrc/ntm_device.h
+// Stand-alone check of the lane-masked lift recursion of csrc/ntm_lanes.h and ntm_lift.h
 // (lift_chunk_lanes / lift_chunk_at under lift_phase's slim far N = 20 branch)
 // against the select form it replaces, bit for bit.  One 64-lane block.
 //
@@ -41,21 +41,21 @@
 #include <vector>
 
 #define NTM_CH 5                               // the far N = 20 unit's chunk (csrc/ntm_n20.hip): lift_phase takes it from here
-#include "../mpc-ntm-control_amd/csrc/ntm_device.h"
+#include "../mpc-ntm-control_amd/csrc/ntm_lift.h"
+#include "check_common.h"
 
 using W20 = ntm::WS<20, false, true>;
 constexpr int kN = 20, kGam = kN * (kN + 1);
 constexpr int kWs = 640;                       // rho 60, a11 20, a21 20, scratch 40, e 40, Gamma 420, guard 40
 constexpr int kJunk = 40 * (63 - kN);          // chunk level: a 20-stage record for each lane above N
 constexpr int kWs2 = kWs + kJunk;
-constexpr uint64_t kPoison = 0xEEEEEEEEEEEEEEEEull;
 static_assert(ntm::lift_lanes_ok<64, 5, W20>(), "the slim far N = 20 workspace must take the masked lift");
 static_assert(!ntm::lift_lanes_ok<64, 4, W20>() && !ntm::lift_lanes_ok<32, 5, W20>() &&
                   !ntm::lift_lanes_ok<64, 5, ntm::WS<20, false, false>>() &&
                   !ntm::lift_lanes_ok<64, 5, ntm::WS<50, false, true>>() && !ntm::lift_lanes_ok<64, 5, ntm::WS<0>>(),
               "no other kernel may reach the masked lift");
 
-__device__ __forceinline__ double poison() { return __builtin_bit_cast(double, kPoison); }
+__device__ __forceinline__ double poison() { return __builtin_bit_cast(double, kPoison64); }
 __device__ __forceinline__ W20 ws_at(double* base) {
     W20 w;
     w.N_rt = kN;
@@ -169,18 +169,10 @@ __global__ void k_chunks(ChunkIo* io, double a22, unsigned long long entry, doub
     for (int i = lane; i < 2 * kWs2; i += 64) out[i] = lds[i];
 }
 
-static bool same_bits(double a, double b) { return std::memcmp(&a, &b, sizeof a) == 0; }
-static bool is_poison(double a) {
-    uint64_t u;
-    std::memcpy(&u, &a, 8);
-    return u == kPoison;
-}
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
+static bool is_poison(double a) { return bits_of(a) == kPoison64; }
 static double rnd() {                                   // finite, both signs, 2^-2 .. 2^2
-    rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
-    const double u = (double)(rng_state >> 11) / 9007199254740992.0;
-    rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
-    const int e = (int)((rng_state >> 33) % 5u) - 2;
+    const double u = (double)(rng_step() >> 11) / 9007199254740992.0;
+    const int e = (int)((rng_step() >> 33) % 5u) - 2;
     return (2.0 * u - 1.0) * std::ldexp(1.0, e);
 }
 
@@ -200,7 +192,7 @@ static bool run_lift(const ntm::Prob& pb, const std::vector<double>& rho, double
     unsigned sent[64];
     ws.assign(2 * kWs, 0.0);
     if (hipMemcpy(d_rho, rho.data(), 3 * kN * 8, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(d_sent, 0xEE, sizeof sent) != hipSuccess) return false;
+        hipMemset(d_sent, kPoisonByte, sizeof sent) != hipSuccess) return false;
     hipLaunchKernelGGL(k_lift, dim3(1), dim3(64), 0, 0, pb, d_rho, x0, x1, d_out, d_sent);
     if (hipDeviceSynchronize() != hipSuccess ||
         hipMemcpy(ws.data(), d_out, 2 * kWs * 8, hipMemcpyDeviceToHost) != hipSuccess ||
@@ -276,7 +268,7 @@ static void chunks_case(int c, unsigned long long entry, bool nonfinite, ChunkIo
         io.a11[3 + c % 5] = -__builtin_huge_val();
         io.a21[12 + c % 5] = __builtin_nan("");
     }
-    std::memset(io.sent, 0xEE, sizeof io.sent);
+    std::memset(io.sent, kPoisonByte, sizeof io.sent);
     const double a22 = 0.9375 + rnd() / 64;
     if (hipMemcpy(d_io, &io, sizeof io, hipMemcpyHostToDevice) != hipSuccess) { ++bad; return; }
     hipLaunchKernelGGL(k_chunks, dim3(1), dim3(64), 0, 0, d_io, a22, entry, d_out2);
@@ -294,7 +286,7 @@ static void chunks_case(int c, unsigned long long entry, bool nonfinite, ChunkIo
     }
     for (int l = 0; l < 64; ++l) {
         const bool on = (entry >> l) & 1ull;
-        if (on ? o.sent[l] != 0x5A000000u + l : o.sent[l] != 0xEEEEEEEEu)
+        if (on ? o.sent[l] != 0x5A000000u + l : o.sent[l] != kPoison32)
             fail(on ? "chunks: EXEC not restored (sentinel missing)" : "chunks: an off lane ran", c, l, 0, 0);
         if (!same_bits(o.m0[l], o.s0[l]) || !same_bits(o.m1[l], o.s1[l])) fail("chunks: g behind the stages", c, l, o.s0[l], o.m0[l]);
         if ((!on || l > kN) && (!same_bits(o.m0[l], io.g0[l]) || !same_bits(o.m1[l], io.g1[l])))

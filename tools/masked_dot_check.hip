@@ -1,6 +1,6 @@
-// Stand-alone check of the lane-masked accumulation helpers of csrc/ntm_device.h
+// Stand-alone check of the lane-masked accumulation helpers of csrc/ntm_lanes.h
 // (fmac5_lanes_from, fmac5x2_lanes_from and the N = 20 far kernel's
-// gamma_row_dot / gamma_row_dot2 built on them; fadd5_lanes_upto and
+// gamma_row_dot / gamma_row_dot2 of csrc/ntm_dots.h built on them; fadd5_lanes_upto and
 // fadd5x2_class_lanes_upto of the column passes) against the select form they
 // replace, bit for bit.  One 64-lane block.
 //
@@ -43,7 +43,9 @@
 #include <cstring>
 #include <vector>
 
-#include "../mpc-ntm-control_amd/csrc/ntm_device.h"
+#include "../mpc-ntm-control_amd/csrc/ntm_dots.h"
+#include "../mpc-ntm-control_amd/csrc/ntm_ws.h"
+#include "check_common.h"
 
 using W20 = ntm::WS<20, false, true>;
 constexpr int kN = 20, kGam = kN * (kN + 1), kLds = 1024;
@@ -190,13 +192,9 @@ __global__ void k_cols(const TermIn* in, unsigned long long entry, ColOut* out) 
     out->acfm[lane] = cfm;
 }
 
-static bool same_bits(double a, double b) { return std::memcmp(&a, &b, sizeof a) == 0; }
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
 static double rnd() {                                   // finite, both signs, a few decades
-    rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
-    const double u = (double)(rng_state >> 11) / 9007199254740992.0;
-    rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
-    const int e = (int)((rng_state >> 33) % 9u) - 4;
+    const double u = (double)(rng_step() >> 11) / 9007199254740992.0;
+    const int e = (int)((rng_step() >> 33) % 9u) - 4;
     return (2.0 * u - 1.0) * std::ldexp(1.0, 3 * e);
 }
 
@@ -211,7 +209,7 @@ static bool fetch(RowOut& h) {
     if (hipDeviceSynchronize() != hipSuccess) return false;
     return hipMemcpy(&h, d_out, sizeof h, hipMemcpyDeviceToHost) == hipSuccess;
 }
-static bool poison() { return hipMemset(d_out, 0xEE, sizeof(RowOut)) == hipSuccess; }
+static bool poison() { return hipMemset(d_out, kPoisonByte, sizeof(RowOut)) == hipSuccess; }
 
 // row level; nonfinite_j < 0: finite data.  Returns the count of lanes outside the
 // term's rows on which the two forms differ (non-finite data only)
@@ -236,7 +234,7 @@ static int rows_case(int c, unsigned long long entry, int nonfinite_j, double sp
     for (int lane = 0; lane < 64; ++lane) {
         const bool on = (entry >> lane) & 1ull;
         if (!on) {                                      // nothing written, the sentinels included
-            if (h.sent[lane] != 0xEEEEEEEEu || h.sent2[lane] != 0xEEEEEEEEu) fail("rows: an off lane wrote", c, lane, 0, 0);
+            if (h.sent[lane] != kPoison32 || h.sent2[lane] != kPoison32) fail("rows: an off lane wrote", c, lane, 0, 0);
             continue;
         }
         if (h.sent[lane] != 0xA5000000u + lane || h.sent2[lane] != 0x5A000000u + lane)
@@ -340,11 +338,6 @@ static int terms_case(int c, Kind kind, TermIn* d_in) {
     if (kind != kNonFinite && flagged != 0) fail("terms: a lane flagged on finite data", c, 0, 0, 0);
     return signs;
 }
-static bool poisoned(const void* p, size_t n) {
-    for (size_t i = 0; i < n; ++i)
-        if (static_cast<const unsigned char*>(p)[i] != 0xEE) return false;
-    return true;
-}
 template <int I0>
 static void cols_case(int c, unsigned long long entry, bool nonfinite, TermIn* d_in, ColOut* d_col) {
     static TermIn in;
@@ -363,7 +356,7 @@ static void cols_case(int c, unsigned long long entry, bool nonfinite, TermIn* d
         }
     }
     if (hipMemcpy(d_in, &in, sizeof in, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(d_col, 0xEE, sizeof(ColOut)) != hipSuccess) { ++bad; return; }
+        hipMemset(d_col, kPoisonByte, sizeof(ColOut)) != hipSuccess) { ++bad; return; }
     hipLaunchKernelGGL(k_cols<I0>, dim3(1), dim3(64), 0, 0, d_in, entry, d_col);
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&h, d_col, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) {
         std::printf("cols case %d: the kernel failed\n", c);

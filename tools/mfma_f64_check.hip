@@ -1,5 +1,5 @@
 // Unit check of the V_MFMA_F64_16X16X4F64 lane maps gram_mfma relies on
-// (csrc/ntm_device.h): lane l supplies A(l & 15, l >> 4) and B(l >> 4, l & 15);
+// (csrc/ntm_gram.h): lane l supplies A(l & 15, l >> 4) and B(l >> 4, l & 15);
 // D(row (l >> 4) + 4 i, col l & 15) comes back in element i.  Exact integer data,
 // so the product must match bit for bit.   hipcc --offload-arch=gfx950 -o /tmp/mc tools/mfma_f64_check.hip
 #include <hip/hip_runtime.h>
