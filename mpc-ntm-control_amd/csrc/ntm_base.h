@@ -46,7 +46,10 @@ constexpr int kCdpExtra = 8;
 #ifndef NTM_COLL3
 #define NTM_COLL3 1        // k = 2 sets with one collision (three holes) on the null-space path (round 6)
 #endif
-constexpr int kBoxRepairs = 16;   // box-only QPs: single-row exchanges before GI (qp_phase)   // also at N = 50: 16 / 32 were no faster in mode 2, 6% / 10% slower in mode 3
+#ifndef NTM_N20_NO_RATE
+#define NTM_N20_NO_RATE 0  // 1: the slim N = 20 far kernels of this unit are compiled without rate rows
+#endif                     // (rate_rows in ntm_ws.h; on in ntm_n20.hip and the diag20 build)
+constexpr int kBoxRepairs = 16;  // box-only QPs: single-row exchanges before GI (qp_phase)   // also at N = 50: 16 / 32 were no faster in mode 2, 6% / 10% slower in mode 3
 // A constant row (Lin_i = 0: the x_0 rows of getWLc, state rows Gamma doesn't
 // reach) is violated when b_i < -kConstTol (D22, oracle CONST_ROW_TOL): the same
 // absolute 1e-9 the KKT certificate allows on a unit-scale row.  An exact test

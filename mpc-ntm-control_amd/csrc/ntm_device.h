@@ -103,8 +103,12 @@ struct StructRows {
     // 4 = rate up (U_j - U_{j-1} <= du), 5 = rate down (U_{j-1} - U_j <= du);
     // j = variable (u and rate rows) or state row r (state rows); -1 for x_0 rows.
     // Rate rows follow the 6N+4 getWLc rows: id = 6N+4 + 2(j-1) + {0 up, 1 down}.
+    // kRate = false (callers that know their kernel: rate_rows<W>() in ntm_ws.h): the
+    // launch has no rate rows whatever `mode` says, so no kind >= 4 comes out, and the
+    // callers' rate arms, written `rate_rows<W>() && ...`, fold away with every read of du
+    template <bool kRate = true>
     __device__ __forceinline__ void decode(int id, int N, int& kind, int& j) const {
-        if (mode == NTM_MODE_FULL_DU && id >= 6 * N + 4) {
+        if (kRate && mode == NTM_MODE_FULL_DU && id >= 6 * N + 4) {
             const int t = id - (6 * N + 4);
             kind = 4 + (t & 1);
             j = (t >> 1) + 1;
@@ -134,9 +138,9 @@ struct StructRows {
     template <class W>
     __device__ __forceinline__ double lin(const W& w, int id, int col) const {          // Lin[id][col]
         int kind, j;
-        decode(id, w.n(), kind, j);
+        decode<rate_rows<W>()>(id, w.n(), kind, j);
         if (kind < 2) return (col == j) ? (kind == 0 ? -1.0 : 1.0) : 0.0;
-        if (kind >= 4) {
+        if (rate_rows<W>() && kind >= 4) {
             const double sg = kind == 4 ? 1.0 : -1.0;
             return col == j ? sg : (col == j - 1 ? -sg : 0.0);
         }
@@ -147,18 +151,18 @@ struct StructRows {
     template <class W>
     __device__ __forceinline__ double bval(const W& w, int id) const {                  // b[id]
         int kind, j;
-        decode(id, w.n(), kind, j);
+        decode<rate_rows<W>()>(id, w.n(), kind, j);
         if (kind == 0) return -umin;
         if (kind == 1) return umax;
-        if (kind >= 4) return du;
+        if (rate_rows<W>() && kind >= 4) return du;
         int c = j & 1;
         return kind == 2 ? (-xmin(c) + w.e()[j]) : (xmax(c) - w.e()[j]);
     }
     template <class W>
     __device__ __forceinline__ double rnorm(const W& w, int id) const {
         int kind, j;
-        decode(id, w.n(), kind, j);
-        if (kind >= 4) return 1.0 / w.idun()[j];
+        decode<rate_rows<W>()>(id, w.n(), kind, j);
+        if (rate_rows<W>() && kind >= 4) return 1.0 / w.idun()[j];
         return kind < 2 ? w.D()[j] : 1.0 / w.irn()[j];
     }
 
@@ -244,7 +248,7 @@ struct StructRows {
             consider(Vl - lo, idl, lo, bound_tol<W>());
             consider(hi - Vl, idh, -hi, bound_tol<W>());
         }
-        if (has_rate() && l >= 1 && l < N) {                 // rate rows on lane j
+        if (rate_rows<W>() && has_rate() && l >= 1 && l < N) {   // rate rows on lane j
             const double ir = w.idun()[l];
             const double dU = w.U()[l] - w.U()[l - 1];
             const int id0 = 6 * N + 4 + 2 * (l - 1);
@@ -1079,6 +1083,10 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
                                int* ns_out, int* fail_kind = nullptr, int* fail_pos = nullptr,
                                double* v_out = nullptr, double* mult_out = nullptr, int dir_p = -1) {
     const int N = w.n(), LD = w.ldj(), LDJ = w.ldj();
+    // false: no rate rows in this kernel, so no general-row code r >= 2N and no kind >= 4.
+    // A constant in front of the plain tests, not a method of rows: a call from the
+    // lambdas below changes their captures, and with them the code of every unit
+    constexpr bool kRate = rate_rows<W>();
     const OmQ<qi_on<W>()> om(pb.Q);
     const bool dir = dir_p >= 0;
     const double Vprev = (l < N) ? w.V()[l] : 0.0;
@@ -1091,7 +1099,7 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
     if (l < q) {
         id = w.act()[l];
         int kind, j;
-        rows.decode(id, N, kind, j);
+        rows.template decode<kRate>(id, N, kind, j);
         if (kind < 2) {                                   // u bound: Lin = -+e_j, b = -umin / umax
             fixj = j;
             // lv = -+1: b / lv is -+b exactly, and -((lv D_j) / D_j) is -lv exactly (D_j
@@ -1099,7 +1107,7 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
             const double bv = rows.bval(w, id);
             ufix = kind == 0 ? -bv : bv;
             nfix = kind == 0 ? 1.0 : -1.0;
-        } else if (kind >= 4) {                           // rate row: Lin = sg (e_j - e_{j-1})
+        } else if (kRate && kind >= 4) {                  // rate row: Lin = sg (e_j - e_{j-1})
             isgen = 1;
             srow = 2 * N + j;                             // general-row code >= 2N: rate row j
             ssign = (kind == 4) ? 1.0 : -1.0;
@@ -1234,7 +1242,7 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
         if (l < nS) {
             const int r = w.srw()[l];
             int lj = -1;
-            if (r >= 2 * N) {                                  // rate row of input i: e_i - e_{i-1}
+            if (kRate && r >= 2 * N) {                         // rate row of input i: e_i - e_{i-1}
                 const int i = r - 2 * N;
                 lj = ((fm >> i) & 1ull) ? i : (((fm >> (i - 1)) & 1ull) ? i - 1 : -1);
             } else {                                           // state row r: from its last non-zero
@@ -1399,7 +1407,7 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
     // GI normal of general row s at variable j: n = -(Lin_j D_j)/rn, Lin = sg Gamma_r
     auto gen_n = [&](int s2, int j) -> double {
         const int r = w.srw()[s2];
-        if (r >= 2 * N) {                                 // rate row i = r - 2N
+        if (kRate && r >= 2 * N) {                        // rate row i = r - 2N
             const int i = r - 2 * N;
             const double sg = w.ssg()[s2];
             const double lv = (j == i) ? sg : (j == i - 1 ? -sg : 0.0);
@@ -1413,7 +1421,7 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
         if (s2 < nS) {
             const int r = w.srw()[s2];
             const double sg = w.ssg()[s2];
-            if (r >= 2 * N) {                             // rate row i: b = du, fixed part sg (U_i - U_{i-1})
+            if (kRate && r >= 2 * N) {                    // rate row i: b = du, fixed part sg (U_i - U_{i-1})
                 const int i = r - 2 * N;
                 const double ir = w.idun()[i];
                 const double ui = w.fx()[i] ? w.Uf()[i] : 0.0;
@@ -2072,7 +2080,7 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
             if (l < nS) {                                  // primal residual of general row l
                 const int r = w.srw()[l];
                 const double sg = w.ssg()[l];
-                if (r >= 2 * N) {
+                if (kRate && r >= 2 * N) {
                     const int i = r - 2 * N;
                     r2 = w.idun()[i] * (rows.du - sg * (w.U()[i] - w.U()[i - 1]));
                 } else {

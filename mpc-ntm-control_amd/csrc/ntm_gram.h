@@ -16,6 +16,13 @@
 
 namespace ntm {
 
+// the launch has input-rate rows (never, in a kernel compiled without them: rate_rows)
+template <class W>
+__device__ __forceinline__ bool rate_mode(const Prob& pb) {
+    if constexpr (rate_rows<W>()) return pb.mode == NTM_MODE_FULL_DU;
+    else return false;
+}
+
 // ---------------------------------------------------------------------------
 // Gram of Gamma columns on the matrix cores (long horizons): for the columns
 // j_a = col_of(a), a < nc, S(a, c) = X_a' (I (x) Q) X_c with X_a = Gamma(:, j_a),
@@ -286,7 +293,7 @@ __device__ __forceinline__ int diag_scale_phase(const Prob& pb, const W& w, int 
         }
         NTM_WSYNC();
         NTM_ACC(ST_SC_COL, tsc);
-        if (pb.mode == NTM_MODE_FULL_DU && l >= 1 && l < N) {
+        if (rate_mode<W>(pb) && l >= 1 && l < N) {
             const double a = w.D()[l], b = w.D()[l - 1];
             w.idun()[l] = 1.0 / sqrt(a * a + b * b);
         }
@@ -404,7 +411,7 @@ __device__ __forceinline__ int diag_scale_phase(const Prob& pb, const W& w, int 
     }
     NTM_WSYNC();
     NTM_ACC(ST_SC_COL, tsc);
-    if (pb.mode == NTM_MODE_FULL_DU && l >= 1 && l < N) {      // rate-row norms |D (e_l - e_{l-1})|
+    if (rate_mode<W>(pb) && l >= 1 && l < N) {                  // rate-row norms |D (e_l - e_{l-1})|
         const double a = w.D()[l], b = w.D()[l - 1];
         w.idun()[l] = 1.0 / sqrt(a * a + b * b);
     }

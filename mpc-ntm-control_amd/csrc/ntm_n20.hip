@@ -23,6 +23,20 @@
 #pragma clang diagnostic ignored "-Wpass-failed"
 #undef NTM_CH
 #define NTM_CH NTM_N20_CH
+// Round 13: mode 3 at N = 20 runs on the runtime-N kernels (host dispatch; the launchers
+// below refuse it), so the three kernels of this unit are compiled without input-rate
+// rows (rate_rows in ntm_ws.h).  `mode` is a launch value, so the compiler had kept every
+// rate arm and restored the spilled eight-dword kernel-argument tuple that holds `du`
+// wherever one stood: in the benchmark's kernel 9,446 -> 8,809 static VALU instructions,
+// v_readlane_b32 from the SGPR-spill VGPRs 536 -> 432 (the r / eps / du tuple 27 -> 18
+// restore sites), 47 -> 40 spilled VGPRs, scratch 192 -> 164 B per lane, code 132.2 ->
+// 123.6 KB (tools/spill_slots.py, profiles/r13_ab/resources.txt).  Config 3, three
+// alternating runs each: 5.420-5.434 -> 5.291-5.295 ms per step-batch, outputs byte-equal
+// (profiles/r13_ab/).  Kept.  Not built: detaching r[], xmin[], xmax[] from their tuples
+// or reading them by parity from LDS.
+#ifndef NTM_N20_NO_RATE
+#define NTM_N20_NO_RATE 1
+#endif
 #include "ntm_step.h"
 
 // the far layout is what the host side attaches a far block for (ws_far(20)); the
@@ -30,4 +44,6 @@
 #if !NTM_FAR_N20
 #error "ntm_n20.hip is the far-workspace N = 20 build: NTM_FAR_N20=0 applies to single-TU builds only"
 #endif
+static_assert(!ntm::rate_rows<ntm::WS<20, false, ntm::ws_far(20)>>() && !ntm::rate_rows<ntm::WS<20, true, ntm::ws_far(20)>>(),
+              "the kernels of this unit are built without rate rows; its launchers refuse mode 3 (ntm_mode_built)");
 NTM_DEFINE_LAYOUT_LAUNCHERS(n20, 20, ntm::ws_far(20))

@@ -304,10 +304,17 @@ hipError_t ntm_lds_opt_in(K kern, size_t lds) {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)lds);
 }
+// a build without rate rows (rate_rows in ntm_ws.h) must never see mode 3: the host's
+// dispatch sends it to the runtime-N kernels, and this keeps that explicit
+template <int NN, bool FAR>
+bool ntm_mode_built(const ntm::Prob& pb) {
+    return ntm::rate_rows<ntm::WS<NN, false, FAR>>() || pb.mode != NTM_MODE_FULL_DU;
+}
 template <int NN, bool FAR>
 hipError_t ntm_launch_step_v(const ntm::Prob& pb, int64_t B, const double* x_k, double* rho, double* U_old, double* U,
                              double* x_pred, double* x_next, int32_t* exitflag, int32_t* inner_iters,
                              int32_t* active_ws, size_t lds, hipStream_t st) {
+    if (!ntm_mode_built<NN, FAR>(pb)) return hipErrorInvalidValue;
     const bool gen = pb.g.phys_on || pb.g.dist_on;     // the generator's build only when it is used
     if (static_lds<64, NN>()) lds = 0;                 // the workspace is the kernel's static LDS
     hipError_t e = gen ? ntm_lds_opt_in(k_mpc_step<64, NN, true, FAR>, lds)
@@ -326,6 +333,7 @@ template <int NN, bool FAR>
 hipError_t ntm_launch_run_v(const ntm::Prob& pb, int64_t B, int k_sim, const double* x0, double* xk, double* uk,
                             double* Uk, double* wpred, int32_t* exitflag, int32_t* inner_iters, size_t lds,
                             hipStream_t st) {
+    if (!ntm_mode_built<NN, FAR>(pb)) return hipErrorInvalidValue;
     if (static_lds<64, NN>()) lds = 0;                 // the workspace is the kernel's static LDS
     hipError_t e = ntm_lds_opt_in(k_mpc_run<64, NN, FAR>, lds);
     if (e != hipSuccess) return e;

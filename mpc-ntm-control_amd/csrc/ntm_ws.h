@@ -243,6 +243,16 @@ struct WS {
     __device__ __forceinline__ unsigned char* aflag() const { return fx() + n(); }
 };
 
+// Input-rate rows (NTM_MODE_FULL_DU) in this kernel's code.  The host never launches
+// mode 3 on the slim N = 20 far kernels (it takes the runtime-N kernels, and the layout
+// has no active-row flags for rate rows: slim_ab), but `mode` is a launch value, so the
+// compiler kept every rate arm and restored du wherever one stood.  A unit that sets
+// NTM_N20_NO_RATE compiles those kernels without them (StructRows::decode<false>, the
+// `rate_rows<W>() &&` tests of the row provider and polish_compact, rate_mode in ntm_gram.h);
+// the launchers of ntm_step.h refuse mode 3 for such a build.
+template <class W>
+__host__ __device__ constexpr bool rate_rows() { return !(NTM_N20_NO_RATE && W::kAB != 0); }
+
 __host__ __device__ constexpr int ldj_of(int N) { return N | 1; }
 // the J/R block of a far layout, in HBM per scenario (no T: WS::useT)
 __host__ __device__ constexpr int far_doubles(int N) {

@@ -8,6 +8,7 @@ set -e
 cd "$(dirname "$0")/../mpc-ntm-control_amd"
 H="/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wall -Wno-unused-function --cuda-device-only -S"
 N20="-mllvm -amdgpu-use-amdgpu-trackers=1"
+N20DEFS="-DNTM_N20_NO_RATE=1"    # the Makefile's N20DEFS (diag20); ntm_n20.hip sets it itself
 DIAG="-DNTM_CH=5 -DNTM_CHUNK_UNROLL=2 -Wno-pass-failed -DNTM_STAMPS"
 ONE="csrc/ntm_kernels.hip -DNTM_SINGLE_TU"
 UNITS=${*:-ntm_kernels ntm_n20 ntm_n20near ntm_n20near1w ntm_n50 ntm_n50m3 diag diag20 poison ru_only20}
@@ -18,7 +19,7 @@ for n in $UNITS; do
     ntm_n20) F="$N20 csrc/$n.hip";;
     ntm_*) F="csrc/$n.hip";;
     diag) F="$DIAG $ONE";;
-    diag20) F="$DIAG $N20 $ONE";;
+    diag20) F="$DIAG $N20 $N20DEFS $ONE";;
     poison) F="-DNTM_POISON=1e300 $ONE";;
     ru_only20) F="-DNTM_RU_ONLY20 $ONE";;
     *) echo "unknown unit $n" >&2; exit 1;;
