@@ -33,7 +33,7 @@
 //                      scn_coef, scn_store
 //   ntm_lanes.h        every inline-assembly helper that runs under a narrowed EXEC, with the
 //                      rules they share: lane_masked_ok, fmac5*_lanes_from, fadd5*_lanes_upto,
-//                      lift_chunk_lanes, esub_lanes_ok, fsub_lanes, bsub_lanes
+//                      lift_chunk_lanes, esub_lanes_ok, fsub_lanes, bsub_lanes, rownorm5_lanes_from
 //                      (lift_lanes_ok names fuse_colsum and stays with it in ntm_lift.h)
 //   ntm_dots.h         qdot_rows, dot_batched, dot_range, sub_dot, axpy_sub, gamma_row_dot,
 //                      gamma_row_dot2, dot_rows2

@@ -209,6 +209,19 @@ __device__ __forceinline__ void scale_col_chunk_lanes(const OM& qw, const double
     }
     fadd5x2_class_lanes_upto<I0>(s, fs, nf, t, tf, ga, gb);
 }
+// Lane-masked row pass of the scaling pass (esub_lanes_ok: state row r on lane r < 2N): s = the
+// sum over j <= r / 2 of (Gamma_rj D_j)^2 in ascending j, last = the largest such j with
+// Gamma_rj != 0 (-1: none), cnt = how many there are, added to what s / last / cnt hold on entry
+template <class W>
+__device__ __forceinline__ void row_norm_lanes(const W& w, int r, double& s, int& last, int& cnt) {
+    static_assert(W::kNN == 20, "the packed offsets j (2N - 1 - j) of rownorm5_lanes_from are N = 20's");
+    const unsigned at = (unsigned)(uintptr_t)(__attribute__((address_space(3))) double*)(w.Gt() + r);
+    const unsigned ad = (unsigned)(uintptr_t)(__attribute__((address_space(3))) double*)w.D();
+    rownorm5_lanes_from<0>(s, last, cnt, at, ad);
+    rownorm5_lanes_from<5>(s, last, cnt, at, ad);
+    rownorm5_lanes_from<10>(s, last, cnt, at, ad);
+    rownorm5_lanes_from<15>(s, last, cnt, at, ad);
+}
 template <int P, class W>
 __device__ __forceinline__ int diag_scale_phase(const Prob& pb, const W& w, int l, bool with_state_rows,
                                                 double x0 = 0.0, double x1 = 0.0, const ColSums* cs = nullptr) {
@@ -421,6 +434,9 @@ __device__ __forceinline__ int diag_scale_phase(const Prob& pb, const W& w, int 
             const int jmax = r >> 1;
             int last = -1, cnt = 0;
             constexpr int CH = NTM_CH;
+            if constexpr (esub_lanes_ok<P, CH, W>()) {   // terms j > jmax masked by lane (r = l: one trip)
+                row_norm_lanes(w, r, s, last, cnt);
+            } else {
             NTM_CHUNK_PRAGMA
             for (int j0 = 0; j0 < N; j0 += CH) { // fixed trip count, j > jmax masked; batched loads
                 double g[CH], dd[CH];
@@ -438,6 +454,7 @@ __device__ __forceinline__ int diag_scale_phase(const Prob& pb, const W& w, int 
                     s += in ? v * v : 0.0;
                     if (in && g[u] != 0.0) { last = j0 + u; ++cnt; }
                 }
+            }
             }
             bad |= !isfinite(s) || !isfinite(w.e()[r]);
             const double ir = (s > 0.0 && s < kInf) ? rsqrt_nr(s) : 0.0;

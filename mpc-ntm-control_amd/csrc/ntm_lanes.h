@@ -1,8 +1,9 @@
-// ntm_lanes.h — the inline-assembly helpers that run under a narrowed EXEC.  Three
+// ntm_lanes.h — the inline-assembly helpers that run under a narrowed EXEC.  Four
 // families, all for the far N = 20 kernels (one scenario per wave, a row, a column
 // or a substitution step's unknown on its own lane): the lane-masked accumulation
-// of the triangular Gamma passes, the lane-masked lift recursion, and the
-// triangular substitutions of the echelon re-solve.  In each the lanes an
+// of the triangular Gamma passes, the lane-masked lift recursion, the triangular
+// substitutions of the echelon re-solve, and the row norms of the scaling pass
+// with their non-zero tracking.  In each the lanes an
 // instruction belongs to are known at compile time, so the instruction runs with
 // EXEC narrowed to them where the plain form computes on every lane and selects.
 //
@@ -475,5 +476,76 @@ __device__ __forceinline__ void bsub_lanes(int n, double& acc, double& mu, doubl
     bsub_from<5>(n, acc, mu, sq, col, c);
     bsub_from<0>(n, acc, mu, sq, col, c);
 }
+
+// ---------------------------------------------------------------------------
+// Lane-masked row norms of the scaling pass (the slim far N = 20 kernels: state
+// row r on lane r < 2N, |Gamma_r D|^2 = sum_j (Gamma_rj D_j)^2 over j <= r / 2, and
+// with it the row's last non-zero column and the count of its non-zeros).  The
+// loop form runs all N terms on every lane: it zeroes the square of a term outside
+// the row with a select (a v_cmp and two v_cndmask), ANDs the row test into the
+// non-zero test, tracks last / cnt by selects (a v_mov, two v_cndmask and half a
+// v_add3 per term) and rebuilds the packed address per term (an s_mul, two s_add
+// and a v_lshl_add).  Here the terms are unrolled over the compile-time j in
+// chunks of five: gt(r, j) sits at Gt + r + j (2N - 1 - j), an immediate offset
+// from the lane's address of Gt[r], D_j at an immediate offset from D, and term j
+// runs with EXEC narrowed to the lanes 2j .. 2N - 1.  Per term: v_cmp_neq_f64 (the
+// non-zero test, VCC), the two v_mul_f64 and the v_add_f64 of the loop form as it
+// is compiled (g D_j with g as src0, the square, s + square; no contraction),
+// v_cndmask_b32 last <- j under VCC and v_addc_co_u32 cnt += VCC.
+//   Bit-equality with the loop form, whatever the data: the sum starts at +0.0 and
+// adds squares (each +0.0 or above, or a NaN) in ascending j, so it is never -0.0,
+// and a row's masked terms (j > r / 2) come after its own: s + (+0.0) leaves the
+// bits of any such s, a quiet NaN included, which is what a lane that is off
+// keeps.  last and cnt change only on a lane the term belongs to, under the same
+// test (v_cmp_neq is true for a NaN, false for -0.0, as `g != 0.0`).  Lanes off on
+// entry and lanes >= 2N are in no mask (rule 1) and keep s, last and cnt.
+//   One block per chunk.  Its ten loads are issued first, under the chunk's widest
+// mask (lanes >= 2 J0 below 2N: gt(r, j) of such a lane lies inside the packed
+// Gamma for any j), and term k waits for its own pair (LDS loads return in order:
+// lgkmcnt(8 - 2k)); loads and waits are one statement (rule 5).  The masks are
+// s_bfm_b64 (40 - 2j ones from bit 2j) ANDed with the saved EXEC.  VCC written by
+// v_cmp is read as a mask by v_cndmask and as a carry by v_addc: two wait states
+// (rule 4), which the two v_mul_f64 between them are, in the order the compiler
+// itself schedules this pair (v_cmp, two VALU, v_cndmask).  v_addc's carry-out
+// overwrites VCC, which the next term's v_cmp writes again; VCC is a clobber.  The
+// block ends by rule 3.
+//   Round 8 had masked only the add of this pass and kept the select-based tracking
+// and the per-term address arithmetic (5.762 -> 5.792 ms, not kept; above).  This
+// form, measured on the far N = 20 kernel at B = 1e5 (A/B on one box, three runs
+// each): 5.261-5.269 -> 5.182-5.197 ms per step-batch, outputs byte-equal
+// (DESIGN.md section 10, round 14).
+// ---------------------------------------------------------------------------
+#define NTM_RN_LD(k) \
+    "ds_read_b64 %[g" #k "], %[at] offset:%[o" #k "]\n\tds_read_b64 %[d" #k "], %[ad] offset:%[q" #k "]\n\t"
+#define NTM_RN_MASK(k) "s_bfm_b64 %[m], %[w" #k "], %[b" #k "]\n\ts_and_b64 exec, %[sv], %[m]\n\t"
+#define NTM_RN_TERM(k, cntk)                                                                          \
+    "s_waitcnt lgkmcnt(" #cntk ")\n\tv_cmp_neq_f64_e32 vcc, 0, %[g" #k "]\n\tv_mul_f64 %[v], %[g" #k "], %[d" #k "]\n\t"                \
+    "v_mul_f64 %[v], %[v], %[v]\n\tv_cndmask_b32_e64 %[last], %[last], %[j" #k "], vcc\n\t"          \
+    "v_addc_co_u32_e32 %[cnt], vcc, 0, %[cnt], vcc\n\tv_add_f64 %[s], %[s], %[v]\n\t"
+#define NTM_RN_N(k, J0)                                                                               \
+    [w##k] "n"(40 - 2 * ((J0) + k)), [b##k] "n"(2 * ((J0) + k)), [j##k] "n"((J0) + k),                \
+        [o##k] "n"(8 * ((J0) + k) * (39 - ((J0) + k))), [q##k] "n"(8 * ((J0) + k))
+// terms J0 .. J0 + 4 of row `lane`: at / ad the LDS byte addresses of Gt[lane] and of D[0]
+template <int J0>
+__device__ __forceinline__ void rownorm5_lanes_from(double& s, int& last, int& cnt, unsigned at, unsigned ad) {
+    static_assert(J0 >= 0 && J0 + 5 <= 20, "terms 0..19 of the N = 20 row pass");
+    unsigned long long sv, m;
+    double g0, g1, g2, g3, g4, d0, d1, d2, d3, d4, v;
+    asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_RN_MASK(0)
+                 NTM_RN_LD(0) NTM_RN_LD(1) NTM_RN_LD(2) NTM_RN_LD(3) NTM_RN_LD(4) NTM_RN_TERM(0, 8)
+                 NTM_RN_MASK(1) NTM_RN_TERM(1, 6) NTM_RN_MASK(2) NTM_RN_TERM(2, 4)
+                 NTM_RN_MASK(3) NTM_RN_TERM(3, 2) NTM_RN_MASK(4) NTM_RN_TERM(4, 0)
+                 "s_mov_b64 exec, %[sv]\n\ts_nop 0"
+                 : [s] "+v"(s), [last] "+v"(last), [cnt] "+v"(cnt), [v] "=&v"(v), [sv] "=&s"(sv), [m] "=&s"(m),
+                   [g0] "=&v"(g0), [g1] "=&v"(g1), [g2] "=&v"(g2), [g3] "=&v"(g3), [g4] "=&v"(g4),
+                   [d0] "=&v"(d0), [d1] "=&v"(d1), [d2] "=&v"(d2), [d3] "=&v"(d3), [d4] "=&v"(d4)
+                 : [at] "v"(at), [ad] "v"(ad), NTM_RN_N(0, J0), NTM_RN_N(1, J0), NTM_RN_N(2, J0), NTM_RN_N(3, J0),
+                   NTM_RN_N(4, J0)
+                 : "scc", "vcc", "memory");
+}
+#undef NTM_RN_LD
+#undef NTM_RN_MASK
+#undef NTM_RN_TERM
+#undef NTM_RN_N
 
 }  // namespace ntm
