@@ -228,7 +228,9 @@ int ntm_qp_device(ntm_ctx* ctx, int64_t B, int32_t N, int32_t m,
  * fp32 on fp32-rounded data -> U32[N] (widened), then that active set re-solved
  * exactly in fp64 with the KKT certificate -> U[N]; if it does not certify, the
  * fp64 solve takes over.  info: bit 0 the fp32 active set certified, bit 1 fp64
- * fallback, bit 2 the fp32 solve itself was not optimal.  iters32: fp32 GI
+ * fallback, bit 2 the fp32 solve itself was not optimal (U32 is then its last
+ * iterate; 0 where the data leave fp32 no first one: non-finite or G not PD
+ * after rounding, a violated constant row).  iters32: fp32 GI
  * iterations.  N <= 64, m <= 8N+4 rows within the 160 KiB LDS of one CU. */
 int ntm_qp_mixed_device(ntm_ctx* ctx, int64_t B, int32_t N, int32_t m,
                         const double* G, const double* F, const double* Lin,

@@ -102,6 +102,7 @@ __device__ int gi32_solve(GI32& g, const double* G64, const double* F64, const D
     *iters_out = 0;
     // --- fp32 data and Jacobi scaling U = D V (diag(D G D) = 1) ---
     if (l < N) {
+        g.U[l] = 0.0f;   // the answer of a stage that ends before its first iterate (the caller's U32)
         const float gll = (float)G64[s * (N * N) + l + l * N];
         g.D[l] = gll > 0.0f ? 1.0f / sqrtf(gll) : 1.0f;
     }
