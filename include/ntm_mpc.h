@@ -237,6 +237,71 @@ int ntm_qp_mixed_device(ntm_ctx* ctx, int64_t B, int32_t N, int32_t m,
                         const double* b, double* U, double* U32, int32_t* exitflag,
                         int32_t* info, int32_t* iters32, void* stream);
 
+/* ---- multipliers and the KKT audit ------------------------------------- */
+/* The multiplier lambda follows quadprog's lambda.ineqlin: the Lagrangian is
+ * 1/2 U'GU + F'U + lambda'(Lin U - b), lambda >= 0, one entry per row, zero on rows
+ * that are not active.  (The solver works in scaled units, V = U/D with
+ * D_j = 1/sqrt(G_jj), rows normalised by rn_i = |Lin_i o D|_2; its multipliers are
+ * mu_i = lambda_i rn_i and the export divides by rn_i.)
+ * Row order of an MPC step's QP (the oracle's constraints(), the ids of active_ws):
+ *   mode 1: rows 0..N-1 are -U_j <= -umin, rows N..2N-1 are U_j <= umax;
+ *   modes 2, 3: getWLc's 6N+4 rows: per stage i = 0..N-1 the block [-U_i <= -umin;
+ *     U_i <= umax; -x_i <= -xmin (2 rows); x_i <= xmax (2 rows)], then the terminal
+ *     [-x_N <= -xmin (2); x_N <= xmax (2)];
+ *   mode 3 then adds, for i = 1..N-1, row 6N+4 + 2(i-1) + {0, 1}:
+ *     U_i - U_{i-1} <= du_max and U_{i-1} - U_i <= du_max.
+ *
+ * ntm_qp_device with [x, fval, exitflag, output, lambda] of quadprog: arguments,
+ * validation, limits and the results U, exitflag, iters (bit for bit) are
+ * ntm_qp_device's.  lambda[m] per scenario (may be NULL when m == 0): for exit flag
+ * 1 the multipliers of the certified re-solve (Goldfarb-Idnani's own where the
+ * re-solve does not certify and its iterate is returned); every entry 0 for exit
+ * flags 0, -2 and -7.  fval (B, may be NULL) = 1/2 U'GU + F'U at the returned U
+ * (0 where U = 0). */
+int ntm_qp_dual_device(ntm_ctx* ctx, int64_t B, int32_t N, int32_t m,
+                       const double* G, const double* F, const double* Lin,
+                       const double* b, double* U, int32_t* exitflag,
+                       int32_t* iters, double* lambda, double* fval, void* stream);
+/* ntm_mpc_step_ws plus, per scenario, lambda[rows(mode)] (the multipliers of the
+ * step's last QP; 0 where that QP's exit flag is not 1; may be NULL in mode 0) and
+ * rho_qp[3N] (the scheduling rho that QP was built from: the step's rho output is
+ * already the post-rollout update).  Every horizon runs on the runtime-N kernels
+ * here, N = 10, 20 and 50 included, so the results agree with ntm_mpc_step_ws to
+ * the parity tolerances, not bit for bit. */
+int ntm_mpc_step_dual(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg,
+                      int64_t B, const double* x_k, double* rho, double* U_old,
+                      double* U, double* x_pred, double* x_next,
+                      int32_t* exitflag, int32_t* inner_iters, int32_t* active_ws,
+                      double* lambda, double* rho_qp);
+int ntm_mpc_step_dual_device(ntm_ctx* ctx, const ntm_physics* phys,
+                             const ntm_config* cfg, int64_t B, const double* x_k,
+                             double* rho, double* U_old, double* U, double* x_pred,
+                             double* x_next, int32_t* exitflag, int32_t* inner_iters,
+                             int32_t* active_ws, double* lambda, double* rho_qp,
+                             void* stream);
+/* The KKT audit: kkt[4] per scenario from (U, lambda) alone, by arithmetic that
+ * shares nothing with the solver but the lift.  With d = D as above, V = U/d,
+ * vmax = max(1, max|V|), rn_i as above (1 for a constant row, rn_i = 0),
+ * mu_i = lambda_i rn_i, mumax = max(1, max|mu|):
+ *   kkt[0] stationarity    max_j |(GU + F + Lin'lambda)_j d_j| / max(1, max_j |F_j d_j|)
+ *   kkt[1] primal          max(0, max_i v_i), v_i = (Lin_i U - b_i)/(rn_i vmax) on
+ *                          ordinary rows, v_i = -b_i on constant rows
+ *   kkt[2] dual            max(0, max_i -mu_i) / mumax
+ *   kkt[3] complementarity max_i |mu_i (Lin_i U - b_i)/rn_i| / (mumax vmax), ordinary rows
+ * These are the units of the solver's certificate (tolerance 1e-9).  m = 0: only
+ * kkt[0] is non-zero.  Non-finite input gives NaN in that scenario's kkt.
+ * ntm_qp_kkt_device takes the QP's data (ntm_qp_device's layout; lambda may be NULL
+ * when m == 0); ntm_mpc_kkt_device rebuilds the step's QP from x_k[2] and
+ * rho_qp[3N] (nominal plasma: a scenario generator's spread is not applied). */
+int ntm_qp_kkt_device(ntm_ctx* ctx, int64_t B, int32_t N, int32_t m,
+                      const double* G, const double* F, const double* Lin,
+                      const double* b, const double* U, const double* lambda,
+                      double* kkt, void* stream);
+int ntm_mpc_kkt_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg,
+                       int64_t B, const double* x_k, const double* rho_qp,
+                       const double* U, const double* lambda, double* kkt,
+                       void* stream);
+
 /* Synthetic scenarios, counter-based and shard-invariant:
  * x0 for global scenario ids first_id .. first_id+B-1 (host array, 2 per scenario). */
 void ntm_scenarios_x0(uint64_t seed, int64_t first_id, int64_t B, double* x0);

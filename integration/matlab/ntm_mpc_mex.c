@@ -12,7 +12,7 @@
  * ABI's scenario-major layout [s*E + e] in MATLAB's column-major storage, so
  * arrays pass through without copies):
  *
- *   [U, x_pred, x_next, exitflag, iters, rho, Uold, ws] = ...
+ *   [U, x_pred, x_next, exitflag, iters, rho, Uold, ws, lambda, rho_qp] = ...
  *       ntm_mpc_mex('step', x_k, rho, Uold, cfg[, ws])
  *         x_k  2-by-B        current state [w; omega]           (xk(:,k))
  *         rho  3N-by-B       Rho(:) per scenario                (:63-65,116)
@@ -20,7 +20,12 @@
  *         ws   2(N+1)-by-B   optional int32 warm-start workspace (start with
  *                            -1 everywhere; pass the returned one back next step)
  *       outputs: U N-by-B, x_pred 2(N+1)-by-B, x_next 2-by-B, exitflag and
- *       iters 1-by-B
+ *       iters 1-by-B.  Asked for more than eight outputs, the step also returns
+ *       lambda rows(mode)-by-B, the last QP's multipliers (quadprog's
+ *       lambda.ineqlin, the row order of include/ntm_mpc.h), and rho_qp 3N-by-B,
+ *       the scheduling rho that QP was built from (ntm_mpc_step_dual: the
+ *       runtime-horizon kernels, results to the parity tolerances); with eight
+ *       or fewer it is ntm_mpc_step_ws as before
  *   [rho, Uold] = ntm_mpc_mex('init', x0, cfg)                 (:63-65, :86)
  *   [xk, uk, Uk, wpred, exitflag, iters] = ntm_mpc_mex('run', x0, k_sim, cfg)
  *       outputs 2(k_sim+1)-by-B, k_sim-by-B, N k_sim-by-B, (N+1) k_sim-by-B,
@@ -137,11 +142,25 @@ static void do_step(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
         int32_t* wp = mxGetInt32s(ws);
         for (size_t i = 0; i < B * 2 * (N + 1); ++i) wp[i] = -1;
     }
-    check(ntm_mpc_step_ws(ctx(), &p, &c, (int64_t)B, x, mxGetDoubles(rho), mxGetDoubles(uold), mxGetDoubles(U),
-                          mxGetDoubles(xp), mxGetDoubles(xn), mxGetInt32s(fl), mxGetInt32s(it), mxGetInt32s(ws)),
-          "ntm_mpc_step_ws");
-    mxArray* outs[8] = {U, xp, xn, fl, it, rho, uold, ws};
-    for (int i = 0; i < 8; ++i) {
+    mxArray* lam = NULL;
+    mxArray* rq = NULL;
+    if (nlhs > 8) {
+        const size_t m = c.mode == NTM_MODE_NONE ? 0
+                         : c.mode == NTM_MODE_BOX ? 2 * N
+                         : c.mode == NTM_MODE_FULL_DU ? 8 * N + 2 : 6 * N + 4;
+        lam = mxCreateDoubleMatrix(m, B, mxREAL);
+        rq = mxCreateDoubleMatrix(3 * N, B, mxREAL);
+        check(ntm_mpc_step_dual(ctx(), &p, &c, (int64_t)B, x, mxGetDoubles(rho), mxGetDoubles(uold), mxGetDoubles(U),
+                                mxGetDoubles(xp), mxGetDoubles(xn), mxGetInt32s(fl), mxGetInt32s(it), mxGetInt32s(ws),
+                                m ? mxGetDoubles(lam) : NULL, mxGetDoubles(rq)),
+              "ntm_mpc_step_dual");
+    } else {
+        check(ntm_mpc_step_ws(ctx(), &p, &c, (int64_t)B, x, mxGetDoubles(rho), mxGetDoubles(uold), mxGetDoubles(U),
+                              mxGetDoubles(xp), mxGetDoubles(xn), mxGetInt32s(fl), mxGetInt32s(it), mxGetInt32s(ws)),
+              "ntm_mpc_step_ws");
+    }
+    mxArray* outs[10] = {U, xp, xn, fl, it, rho, uold, ws, lam, rq};
+    for (int i = 0; i < (lam ? 10 : 8); ++i) {
         if (i < (nlhs > 0 ? nlhs : 1)) plhs[i] = outs[i];
         else mxDestroyArray(outs[i]);
     }

@@ -802,10 +802,14 @@ __device__ __forceinline__ int gi_solve(const W& w, const Rows rows, bool has_ro
 //   holds; otherwise w.U() keeps GI's solution.  Pre: w.V() = GI solution.
 //   Writes w.U() (unscaled U).  G~ comes from Gamma (gram, structured rows) or
 //   from Gsave (a copy taken before the GI factorisation, dense rows).
+//   lam_out (optional, one entry per row; may alias the rows' norm array): the
+//   multipliers of a certified set, unscaled (mu_i / rn_i) and zero on the other
+//   rows, written only on success.
 // ---------------------------------------------------------------------------
 template <int P, class Rows, class W>
 __device__ __forceinline__ bool polish_phase(const Prob& pb, const W& w, const Rows* rows, int q, int l,
-                             const double* Gsave, bool g_in_R, bool verify_only, int* ns_out) {
+                             const double* Gsave, bool g_in_R, bool verify_only, int* ns_out,
+                             double* lam_out = nullptr) {
     const int N = w.n(), LD = w.ldj(), LDJ = w.ldj();
     const double Vgi = (l < N) ? w.V()[l] : 0.0;
     // --- classify active rows ---
@@ -1035,6 +1039,23 @@ __device__ __forceinline__ bool polish_phase(const Prob& pb, const W& w, const R
         // the smallest multiplier only feeds this comparison: a predicate per lane
         // (a NaN multiplier compares false here, as fmax dropped it from the minimum)
         ok = ok && !gany<P>(has && mval < -1e-9 * fmax(1.0, mabs));
+        if (lam_out && ok) {
+            // the certified set's multipliers in the caller's units (quadprog's
+            // lambda.ineqlin: mu / rn), by row id.  Every lane forms its entries
+            // before lam_out is written, so lam_out may be the row norms' own array
+            if (fixed) w.d()[l] = res / w.hv()[l];
+            NTM_WSYNC();
+            int i1 = -1, i2 = -1;
+            double v1 = 0.0, v2 = 0.0;
+            if (l < nS) { i1 = w.sidx()[l]; v1 = w.np()[l] / rows->rnorm(w, i1); }
+            if (l < q && !isgen) { i2 = id; v2 = w.d()[fixj] / rows->rnorm(w, id); }
+            NTM_WSYNC();
+            for (int i = l; i < rows->rows(); i += P) lam_out[i] = 0.0;
+            NTM_WSYNC();
+            if (i1 >= 0) lam_out[i1] = v1;
+            if (i2 >= 0) lam_out[i2] = v2;
+            NTM_WSYNC();
+        }
     }
     if (verify_only && !ok) {
         if (l < N) w.V()[l] = Vgi;
@@ -2630,9 +2651,11 @@ __device__ __forceinline__ int shifted_into_act(const Prob& pb, const W& w, cons
 // ---------------------------------------------------------------------------
 // qp_phase's Goldfarb-Idnani fallback (the full G~, GI warm-started from the
 // failed candidate, then its certified polish; ~2.5% of the QPs at N = 20).
-// Inlined like every other phase.
+// Inlined like every other phase.  DUAL (ntm_mpc_step_dual): the polish writes its
+// certified multipliers to w.uu() by active position, as the dual path does; where
+// it does not certify, GI's own stay there.
 // ---------------------------------------------------------------------------
-template <int P, class W>
+template <int P, class W, bool DUAL = false>
 __device__ __forceinline__ int gi_fallback(const Prob& pb, const W w, const StructRows rows, int nrows, int l, int nwarm,
                                            int it, int* qp_iters, int* q_out, int* ns_out, bool* yv_out) {
     NTM_T0(tq);
@@ -2656,7 +2679,16 @@ __device__ __forceinline__ int gi_fallback(const Prob& pb, const W w, const Stru
         }
         NTM_ACC(ST_GI, tq);
         if (flag == NTM_EXIT_OPTIMAL) {
-            const bool okp = polish_compact<P>(pb, w, rows, q, l, false, &ns);
+            bool okp;
+            if constexpr (DUAL) {
+                const double ugi = (l < q) ? w.uu()[l] : 0.0;
+                NTM_WSYNC();
+                okp = polish_compact<P>(pb, w, rows, q, l, false, &ns, nullptr, nullptr, nullptr, w.uu());
+                if (!okp && l < q) w.uu()[l] = ugi;
+                NTM_WSYNC();
+            } else {
+                okp = polish_compact<P>(pb, w, rows, q, l, false, &ns);
+            }
             NTM_TRACE("QP GI flag %d q %d polish %d\n", flag, q, (int)okp);
             yv = okp;
         }
@@ -2671,7 +2703,7 @@ __device__ __forceinline__ int gi_fallback(const Prob& pb, const W w, const Stru
 // ---------------------------------------------------------------------------
 // one inner iteration's QP: build -> scale -> GI -> polish -> w.U()
 // ---------------------------------------------------------------------------
-template <int P, class W>
+template <int P, class W, bool DUAL = false>
 __device__ __forceinline__ int qp_phase(const Prob& pb, const W& w, double x0, double x1, int l, int* qp_iters,
                         int* q_out, int* ns_out, int slot, int* n_try = nullptr, int* n_girun = nullptr,
                         int it = 0, bool* y_valid = nullptr) {
@@ -3012,7 +3044,7 @@ __device__ __forceinline__ int qp_phase(const Prob& pb, const W& w, double x0, d
             }
             if (!done) {
                 if (n_girun) ++*n_girun;
-                flag = gi_fallback<P, W>(pb, w, rows, nrows, l, nwarm, it, qp_iters, &q, &ns, &yv);
+                flag = gi_fallback<P, W, DUAL>(pb, w, rows, nrows, l, nwarm, it, qp_iters, &q, &ns, &yv);
             }
         }
     }

@@ -19,6 +19,7 @@
 #include <string>
 
 #include "ntm_device.h"
+#include "ntm_kkt.h"
 #include "ntm_mixed.h"
 #include "ntm_step.h"
 
@@ -219,6 +220,86 @@ __global__ __launch_bounds__(64) void k_qp(int64_t B, int N, int m, const double
     }
     NTM_WSYNC();
     if (l < N) U[s * N + l] = w.U()[l];
+    if (l == 0) {
+        exitflag[s] = flag;
+        if (iters) iters[s] = its;
+    }
+}
+
+// k_qp with the multipliers and the objective exported (ntm_qp_dual_device).  A
+// sibling and not a flag of k_qp, so that k_qp's own instantiations stay what they
+// are; the solve is k_qp's line for line (U, exitflag and iters agree bit for bit)
+// and so is the workspace: at N = 64, m = 8N + 4 it leaves no room for m more
+// doubles, so lambda is collected in the row norms' array once the solve no longer
+// reads it.  lambda by row id: the certified re-solve's multipliers (polish_phase
+// lam_out), or GI's own (w.uu() on w.act()) where the re-solve does not certify and
+// GI's iterate is returned; zero for every other exit flag.
+template <int P>
+__global__ __launch_bounds__(64) void k_qp_dual(int64_t B, int N, int m, const double* G_in, const double* F_in,
+                                                const double* Lin, const double* b, double* U, int32_t* exitflag,
+                                                int32_t* iters, double* lambda, double* fval) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int G = 64 / P;
+    const int g = threadIdx.x / P, l = threadIdx.x % P;
+    const int64_t s = (int64_t)blockIdx.x * G + g;
+    if (s >= B) return;
+    const int wsm = ws_bytes_rows(N, m);
+    const int wsb = wsm + ((m * 8 + 15) & ~15) + N * ldj_of(N) * 8;
+    char* base = smem + g * wsb;
+    auto w = ws_carve<0>(base, N);
+    double* rnrm = reinterpret_cast<double*>(base + wsm);
+    double* gsave = rnrm + ((m + 1) & ~1);
+    if (l < N) {
+        for (int kk = 0; kk <= l; ++kk) w.R()[l + kk * w.ldj()] = G_in[s * (N * N) + l + kk * N];
+        w.F()[l] = F_in[s * N + l];
+    }
+    for (int i = l; i < m; i += P) w.aflag()[i] = 0;
+    NTM_WSYNC();
+    int flag, its = 0, q = 0;
+    DenseRows rows{Lin, b, rnrm, (int64_t)N, s, m};
+    if (!scale_phase<P>(w, l, false)) {
+        flag = NTM_EXIT_NONFINITE;
+    } else {
+        int code = rows.template prepare_code<P>(w, l);
+        if (code & 1) flag = NTM_EXIT_NONFINITE;
+        else if (code & 2) flag = NTM_EXIT_INFEASIBLE;
+        else {
+            if (l < N) for (int j = 0; j <= l; ++j) gsave[l + j * w.ldj()] = w.R()[l + j * w.ldj()];
+            NTM_WSYNC();
+            flag = gi_solve<P, DenseRows, decltype(w)>(w, rows, m > 0, m, l, &its, &q);
+        }
+    }
+    if (flag == NTM_EXIT_OPTIMAL) {
+        const bool ok =
+            polish_phase<P, DenseRows, decltype(w)>(Prob{}, w, &rows, q, l, gsave, false, false, nullptr, rnrm);
+        if (!ok) {                                       // GI's iterate is returned: GI's multipliers
+            const int id = (l < q) ? w.act()[l] : -1;
+            const double v = (l < q) ? w.uu()[l] / rnrm[id] : 0.0;
+            NTM_WSYNC();
+            for (int i = l; i < m; i += P) rnrm[i] = 0.0;
+            NTM_WSYNC();
+            if (id >= 0) rnrm[id] = v;
+            NTM_WSYNC();
+        }
+    } else if (l < N) {
+        w.U()[l] = (flag == NTM_EXIT_MAXITER) ? w.V()[l] * w.D()[l] : 0.0;
+    }
+    NTM_WSYNC();
+    if (l < N) U[s * N + l] = w.U()[l];
+    if (lambda)
+        for (int i = l; i < m; i += P) lambda[s * m + i] = (flag == NTM_EXIT_OPTIMAL) ? rnrm[i] : 0.0;
+    if (fval) {
+        // 1/2 U'GU + F'U on the caller's data (the lower triangle k_qp reads); 0 where U = 0
+        double t = 0.0;
+        if (l < N && (flag == NTM_EXIT_OPTIMAL || flag == NTM_EXIT_MAXITER)) {
+            double gu = 0.0;
+            for (int j = 0; j < N; ++j)
+                gu += G_in[s * (N * N) + (j <= l ? l + j * N : j + l * N)] * w.U()[j];
+            t = (0.5 * gu + F_in[s * N + l]) * w.U()[l];
+        }
+        t = gsum<P>(t);
+        if (l == 0) fval[s] = t;
+    }
     if (l == 0) {
         exitflag[s] = flag;
         if (iters) iters[s] = its;
@@ -675,6 +756,24 @@ int ensure_buf(ntm_ctx* ctx, size_t bytes) {
 
 size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
 
+template <int P>
+int launch_step_dual(ntm_ctx* ctx, const Prob& pb, int64_t B, const double* x_k, double* rho, double* U_old, double* U,
+                     double* x_pred, double* x_next, int32_t* exitflag, int32_t* inner_iters, int32_t* active_ws,
+                     double* lambda, double* rho_qp, hipStream_t st) {
+    constexpr int G = 64 / P;
+    const size_t lds = (size_t)G * ws_bytes(pb.N, false);
+    if (int rc = set_lds(ctx, k_mpc_step_dual<P>, lds)) return rc;
+    const int64_t blocks = (B + G - 1) / G;
+    hipLaunchKernelGGL((k_mpc_step_dual<P>), dim3((unsigned)blocks), dim3(64), lds, st, pb, B, x_k, rho, U_old, U,
+                       x_pred, x_next, exitflag, inner_iters, active_ws, lambda, rho_qp);
+    return check_hip(ctx, hipGetLastError(), "k_mpc_step_dual launch");
+}
+int rows_of(const ntm_config* c) {
+    return c->mode == NTM_MODE_NONE ? 0
+           : c->mode == NTM_MODE_BOX ? 2 * c->N
+           : c->mode == NTM_MODE_FULL_DU ? 8 * c->N + 2 : 6 * c->N + 4;
+}
+
 }  // namespace
 
 extern "C" {
@@ -896,6 +995,76 @@ int ntm_mpc_step_ws_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_conf
     launch_step<P, NN>(ctx, pb, B, x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters, active_ws, st)
     return NTM_DISPATCH_P(cfg->N, use_generic(cfg), CALL);
 #undef CALL
+}
+
+int ntm_mpc_step_dual_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, int64_t B,
+                             const double* x_k, double* rho, double* U_old, double* U, double* x_pred,
+                             double* x_next, int32_t* exitflag, int32_t* inner_iters, int32_t* active_ws,
+                             double* lambda, double* rho_qp, void* stream) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B);
+    if (rc) return rc;
+    if (B == 0) return NTM_OK;
+    if (!x_k || !rho || !U_old || !U || !x_pred || !x_next || !exitflag || !inner_iters || !rho_qp ||
+        (!lambda && rows_of(cfg) > 0))
+        return fail(ctx, NTM_E_INVALID, "null array");
+    Prob pb = make_prob(phys, cfg);
+    pb.stats = ctx->stats;
+    if (ctx->gen_on) attach_gen(ctx->gen, phys, cfg, pb);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // every horizon on the runtime-N kernels (the export is compiled into those only)
+    const int P = lanes_for(cfg->N);
+#define CALL(P_) \
+    launch_step_dual<P_>(ctx, pb, B, x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters, active_ws, lambda, \
+                         rho_qp, st)
+    return P == 16 ? CALL(16) : (P == 32 ? CALL(32) : CALL(64));
+#undef CALL
+}
+
+int ntm_mpc_step_dual(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, int64_t B, const double* x_k,
+                      double* rho, double* U_old, double* U, double* x_pred, double* x_next, int32_t* exitflag,
+                      int32_t* inner_iters, int32_t* active_ws, double* lambda, double* rho_qp) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B);
+    if (rc) return rc;
+    if (B == 0) return NTM_OK;
+    const int N = cfg->N, m = rows_of(cfg);
+    if (!x_k || !rho || !U_old || !U || !x_pred || !x_next || !exitflag || !inner_iters || !rho_qp || (!lambda && m > 0))
+        return fail(ctx, NTM_E_INVALID, "null array");
+    size_t bx = al(2 * B * 8), brho = al(3 * N * B * 8), bu = al(N * B * 8), bxp = al(2 * (N + 1) * B * 8),
+           bi = al(B * 4), bws = active_ws ? al(2 * (N + 1) * B * 4) : 0, bl = al((size_t)m * B * 8);
+    rc = ensure_buf(ctx, bx * 2 + brho * 2 + bu * 2 + bxp + bi * 2 + bws + bl);
+    if (rc) return rc;
+    char* p = static_cast<char*>(ctx->dbuf);
+    double* dx = (double*)p; p += bx;
+    double* drho = (double*)p; p += brho;
+    double* duo = (double*)p; p += bu;
+    double* dU = (double*)p; p += bu;
+    double* dxp = (double*)p; p += bxp;
+    double* dxn = (double*)p; p += bx;
+    double* drq = (double*)p; p += brho;
+    double* dl = (double*)p; p += bl;
+    int32_t* dfl = (int32_t*)p; p += bi;
+    int32_t* dit = (int32_t*)p; p += bi;
+    int32_t* dws = active_ws ? (int32_t*)p : nullptr;
+    hipStream_t st = ctx->stream;
+    const size_t wsb = 2 * (size_t)(N + 1) * B * 4;
+    if ((rc = check_hip(ctx, hipMemcpyAsync(dx, x_k, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
+    if ((rc = check_hip(ctx, hipMemcpyAsync(drho, rho, 3 * N * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
+    if ((rc = check_hip(ctx, hipMemcpyAsync(duo, U_old, N * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
+    if (dws && (rc = check_hip(ctx, hipMemcpyAsync(dws, active_ws, wsb, hipMemcpyHostToDevice, st), "H2D")))
+        return rc;
+    rc = ntm_mpc_step_dual_device(ctx, phys, cfg, B, dx, drho, duo, dU, dxp, dxn, dfl, dit, dws, dl, drq, st);
+    if (rc) return rc;
+    struct { void* h; const void* d; size_t n; } outs[] = {
+        {rho, drho, (size_t)3 * N * B * 8}, {U_old, duo, (size_t)N * B * 8}, {U, dU, (size_t)N * B * 8},
+        {x_pred, dxp, (size_t)2 * (N + 1) * B * 8}, {x_next, dxn, (size_t)2 * B * 8}, {exitflag, dfl, (size_t)B * 4},
+        {inner_iters, dit, (size_t)B * 4}, {active_ws, dws, wsb}, {lambda, dl, (size_t)m * B * 8},
+        {rho_qp, drq, (size_t)3 * N * B * 8}};
+    for (auto& o : outs)
+        if (o.h && o.d && o.n && (rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H")))
+            return rc;
+    return check_hip(ctx, hipStreamSynchronize(st), "sync");
 }
 
 int ntm_step_launch_info(int32_t N, int32_t* lanes, int32_t* horizon_template) {
@@ -1162,6 +1331,74 @@ int ntm_qp_mixed_device(ntm_ctx* ctx, int64_t B, int32_t N, int32_t m, const dou
     hipLaunchKernelGGL((k_qp_mixed<64>), dim3((unsigned)B), dim3(64), lds, (hipStream_t)stream, B, N, m, G, F, Lin, b,
                        U, U32, exitflag, info, iters32);
     return check_hip(ctx, hipGetLastError(), "k_qp_mixed");
+}
+
+int ntm_qp_dual_device(ntm_ctx* ctx, int64_t B, int32_t N, int32_t m, const double* G, const double* F,
+                       const double* Lin, const double* b, double* U, int32_t* exitflag, int32_t* iters,
+                       double* lambda, double* fval, void* stream) {
+    DeviceGuard dg(ctx);
+    if (!ctx) return NTM_E_INVALID;
+    if (N < 1 || N > NTM_MAX_N) return fail(ctx, NTM_E_INVALID, "N out of range [1, 64]");
+    if (m < 0 || m > 8 * NTM_MAX_N + 4) return fail(ctx, NTM_E_INVALID, "m out of range");
+    if (B < 0) return fail(ctx, NTM_E_INVALID, "negative batch");
+    if (B == 0) return NTM_OK;
+    if (!G || !F || !U || !exitflag) return fail(ctx, NTM_E_INVALID, "null array");
+    if (m > 0 && (!Lin || !b || !lambda)) return fail(ctx, NTM_E_INVALID, "m > 0 needs Lin, b and lambda");
+    int P = lanes_for(N), Gs = 64 / P;
+    // k_qp's workspace: the export takes no LDS of its own (k_qp_dual)
+    size_t per = (size_t)ws_bytes_rows(N, m) + ((m * 8 + 15) & ~15) + (size_t)N * ldj_of(N) * 8;
+    size_t lds = Gs * per;
+    unsigned blocks = (unsigned)((B + Gs - 1) / Gs);
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if (P == 16) {
+        if ((rc = set_lds(ctx, k_qp_dual<16>, lds))) return rc;
+        hipLaunchKernelGGL((k_qp_dual<16>), dim3(blocks), dim3(64), lds, st, B, N, m, G, F, Lin, b, U, exitflag,
+                           iters, lambda, fval);
+    } else if (P == 32) {
+        if ((rc = set_lds(ctx, k_qp_dual<32>, lds))) return rc;
+        hipLaunchKernelGGL((k_qp_dual<32>), dim3(blocks), dim3(64), lds, st, B, N, m, G, F, Lin, b, U, exitflag,
+                           iters, lambda, fval);
+    } else {
+        if ((rc = set_lds(ctx, k_qp_dual<64>, lds))) return rc;
+        hipLaunchKernelGGL((k_qp_dual<64>), dim3(blocks), dim3(64), lds, st, B, N, m, G, F, Lin, b, U, exitflag,
+                           iters, lambda, fval);
+    }
+    return check_hip(ctx, hipGetLastError(), "k_qp_dual");
+}
+
+int ntm_qp_kkt_device(ntm_ctx* ctx, int64_t B, int32_t N, int32_t m, const double* G, const double* F,
+                      const double* Lin, const double* b, const double* U, const double* lambda, double* kkt,
+                      void* stream) {
+    DeviceGuard dg(ctx);
+    if (!ctx) return NTM_E_INVALID;
+    if (N < 1 || N > NTM_MAX_N) return fail(ctx, NTM_E_INVALID, "N out of range [1, 64]");
+    if (m < 0 || m > 8 * NTM_MAX_N + 4) return fail(ctx, NTM_E_INVALID, "m out of range");
+    if (B < 0) return fail(ctx, NTM_E_INVALID, "negative batch");
+    if (B == 0) return NTM_OK;
+    if (!G || !F || !U || !kkt) return fail(ctx, NTM_E_INVALID, "null array");
+    if (m > 0 && (!Lin || !b || !lambda)) return fail(ctx, NTM_E_INVALID, "m > 0 needs Lin, b and lambda");
+    const int P = lanes_for(N), Gs = 64 / P;
+    const unsigned blocks = (unsigned)((B + Gs - 1) / Gs);
+    hipStream_t st = (hipStream_t)stream;
+    if (P == 16)
+        hipLaunchKernelGGL((k_qp_kkt<16>), dim3(blocks), dim3(64), 0, st, B, N, m, G, F, Lin, b, U, lambda, kkt);
+    else if (P == 32)
+        hipLaunchKernelGGL((k_qp_kkt<32>), dim3(blocks), dim3(64), 0, st, B, N, m, G, F, Lin, b, U, lambda, kkt);
+    else
+        hipLaunchKernelGGL((k_qp_kkt<64>), dim3(blocks), dim3(64), 0, st, B, N, m, G, F, Lin, b, U, lambda, kkt);
+    return check_hip(ctx, hipGetLastError(), "k_qp_kkt");
+}
+
+int ntm_mpc_kkt_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, int64_t B, const double* x_k,
+                       const double* rho_qp, const double* U, const double* lambda, double* kkt, void* stream) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B);
+    if (rc || B == 0) return rc;
+    if (!x_k || !rho_qp || !U || !kkt || (!lambda && rows_of(cfg) > 0)) return fail(ctx, NTM_E_INVALID, "null array");
+    Prob pb = make_prob(phys, cfg);
+    NTM_GROUP_LAUNCH(k_mpc_kkt, cfg->N, B, (hipStream_t)stream, pb, B, x_k, rho_qp, U, lambda, kkt);
+    return check_hip(ctx, hipGetLastError(), "k_mpc_kkt");
 }
 
 // splitmix64-based counter generator (identical to oracle/ntm_oracle.py scenario_x0)

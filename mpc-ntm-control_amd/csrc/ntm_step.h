@@ -91,10 +91,13 @@ __device__ __forceinline__ void load_candidates(const Prob& pb, const W& w, int6
 #ifndef NTM_ROLL_LIFTED
 #define NTM_ROLL_LIFTED 1
 #endif
-// one MPC step on LDS-resident state; returns exit flag, sets *iters
-template <int P, class W>
+// one MPC step on LDS-resident state; returns exit flag, sets *iters.
+// DUAL (k_mpc_step_dual): rho_qp (this scenario's 3N record in HBM) receives the
+// scheduling rho each QP is built from, so it ends as the last QP's; *q_last is that
+// QP's active-row count (w.act(), multipliers by position in w.uu(): qp_phase)
+template <int P, class W, bool DUAL = false>
 __device__ __forceinline__ int mpc_step_dev(const Prob& pb, const W& w, double x0, double x1, int l, int* iters,
-                            int64_t B = 0, int64_t s = 0) {
+                            int64_t B = 0, int64_t s = 0, double* rho_qp = nullptr, int* q_last = nullptr) {
     int flag = NTM_EXIT_OPTIMAL, it;
     int n_qp = 0, n_gi = 0, n_act = 0, n_gen = 0, n_try = 0, n_girun = 0;
 #ifdef NTM_STAMPS
@@ -107,7 +110,11 @@ __device__ __forceinline__ int mpc_step_dev(const Prob& pb, const W& w, double x
     for (it = 1; it <= pb.i_sim; ++it) {
         int qi = 0, qa = 0, ns = 0;
         bool yv = false;
-        flag = qp_phase<P>(pb, w, x0, x1, l, &qi, &qa, &ns, (it - 1) & 1, &n_try, &n_girun, it, &yv);
+        if constexpr (DUAL) {
+            for (int e = l; e < 3 * w.n(); e += P) rho_qp[e] = w.rho()[e];
+        }
+        flag = qp_phase<P, W, DUAL>(pb, w, x0, x1, l, &qi, &qa, &ns, (it - 1) & 1, &n_try, &n_girun, it, &yv);
+        if constexpr (DUAL) *q_last = qa;
         ++n_qp;
         n_gi += qi;
         n_act += qa;
@@ -235,6 +242,66 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, NN, FAR)) void k_mpc_step
     if (active_ws)
         for (int e = l; e < 2 * (N + 1); e += P) active_ws[s * (2 * (N + 1)) + e] = w.cand()[e];
     NTM_STAMPS_FLUSH();
+}
+
+// k_mpc_step<P, 0, true> (the runtime-N kernel, generator build) with the last QP's
+// multipliers and scheduling rho exported (ntm_mpc_step_dual).  A sibling kernel and
+// not a flag of k_mpc_step: two more kernel arguments on the template would change
+// every existing instantiation's argument block.  lambda[rows(mode)] per scenario,
+// quadprog's lambda.ineqlin by row id (mu_i / rn_i; zero on inactive rows and for
+// every exit flag but 1).  After the last rollout the workspace still holds that
+// QP's Gamma, scaling and row norms: the rollout updates rho and does not re-lift.
+template <int P>
+__global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_step_dual(
+    Prob pb, int64_t B, const double* __restrict__ x_k, double* __restrict__ rho, double* __restrict__ U_old,
+    double* __restrict__ U, double* __restrict__ x_pred, double* __restrict__ x_next, int32_t* __restrict__ exitflag,
+    int32_t* __restrict__ inner_iters, int32_t* __restrict__ active_ws, double* __restrict__ lambda,
+    double* __restrict__ rho_qp) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int G = 64 / P;
+    const int g = threadIdx.x / P, l = threadIdx.x % P;
+    const int64_t s = xcd_swizzle(blockIdx.x, gridDim.x) * G + g;
+    const int N = pb.N;
+    if (s >= B) return;
+    auto w = ws_carve<0, true, false>(smem + g * ws_bytes(N, false), N, &pb, s);
+    const double x0 = x_k[2 * s], x1 = x_k[2 * s + 1];
+    if (active_ws) {
+        load_candidates<P>(pb, w, B, s, active_ws, l);
+    } else if (l < 2) {
+        w.cand()[l * (N + 1) + N] = -1;
+    }
+    load_state<P>(w, B, s, rho, U_old, l);
+    scn_store(pb, w, pb.g.first_id + s, l);
+    NTM_WSYNC();
+    int its, q = 0;
+    int flag = mpc_step_dev<P, decltype(w), true>(pb, w, x0, x1, l, &its, B, s, rho_qp + s * (3 * N), &q);
+    {
+        const StructRows rows(pb);
+        const int nrows = rows.rows();
+        double* ls = lambda + s * nrows;
+        for (int i = l; i < nrows; i += P) {
+            double v = 0.0;
+            if (flag == NTM_EXIT_OPTIMAL)
+                for (int a = 0; a < q; ++a)
+                    if (w.act()[a] == i) v = w.uu()[a] / rows.rnorm(w, i);
+            ls[i] = v;
+        }
+    }
+    store_record<P>(rho + s * (3 * N), w.rho(), 3 * N, l);
+    store_record<P>(U_old + s * N, w.Uold(), N, l);
+    store_record<P>(U + s * N, w.U(), N, l);
+    store_record<P>(x_pred + s * (2 * (N + 1)), w.xp(), 2 * (N + 1), l);
+    {
+        double n0, n1;
+        plant_step<true>(pb, scn_coef(pb, w), x0, x1, w.U()[0], n0, n1, pb.g.first_id + s, pb.g.k0);
+        if (l < 2) x_next[2 * s + l] = l ? n1 : n0;
+    }
+    if (l == 0) {
+        exitflag[s] = flag;
+        inner_iters[s] = its;
+    }
+    if (active_ws)
+        for (int e = l; e < 2 * (N + 1); e += P) active_ws[s * (2 * (N + 1)) + e] = w.cand()[e];
 }
 
 template <int P, int NN, bool FAR = ws_far(NN)>

@@ -491,6 +491,120 @@ class NtmMpc:
                     "ntm_qp_device")
         return U, flag, its
 
+    # ------------------------------------------------------------ multipliers and the KKT audit
+    def _qp_args(self, H, f, Lin, b):
+        N, Bn = f.shape
+        m = 0 if Lin is None else b.shape[0]
+        H, _ = _dev_arg(H, (N * N, Bn), name="H")
+        f, _ = _dev_arg(f, (N, Bn), name="f")
+        if m:
+            Lin, _ = _dev_arg(Lin, (m * N, Bn), name="A")
+            b, _ = _dev_arg(b, (m, Bn), name="b")
+        return N, Bn, m, H, f, (Lin if m else None), (b if m else None)
+
+    def quadprog_dual(self, H: torch.Tensor, f: torch.Tensor, Lin: torch.Tensor | None, b: torch.Tensor | None):
+        """[x, fval, exitflag, output, lambda] = quadprog(H, f, A, b) for a batch
+        (ntm_qp_dual_device).  Returns (U (N, B), fval (B,), exitflag (B,),
+        iterations (B,), lambda (m, B)): U, exitflag and iterations are quadprog()'s
+        bit for bit; lambda is quadprog's lambda.ineqlin (>= 0, one entry per row
+        of A, zero on inactive rows and wherever exitflag != 1); fval =
+        1/2 U'HU + f'U at the returned U."""
+        N, Bn, m, H, f, Lin, b = self._qp_args(H, f, Lin, b)
+        U, lam, fval = self._empty(N, Bn), self._empty(m, Bn), self._empty(Bn)
+        flag = self._empty(Bn, dtype=torch.int32)
+        its = self._empty(Bn, dtype=torch.int32)
+        self._raise(self.lib.ntm_qp_dual_device(self._ctx, Bn, N, m, _ptr(H), _ptr(f), _ptr(Lin), _ptr(b), _ptr(U),
+                                                _ptr(flag), _ptr(its), _ptr(lam) if m else None, _ptr(fval),
+                                                self._stream()), "ntm_qp_dual_device")
+        return U, fval, flag, its, lam
+
+    def kkt(self, H: torch.Tensor, f: torch.Tensor, Lin: torch.Tensor | None, b: torch.Tensor | None,
+            U: torch.Tensor, lam: torch.Tensor | None):
+        """The KKT audit of (U, lambda) on explicit QP data (ntm_qp_kkt_device):
+        (4, B) = stationarity, primal, dual, complementarity in the solver's scaled
+        units (include/ntm_mpc.h); NaN for a scenario with non-finite input."""
+        N, Bn, m, H, f, Lin, b = self._qp_args(H, f, Lin, b)
+        U, _ = _dev_arg(U, (N, Bn), name="U")
+        if m:
+            lam, _ = _dev_arg(lam, (m, Bn), name="lam")
+        out = self._empty(4, Bn)
+        self._raise(self.lib.ntm_qp_kkt_device(self._ctx, Bn, N, m, _ptr(H), _ptr(f), _ptr(Lin), _ptr(b), _ptr(U),
+                                               _ptr(lam) if m else None, _ptr(out), self._stream()),
+                    "ntm_qp_kkt_device")
+        return out
+
+    def step_dual(self, x_k: torch.Tensor, rho: torch.Tensor, U_old: torch.Tensor, cfg: Config | None = None,
+                  active_ws: torch.Tensor | None = None):
+        """step() plus, in the returned dict, ``lambda`` (cfg.m, B): the multipliers of
+        the step's last QP by row id (zero where its exit flag is not 1), and
+        ``rho_qp`` (3N, B): the scheduling rho that QP was built from
+        (ntm_mpc_step_dual_device).  Every horizon runs on the runtime-N kernels
+        here, so U agrees with step() to the parity tolerances, not bit for bit."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x_k.shape[1]
+        xk, _ = _dev_arg(x_k, (2, Bn), name="x_k")
+        rh, rho_st = _dev_arg(rho, (3 * N, Bn), name="rho")
+        uo, uo_st = _dev_arg(U_old, (N, Bn), name="U_old")
+        ws, ws_st = (None, False) if active_ws is None else _dev_arg(active_ws, (2 * (N + 1), Bn), torch.int32,
+                                                                     "active_ws")
+        out = {"U": self._empty(N, Bn), "x_pred": self._empty(2 * (N + 1), Bn), "x_next": self._empty(2, Bn),
+               "exitflag": self._empty(Bn, dtype=torch.int32), "inner_iters": self._empty(Bn, dtype=torch.int32),
+               "lambda": self._empty(cfg.m, Bn), "rho_qp": self._empty(3 * N, Bn)}
+        rc = self.lib.ntm_mpc_step_dual_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()), Bn,
+                                               _ptr(xk), _ptr(rh), _ptr(uo), _ptr(out["U"]), _ptr(out["x_pred"]),
+                                               _ptr(out["x_next"]), _ptr(out["exitflag"]), _ptr(out["inner_iters"]),
+                                               _ptr(ws), _ptr(out["lambda"]) if cfg.m else None, _ptr(out["rho_qp"]),
+                                               self._stream())
+        self._raise(rc, "ntm_mpc_step_dual_device")
+        for staged, dst, src in ((rho_st, rho, rh), (uo_st, U_old, uo), (ws_st, active_ws, ws)):
+            if staged:
+                dst.copy_(src)
+        return out
+
+    def step_dual_host(self, x_k: np.ndarray, rho: np.ndarray, U_old: np.ndarray, cfg: Config | None = None,
+                       active_ws: np.ndarray | None = None):
+        """ntm_mpc_step_dual with host arrays (the MEX path): step_host plus ``lambda``
+        and ``rho_qp``."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x_k.shape[1]
+        xk, _ = _host_arg(x_k, (2, Bn), name="x_k")
+        rh, rho_st = _host_arg(rho, (3 * N, Bn), name="rho")
+        uo, uo_st = _host_arg(U_old, (N, Bn), name="U_old")
+        ws, ws_st = (None, False) if active_ws is None else _host_arg(active_ws, (2 * (N + 1), Bn), np.int32,
+                                                                      "active_ws")
+        out = {"U": _host_empty(N, Bn), "x_pred": _host_empty(2 * (N + 1), Bn), "x_next": _host_empty(2, Bn),
+               "exitflag": np.empty(Bn, np.int32), "inner_iters": np.empty(Bn, np.int32),
+               "lambda": _host_empty(cfg.m, Bn), "rho_qp": _host_empty(3 * N, Bn)}
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))          # noqa: E731
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))           # noqa: E731
+        rc = self.lib.ntm_mpc_step_dual(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()), Bn, dp(xk),
+                                        dp(rh), dp(uo), dp(out["U"]), dp(out["x_pred"]), dp(out["x_next"]),
+                                        ip(out["exitflag"]), ip(out["inner_iters"]), None if ws is None else ip(ws),
+                                        dp(out["lambda"]) if cfg.m else None, dp(out["rho_qp"]))
+        self._raise(rc, "ntm_mpc_step_dual")
+        for staged, dst, src in ((rho_st, rho, rh), (uo_st, U_old, uo), (ws_st, active_ws, ws)):
+            if staged:
+                dst[...] = src
+        return out
+
+    def step_kkt(self, x_k: torch.Tensor, rho_qp: torch.Tensor, U: torch.Tensor, lam: torch.Tensor | None,
+                 cfg: Config | None = None):
+        """The KKT audit of an MPC step's own QP (ntm_mpc_kkt_device), rebuilt in the
+        kernel from x_k (2, B) and rho_qp (3N, B) and never materialised: (4, B) as
+        kkt().  ``lam`` (cfg.m, B) in the step's row order (step_dual)."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x_k.shape[1]
+        xk, _ = _dev_arg(x_k, (2, Bn), name="x_k")
+        rq, _ = _dev_arg(rho_qp, (3 * N, Bn), name="rho_qp")
+        U, _ = _dev_arg(U, (N, Bn), name="U")
+        if cfg.m:
+            lam, _ = _dev_arg(lam, (cfg.m, Bn), name="lam")
+        out = self._empty(4, Bn)
+        self._raise(self.lib.ntm_mpc_kkt_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()), Bn,
+                                                _ptr(xk), _ptr(rq), _ptr(U), _ptr(lam) if cfg.m else None, _ptr(out),
+                                                self._stream()), "ntm_mpc_kkt_device")
+        return out
+
 
 def _quadprog_mixed(self, H: torch.Tensor, f: torch.Tensor, Lin: torch.Tensor | None, b: torch.Tensor | None):
     """Config 5's fp32 leg (ntm_qp_mixed_device; not the fp64 product path): the QP
