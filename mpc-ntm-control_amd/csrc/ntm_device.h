@@ -1654,10 +1654,13 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
             NTM_WSYNC();
             double g1 = 0.0, g2 = 0.0, h11 = 0.0, h12 = 0.0, h22 = 0.0;
             if (l < N) {
-                const double qa = w.xp()[2 * l] + w.e()[2 * l] - pb.r[0];
-                const double qb = w.xp()[2 * l + 1] + w.e()[2 * l + 1] - pb.r[1];
-                const double aa = w.Phi()[2 * l], ab = w.Phi()[2 * l + 1];
-                const double ca = y2s[2 * l], cb = y2s[2 * l + 1];
+                constexpr bool AL = pair_ld_ok<P, W>();
+                const dpair yv = ld_pair<AL>(w.xp() + 2 * l), ev = ld_pair<AL>(w.e() + 2 * l);
+                const dpair av = ld_pair<AL>(w.Phi() + 2 * l), cv = ld_pair<AL>(y2s + 2 * l);
+                const double qa = yv.x + ev.x - pb.r[0];
+                const double qb = yv.y + ev.y - pb.r[1];
+                const double aa = av.x, ab = av.y;
+                const double ca = cv.x, cb = cv.y;
                 const double oa = om.o0(aa, ab), ob = om.o1(aa, ab);      // Om y1
                 const double oc = om.o0(ca, cb), od = om.o1(ca, cb);      // Om y2
                 g1 = oa * qa + ob * qb;
@@ -1799,9 +1802,12 @@ __device__ __forceinline__ bool polish_compact(const Prob& pb, const W& w, const
             NTM_WSYNC();
             double num = 0.0, den = 0.0;
             if (l < N) {
-                const double y0a = w.xp()[2 * l] + w.e()[2 * l] - pb.r[0];
-                const double y0b = w.xp()[2 * l + 1] + w.e()[2 * l + 1] - pb.r[1];
-                const double za = w.Phi()[2 * l], zb = w.Phi()[2 * l + 1];
+                constexpr bool AL = pair_ld_ok<P, W>();
+                const dpair yv = ld_pair<AL>(w.xp() + 2 * l), ev = ld_pair<AL>(w.e() + 2 * l);
+                const dpair zv2 = ld_pair<AL>(w.Phi() + 2 * l);
+                const double y0a = yv.x + ev.x - pb.r[0];
+                const double y0b = yv.y + ev.y - pb.r[1];
+                const double za = zv2.x, zb = zv2.y;
                 const double oa = om.o0(za, zb), ob = om.o1(za, zb);
                 num = oa * y0a + ob * y0b;
                 den = oa * za + ob * zb;
@@ -2561,7 +2567,8 @@ __device__ __forceinline__ bool rollout_phase(const Prob& pb, const W& w, double
     double dsum = 0.0, u = 0.0;
     if (l < N) {
         double r1, r2, r3;
-        rho_eval(k, w.xp()[2 * l], w.xp()[2 * l + 1], r1, r2, r3);
+        const dpair xv = ld_pair<pair_ld_ok<P, W>()>(w.xp() + 2 * l);
+        rho_eval(k, xv.x, xv.y, r1, r2, r3);
         w.rho()[3 * l] = r1;
         w.rho()[3 * l + 1] = r2;
         w.rho()[3 * l + 2] = r3;

@@ -128,10 +128,8 @@ template <int J0, class W>
 __device__ __forceinline__ void gamma_row_chunk_lanes(const W& w, const double* gr, const double* v, double& y) {
     double g[5], x[5];
 #pragma unroll
-    for (int u = 0; u < 5; ++u) {
-        g[u] = gr[w.gidx(0, J0 + u)];
-        x[u] = v[J0 + u];
-    }
+    for (int u = 0; u < 5; ++u) g[u] = gr[w.gidx(0, J0 + u)];
+    ld5<J0, W::kPair>(v, x);                              // (kPair: v is U, d or dr, 16-byte aligned)
     __builtin_amdgcn_sched_barrier(0);
     fmac5_lanes_from<J0>(y, g, x);
 }
@@ -140,11 +138,9 @@ __device__ __forceinline__ void gamma_row_chunk2_lanes(const W& w, const double*
                                                        const double* v2, double& y1, double& y2) {
     double g[5], x1[5], x2[5];
 #pragma unroll
-    for (int u = 0; u < 5; ++u) {
-        g[u] = gr[w.gidx(0, J0 + u)];
-        x1[u] = v1[J0 + u];
-        x2[u] = v2[J0 + u];
-    }
+    for (int u = 0; u < 5; ++u) g[u] = gr[w.gidx(0, J0 + u)];
+    ld5<J0, W::kPair>(v1, x1);
+    ld5<J0, W::kPair>(v2, x2);
     __builtin_amdgcn_sched_barrier(0);
     fmac5x2_lanes_from<J0>(y1, y2, g, x1, x2);
 }
@@ -248,16 +244,18 @@ __device__ __forceinline__ double dot_rows2(const double* a, const double* c, in
 }
 // chunk I0 / 5 of column `lane`'s sum: the batched loads at compile-time offsets, the
 // terms formed on every lane, then added on the lanes <= i
-template <int I0>
+// (AL: a and c are 16-byte aligned, ld_pair)
+template <int I0, bool AL>
 __device__ __forceinline__ void dot_rows2_chunk_lanes(const double* a, const double* c, double& s) {
     double a0[5], a1[5], c0[5], c1[5], t[5];
 #pragma unroll
     for (int u = 0; u < 5; ++u) {
         const int i = I0 + u;
-        a0[u] = a[2 * i];
-        a1[u] = a[2 * i + 1];
-        c0[u] = c[2 * i];
-        c1[u] = c[2 * i + 1];
+        const dpair av = ld_pair<AL>(a + 2 * i), cv = ld_pair<AL>(c + 2 * i);
+        a0[u] = av.x;
+        a1[u] = av.y;
+        c0[u] = cv.x;
+        c1[u] = cv.y;
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -265,15 +263,17 @@ __device__ __forceinline__ void dot_rows2_chunk_lanes(const double* a, const dou
     fadd5_lanes_upto<I0>(s, t);
 }
 // dot_rows2 with imin = the caller's lane (column l on lane l < N): the N = 20 far
-// kernel masks the terms by lane (lane_masked_ok)
+// kernel masks the terms by lane (lane_masked_ok) and reads its pairs aligned (a: a
+// column of the packed Gamma from its even row 0, c: one of the aligned 2N-vectors)
 template <int CH, int P, class W>
 __device__ __forceinline__ double dot_rows2(const W&, const double* a, const double* c, int n, int imin) {
     if constexpr (lane_masked_ok<P, CH, W>()) {
         double s = 0.0;
-        dot_rows2_chunk_lanes<0>(a, c, s);
-        dot_rows2_chunk_lanes<5>(a, c, s);
-        dot_rows2_chunk_lanes<10>(a, c, s);
-        dot_rows2_chunk_lanes<15>(a, c, s);
+        constexpr bool AL = pair_ld_ok<P, W>();
+        dot_rows2_chunk_lanes<0, AL>(a, c, s);
+        dot_rows2_chunk_lanes<5, AL>(a, c, s);
+        dot_rows2_chunk_lanes<10, AL>(a, c, s);
+        dot_rows2_chunk_lanes<15, AL>(a, c, s);
         return s;
     } else {
         return dot_rows2<CH>(a, c, n, imin);

@@ -186,17 +186,19 @@ __device__ __forceinline__ constexpr bool fold_const() { return !(W::kFar && W::
 // Lane-masked chunk of the scaling pass's column pass (lane_masked_ok: column l on lane l),
 // stages I0..I0+4 of column `lane`: the terms of G_ll and F_l formed on every lane, added
 // on the lanes <= i, the non-finite Gamma entries of those lanes into nf
-template <int I0, class OM>
+// (AL: cj and om are 16-byte aligned, ld_pair)
+template <int I0, bool AL, class OM>
 __device__ __forceinline__ void scale_col_chunk_lanes(const OM& qw, const double* cj, const double* om, double& s,
                                                       double& fs, unsigned long long& nf) {
     double ga[5], gb[5], ea[5], eb[5], t[5], tf[5];
 #pragma unroll
     for (int u = 0; u < 5; ++u) {
         const int i = I0 + u;
-        ga[u] = cj[2 * i];
-        gb[u] = cj[2 * i + 1];
-        ea[u] = om[2 * i];
-        eb[u] = om[2 * i + 1];
+        const dpair gv = ld_pair<AL>(cj + 2 * i), ev = ld_pair<AL>(om + 2 * i);
+        ga[u] = gv.x;
+        gb[u] = gv.y;
+        ea[u] = ev.x;
+        eb[u] = ev.y;
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -375,10 +377,11 @@ __device__ __forceinline__ int diag_scale_phase(const Prob& pb, const W& w, int 
             bad |= cs->bad;
         } else if constexpr (lane_masked_ok<P, CH, W>()) {   // terms i < l masked by lane
             unsigned long long nf = 0ull;
-            scale_col_chunk_lanes<0>(qw, cj, om, s, fs, nf);
-            scale_col_chunk_lanes<5>(qw, cj, om, s, fs, nf);
-            scale_col_chunk_lanes<10>(qw, cj, om, s, fs, nf);
-            scale_col_chunk_lanes<15>(qw, cj, om, s, fs, nf);
+            constexpr bool AL = pair_ld_ok<P, W>();     // a Gamma column from row 0, xp
+            scale_col_chunk_lanes<0, AL>(qw, cj, om, s, fs, nf);
+            scale_col_chunk_lanes<5, AL>(qw, cj, om, s, fs, nf);
+            scale_col_chunk_lanes<10, AL>(qw, cj, om, s, fs, nf);
+            scale_col_chunk_lanes<15, AL>(qw, cj, om, s, fs, nf);
             bad |= (int)((nf >> l) & 1ull);
         } else {
         NTM_CHUNK_PRAGMA

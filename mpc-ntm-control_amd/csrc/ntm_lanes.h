@@ -3,7 +3,8 @@
 // or a substitution step's unknown on its own lane): the lane-masked accumulation
 // of the triangular Gamma passes, the lane-masked lift recursion, the triangular
 // substitutions of the echelon re-solve, and the row norms of the scaling pass
-// with their non-zero tracking.  In each the lanes an
+// with their non-zero tracking (and, in plain C++ ahead of them, the aligned pair
+// loads ld_pair / ld5 of the same kernels).  In each the lanes an
 // instruction belongs to are known at compile time, so the instruction runs with
 // EXEC narrowed to them where the plain form computes on every lane and selects.
 //
@@ -60,6 +61,59 @@
 #include "ntm_collectives.h"
 
 namespace ntm {
+
+// ---------------------------------------------------------------------------
+// Aligned pair loads (the slim far N = 20 kernels, W::kPair).  A lane that reads the
+// doubles [2i], [2i+1] of a vector reads 16 contiguous bytes; knowing only that they
+// are 8-byte aligned, the backend's load/store optimizer merges the two reads into one
+// ds_read2_b64 offset1 = offset0 + 1, which the LDS serves as two accesses of four
+// 16-lane groups each: 8 LDS-array cycles for the wave, against 4 for the same bytes
+// as one ds_read_b128 (or as two ds_read_b64), and the 16 waves of a CU share one LDS
+// pipe.  ld_pair<true> tells the compiler the pair is 16-byte aligned, so it reads it
+// with one ds_read_b128; ld_pair<false> is the two plain loads every other kernel had.
+//   Preconditions of ld_pair<true>(p): p is 16-byte aligned, i.e. an even number of
+// doubles into one of the vectors ws_pair_aligned() (ntm_ws.h) asserts: e, xp, Phi,
+// irn, Vb / Uf as one 2N-vector, or a column of the packed Gamma taken at an even row
+// (Gt + gidx(2l, l) - 2l + 2i); and the workspace base is 16-byte aligned (the
+// dynamic LDS base is, and a one-wave block has one workspace).  Loads only: the same
+// bits reach the same arithmetic (tools/lds_read_forms_check.hip compares the three
+// forms, full and partial EXEC).  Both doubles must be readable where the plain form
+// was predicated per element; every caller reads both or neither.
+// ---------------------------------------------------------------------------
+typedef double dpair __attribute__((ext_vector_type(2)));
+template <int P, class W>
+__device__ __forceinline__ constexpr bool pair_ld_ok() {
+    return P == 64 && W::kPair;                            // one scenario per wave, N = 20, far, slim
+}
+template <bool AL>
+__device__ __forceinline__ dpair ld_pair(const double* p) {
+    if constexpr (AL) {
+        return *static_cast<const dpair*>(__builtin_assume_aligned(p, 16));
+    } else {
+        dpair v;
+        v.x = p[0];
+        v.y = p[1];
+        return v;
+    }
+}
+// x[u] = v[J0 + u], u = 0..4 (a chunk of five consecutive entries at a compile-time offset, the
+// same address on every lane).  AL: v is 16-byte aligned, so the chunk holds two aligned
+// pairs, from J0 if it is even and from J0 + 1 if not, and one single entry
+template <int J0, bool AL>
+__device__ __forceinline__ void ld5(const double* v, double (&x)[5]) {
+    if constexpr (AL) {
+        constexpr int o = J0 & 1;                          // the single entry: the first (odd J0) or the last
+        const dpair p0 = ld_pair<true>(v + J0 + o), p1 = ld_pair<true>(v + J0 + o + 2);
+        x[o] = p0.x;
+        x[o + 1] = p0.y;
+        x[o + 2] = p1.x;
+        x[o + 3] = p1.y;
+        x[o ? 0 : 4] = v[J0 + (o ? 0 : 4)];
+    } else {
+#pragma unroll
+        for (int u = 0; u < 5; ++u) x[u] = v[J0 + u];
+    }
+}
 
 // ---------------------------------------------------------------------------
 // Lane-masked accumulation (N = 20, one scenario per wave, row or column =

@@ -103,10 +103,20 @@ template <int I0, int NS, class W>
 __device__ __forceinline__ void lift_chunk_at(const W& w, double& g0, double& g1, double a22, double c0, double c1,
                                               unsigned rec) {
     double ca[5], cb[5];
+    if constexpr (W::kPair && NS == 5) {                  // a11 / a21 are 16-byte aligned (ws_pair_aligned)
+        ld5<I0, true>(w.a11(), ca);
+        ld5<I0, true>(w.a21(), cb);
+    } else if constexpr (W::kPair && I0 % 2 == 0) {       // the last chunk: stages 16..19, two aligned pairs
+        const dpair a0 = ld_pair<true>(w.a11() + I0), a1 = ld_pair<true>(w.a11() + I0 + 2);
+        const dpair b0 = ld_pair<true>(w.a21() + I0), b1 = ld_pair<true>(w.a21() + I0 + 2);
+        ca[0] = a0.x; ca[1] = a0.y; ca[2] = a1.x; ca[3] = a1.y; ca[4] = 0.0;
+        cb[0] = b0.x; cb[1] = b0.y; cb[2] = b1.x; cb[3] = b1.y; cb[4] = 0.0;
+    } else {
 #pragma unroll
-    for (int u = 0; u < 5; ++u) {
-        ca[u] = u < NS ? w.a11()[I0 + u] : 0.0;
-        cb[u] = u < NS ? w.a21()[I0 + u] : 0.0;
+        for (int u = 0; u < 5; ++u) {
+            ca[u] = u < NS ? w.a11()[I0 + u] : 0.0;
+            cb[u] = u < NS ? w.a21()[I0 + u] : 0.0;
+        }
     }
     __builtin_amdgcn_sched_barrier(0);
     lift_chunk_lanes<I0, NS>(g0, g1, ca, cb, a22, c0, c1, rec);
@@ -304,8 +314,9 @@ __device__ __forceinline__ void free_response(const W& w, double x0, double x1, 
     for (int i = l; i < w.n(); i += P) {
         double e0, e1;
         if constexpr (W::kSlim) {                // the lift wrote e itself
-            e0 = w.e()[2 * i];
-            e1 = w.e()[2 * i + 1];
+            const dpair ev = ld_pair<pair_ld_ok<P, W>()>(w.e() + 2 * i);
+            e0 = ev.x;
+            e1 = ev.y;
         } else {
             const double* Ph = w.Phi() + 4 * i;
             e0 = (Ph[0] * x0 + Ph[2] * x1) + w.Lam()[2 * i];

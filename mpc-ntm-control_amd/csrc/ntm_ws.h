@@ -89,7 +89,13 @@ struct WS {
     static constexpr int kAB = slim_ab(NN, FAR);           // kSlim: a11 / a21 (N each) in LDS
     static constexpr bool kSF = slim_far(NN, FAR);          // rho, U_old, cand in the far block
     static constexpr int kRL = kSF ? 0 : 3;                 // kSlim: rho's N-vectors in LDS
-    __device__ __forceinline__ int oJ() const { return (kSlim ? kRL + 4 + kAB : 14) * n() + n() * (n() + 1); }
+    // kSlim: the 2N rinfo ints take N doubles, and vlo / vhi / ldi / kdi / idun leave LDS
+    static constexpr int kRi = kSlim ? 1 : 2;                // doubles of rinfo per N
+    static constexpr int kUo = kSF ? 0 : 1;                  // U_old's N-vector in LDS
+    // (the constexpr forms in n are what the accessors below and the alignment asserts behind
+    // the struct share)
+    static constexpr int oJn(int n) { return (kSlim ? kRL + 4 + kAB : 14) * n + n * (n + 1); }
+    __device__ __forceinline__ int oJ() const { return oJn(n()); }
     __device__ __forceinline__ int oR() const { return oJ() + n() * ldj(); }
     // T = R^{-1} is kept for N <= kMaxNT only: at long horizons its N^2 doubles would
     // halve the scenarios per CU, and the dual direction falls back to back substitution.
@@ -99,10 +105,29 @@ struct WS {
     __device__ __forceinline__ bool useT() const { return !kFar && n() <= kMaxNT; }
     __device__ __forceinline__ int oT() const { return oR() + (n() + 1) * ldj(); }
     // kFar: the E block (packed lower-triangular E, then 2(N+1) ints) replaces J/R/T in LDS
+    static constexpr int oVfar(int n) { return oJn(n) + (n * (n + 1)) / 2 + (n + 1); }
     __device__ __forceinline__ int oV() const {
-        if constexpr (kFar) return oJ() + (n() * (n() + 1)) / 2 + (n() + 1);
+        if constexpr (kFar) return oVfar(n());
         else return oT() + (useT() ? n() * ldj() : 0);   // vector block
     }
+    // kPair (the slim far N = 20 layout, round 15): the 2N-vectors that a lane reads by the pair
+    // [2i], [2i+1] (e, xp, Phi, irn, the re-solve's 2N of scratch at Vb / Uf, Gamma's columns)
+    // start on 16-byte offsets, so such a pair is one aligned 128-bit LDS read (ld_pair,
+    // ntm_lanes.h).  The vector block starts at an odd double (the E block's N + 1 doubles of
+    // ints), and the one vector of odd length in it, uu (N + 1), came after Uf: F .. Uf sat on
+    // odd offsets, xp and what follows on even ones.  uu moves to the head of the block, in
+    // front of rinfo; nothing is padded and nothing else moves.
+    static constexpr bool kPair = kSlim && NN == 20;
+    static constexpr int kUu = kPair ? 1 : 0;               // uu's n() + 1 doubles lead the block
+    static constexpr int oPhin(int n) { return (kSlim ? kRL + kAB : 6) * n; }
+    static constexpr int oEn(int n) { return (kSlim ? kRL + 2 + kAB : 12) * n; }
+    static constexpr int oGtn(int n) { return (kSlim ? kRL + 4 + kAB : 14) * n; }
+    static constexpr int oVecn(int n, int k) { return oVfar(n) + kUu * (n + 1) + (kRi + k) * n; }   // kFar: F = 0, .. Uf = 7
+    static constexpr int oXpn(int n) { return oVfar(n) + (kRi + 9) * n + 1; }
+    static constexpr int oIrnn(int n) { return oVfar(n) + (kRi + 13 + kUo) * n + 3; }
+    static constexpr int oUn(int n) { return oVfar(n) + (kRi + 11) * n + 3; }
+    static constexpr int oDrn(int n) { return oVfar(n) + (kRi + 12 + kUo) * n + 3; }
+    static constexpr int gcoln(int n, int l) { return l * (2 * n - l + 1) - 2 * l; }   // gidx(2l, l) - 2l
     __device__ __forceinline__ double* rho() const {                                  // 3N (3xN col-major)
         if constexpr (kSF) return far + n() * ldj() + (n() + 1) * ldj() + 3 * n();
         else return base;
@@ -111,11 +136,11 @@ struct WS {
     __device__ __forceinline__ double* a11() const { return base + 3 * n(); }         // n()
     __device__ __forceinline__ double* a21() const { return base + 4 * n(); }         // n()
     __device__ __forceinline__ double* bb() const { return base + 5 * n(); }          // n()
-    __device__ __forceinline__ double* Phi() const { return base + (kSlim ? kRL + kAB : 6) * n(); }   // 4N Phi_i (2x2 col-major)
+    __device__ __forceinline__ double* Phi() const { return base + oPhin(n()); }   // 4N Phi_i (2x2 col-major)
     __device__ __forceinline__ double* Lam() const { return base + 10 * n(); }        // 2N
-    __device__ __forceinline__ double* e() const { return base + (kSlim ? kRL + 2 + kAB : 12) * n(); }    // 2N free response
+    __device__ __forceinline__ double* e() const { return base + oEn(n()); }    // 2N free response
     // Gamma, block-lower-triangular and packed by column: column j holds rows 2j..2N-1
-    __device__ __forceinline__ double* Gt() const { return base + (kSlim ? kRL + 4 + kAB : 14) * n(); }   // n()(n()+1)
+    __device__ __forceinline__ double* Gt() const { return base + oGtn(n()); }   // n()(n()+1)
     __device__ __forceinline__ int gidx(int r, int j) const { return j * (2 * n() - j + 1) + r - 2 * j; }
     __device__ __forceinline__ double& gt(int r, int j) const { return Gt()[gidx(r, j)]; }   // r >= 2j
     __device__ __forceinline__ double* J() const {                                   // n() x ldj() row-major
@@ -190,27 +215,29 @@ struct WS {
     }
     // 2N ints (in 2N doubles of space): per state row r, (last column j with
     // Gamma_rj != 0) + 1, plus kRowMulti if it has two or more non-zeros
-    __device__ __forceinline__ int* rinfo() const { return reinterpret_cast<int*>(base + oV()); }
-    // kSlim: the 2N rinfo ints take N doubles, and vlo / vhi / ldi / kdi / idun leave LDS
-    static constexpr int kRi = kSlim ? 1 : 2;                // doubles of rinfo per N
-    __device__ __forceinline__ double* F() const { return base + oV() + kRi * n(); }         // n()  F~
-    __device__ __forceinline__ double* D() const { return base + oV() + (kRi + 1) * n(); }   // n()  Jacobi scaling
-    __device__ __forceinline__ double* V() const { return base + oV() + (kRi + 2) * n(); }   // n()  scaled variables
-    __device__ __forceinline__ double* d() const { return base + oV() + (kRi + 3) * n(); }   // n()
-    __device__ __forceinline__ double* np() const { return base + oV() + (kRi + 4) * n(); }  // n()  GI normal
-    __device__ __forceinline__ double* hv() const { return base + oV() + (kRi + 5) * n(); }  // n()  Householder / polish
-    __device__ __forceinline__ double* Vb() const { return base + oV() + (kRi + 6) * n(); }  // n()  polish fixed (V)
-    __device__ __forceinline__ double* Uf() const { return base + oV() + (kRi + 7) * n(); }  // n()  polish fixed (U)
-    __device__ __forceinline__ double* uu() const { return base + oV() + (kRi + 8) * n(); }  // n()+1 multipliers
-    __device__ __forceinline__ double* xp() const { return base + oV() + (kRi + 9) * n() + 1; }    // 2(n()+1) rollout
-    __device__ __forceinline__ double* U() const { return base + oV() + (kRi + 11) * n() + 3; }    // n()
-    static constexpr int kUo = kSF ? 0 : 1;                  // U_old's N-vector in LDS
+    __device__ __forceinline__ int* rinfo() const { return reinterpret_cast<int*>(base + oV() + kUu * (n() + 1)); }
+    // N-vector k of the block (F = 0 .. Uf = 7): kPair's come from the constexpr offsets the asserts check
+    __device__ __forceinline__ int vec(int k) const {
+        if constexpr (kPair) return oVecn(n(), k);
+        else return oV() + (kRi + k) * n();
+    }
+    __device__ __forceinline__ double* F() const { return base + vec(0); }         // n()  F~
+    __device__ __forceinline__ double* D() const { return base + vec(1); }   // n()  Jacobi scaling
+    __device__ __forceinline__ double* V() const { return base + vec(2); }   // n()  scaled variables
+    __device__ __forceinline__ double* d() const { return base + vec(3); }   // n()
+    __device__ __forceinline__ double* np() const { return base + vec(4); }  // n()  GI normal
+    __device__ __forceinline__ double* hv() const { return base + vec(5); }  // n()  Householder / polish
+    __device__ __forceinline__ double* Vb() const { return base + vec(6); }  // n()  polish fixed (V)
+    __device__ __forceinline__ double* Uf() const { return base + vec(7); }  // n()  polish fixed (U)
+    __device__ __forceinline__ double* uu() const { return base + oV() + (kPair ? 0 : (kRi + 8) * n()); }  // n()+1 multipliers
+    __device__ __forceinline__ double* xp() const { return base + (kPair ? oXpn(n()) : oV() + (kRi + 9) * n() + 1); }    // 2(n()+1) rollout
+    __device__ __forceinline__ double* U() const { return base + (kPair ? oUn(n()) : oV() + (kRi + 11) * n() + 3); }    // n()
     __device__ __forceinline__ double* Uold() const {                                              // n()
         if constexpr (kSF) return rho() + 3 * n();
         else return base + oV() + (kRi + 12) * n() + 3;
     }
-    __device__ __forceinline__ double* dr() const { return base + oV() + (kRi + 12 + kUo) * n() + 3; }    // N: d masked to b < q (GI)
-    __device__ __forceinline__ double* irn() const { return base + oV() + (kRi + 13 + kUo) * n() + 3; }   // 2N: 1/rn_r (0: const row)
+    __device__ __forceinline__ double* dr() const { return base + (kPair ? oDrn(n()) : oV() + (kRi + 12 + kUo) * n() + 3); }    // N: d masked to b < q (GI)
+    __device__ __forceinline__ double* irn() const { return base + (kPair ? oIrnn(n()) : oV() + (kRi + 13 + kUo) * n() + 3); }   // 2N: 1/rn_r (0: const row)
     __device__ __forceinline__ double* ssg() const { return base + oV() + (kRi + 15 + kUo) * n() + 3; }   // N: sign of general row s
     // per-QP constants hoisted out of the solver loops (not kSlim: recomputed from D)
     __device__ __forceinline__ double* vlo() const { return base + oV() + (kRi + 17) * n() + 3; }   // N: umin/D_j
@@ -280,6 +307,35 @@ __host__ __device__ constexpr int ws_bytes(int N, bool far = false) {
     return ws_bytes_rows(N, slim_ab(N, far) ? 6 * N + 4 : 8 * N + 4, far);
 }
 static_assert(16 * ws_bytes(20, true) <= 160 * 1024, "slim N = 20: 16 scenarios per CU");
+// kPair: every vector that ld_pair reads starts on an even double (16 bytes; the workspace
+// itself is a multiple of 16 bytes from a 16-byte aligned base), and so does every column of
+// the packed Gamma: column l starts l (2N - 1 - l) doubles into Gt, and one of l, 2N - 1 - l is even
+template <class W>
+constexpr bool ws_pair_columns_even() {
+    for (int l = 0; l < 20; ++l)
+        if ((W::oGtn(20) + W::gcoln(20, l)) % 2 != 0) return false;
+    return true;
+}
+template <class W>
+constexpr bool ws_pair_aligned() {
+    static_assert(W::kPair, "the slim far N = 20 layout");
+    static_assert(ws_bytes(20, true) % 16 == 0, "a scenario's workspace keeps the next one 16-byte aligned");
+    static_assert(W::oPhin(20) % 2 == 0, "Phi (the re-solve's 2N of scratch) on a 16-byte offset");
+    static_assert(W::oEn(20) % 2 == 0, "e on a 16-byte offset");
+    static_assert(W::oGtn(20) % 2 == 0, "Gt on a 16-byte offset");
+    static_assert(ws_pair_columns_even<W>(), "every packed Gamma column on a 16-byte offset");
+    static_assert(W::oVecn(20, 6) % 2 == 0, "Vb (with Uf the plane search's 2N of scratch) on a 16-byte offset");
+    static_assert(W::oVecn(20, 7) == W::oVecn(20, 6) + 20, "Uf follows Vb");
+    static_assert(W::oVecn(20, 7) + 20 == W::oXpn(20), "xp follows Uf: uu moved, nothing padded");
+    static_assert(W::oXpn(20) % 2 == 0, "xp on a 16-byte offset");
+    static_assert(W::oIrnn(20) % 2 == 0, "irn on a 16-byte offset");
+    // the N-vectors read in chunks of five consecutive entries (ld5): the row dots' U, d, dr and
+    // the lift's a11 / a21 (at 3N and 4N doubles, WS::a11 / a21)
+    static_assert(W::oUn(20) % 2 == 0 && W::oDrn(20) % 2 == 0 && W::oVecn(20, 3) % 2 == 0, "U, dr, d on 16-byte offsets");
+    static_assert(W::kAB == 2 && (3 * 20) % 2 == 0 && (4 * 20) % 2 == 0, "a11, a21 on 16-byte offsets");
+    return true;
+}
+static_assert(ws_pair_aligned<WS<20, false, true>>() && ws_pair_aligned<WS<20, true, true>>(), "slim N = 20: aligned pairs");
 static_assert(4 * ws_bytes(50, true) <= 160 * 1024, "slim N = 50: 4 scenarios per CU");
 
 // s: the scenario's index in the launch (its far block, when the WS has one)

@@ -2,13 +2,17 @@
 of a -DNTM_STAMPS build: each NTM_ACC(i, t) is an s_memtime followed by a
 read-add-write of ntm_lds_stamps[i]; the code between two s_memtime is charged
 to the stamp the second one updates.  Static counts (loops counted once), so a
-guide to what a phase is made of, not a timing.
+guide to what a phase is made of, not a timing.  Per phase also the LDS read
+forms (tools/lds_forms.py): ds_read2_b64 and how many of them address adjacent
+elements, ds_read_b128, ds_read_b64, and the forms' LDS cycles by that tool's table.
 
     python tools/isa_phases.py /tmp/diag20.s [kernel-substring]
 """
 import re
 import sys
 from collections import Counter, defaultdict
+
+from lds_forms import CYCLES, DEFAULT, is_adjacent
 
 NAMES = ("ST_LIFT ST_COST ST_SCALE ST_CAND ST_REGRAM ST_GI ST_POLISH ST_ROLL ST_GI_FACT ST_GI_CHECK "
          "ST_GI_DIR ST_GI_ADD ST_GI_DROP CN_CHECK CN_CAND CN_HIT ST_P_CLASS ST_P_GRAM ST_P_CHOL ST_P_SCHUR "
@@ -70,12 +74,20 @@ def main():
             seg = Counter()
         elif op:
             seg[classify(op)] += 1
+            if op.startswith("ds_"):
+                seg["ldscyc"] += CYCLES.get(op, DEFAULT)
+                if op in ("ds_read2_b64", "ds_read_b128", "ds_read_b64"):
+                    seg[op[3:]] += 1
+                if op == "ds_read2_b64" and is_adjacent(ln):
+                    seg["adj"] += 1
         i += 1
     total["(tail)"].update(seg)
     keys = ("f64", "valu", "mask", "dpp", "lane", "salu", "lds", "scratch", "vmem", "other")
-    print(f"{'phase':12s} " + " ".join(f"{k:>7s}" for k in keys) + "   total")
-    for name, c in sorted(total.items(), key=lambda kv: -sum(kv[1].values())):
-        print(f"{name:12s} " + " ".join(f"{c[k]:7d}" for k in keys) + f"   {sum(c.values()):5d}")
+    lkeys = ("read2_b64", "adj", "read_b128", "read_b64", "ldscyc")
+    print(f"{'phase':12s} " + " ".join(f"{k:>7s}" for k in keys) + "   total | " + " ".join(f"{k:>9s}" for k in lkeys))
+    for name, c in sorted(total.items(), key=lambda kv: -sum(kv[1][k] for k in keys)):
+        print(f"{name:12s} " + " ".join(f"{c[k]:7d}" for k in keys) + f"   {sum(c[k] for k in keys):5d} | " +
+              " ".join(f"{c[k]:9d}" for k in lkeys))
 
 
 if __name__ == "__main__":
