@@ -37,7 +37,8 @@
 extern "C" {
 #endif
 
-#define NTM_MPC_ABI_VERSION 5   /* v5: ntm_config.Ru (input weight); v4: ntm_scenario_gen */
+#define NTM_MPC_ABI_VERSION 6   /* v6: ntm_observer, ntm_mpc_step_obs / run_obs (additive);
+                                   v5: ntm_config.Ru (input weight); v4: ntm_scenario_gen */
 #define NTM_MAX_N 64
 
 /* Physics constants, NTM_MPC_Sim.m:5-22 (same names and units). */
@@ -341,6 +342,68 @@ int ntm_ctx_set_scenarios(ntm_ctx* ctx, const ntm_scenario_gen* gen);
  * first_id .. first_id+B-1, out4[4s..4s+3] = (j_BS factor, w_dep factor,
  * n(id, k, 0), n(id, k, 1)). */
 void ntm_scenario_sample(const ntm_scenario_gen* gen, int64_t B, int32_t k, double* out4);
+
+/* ---- plant-model mismatch and the offset-free disturbance estimate (ABI v6) ---- */
+/* The entry points above give the controller the scenario's own plasma.  Here the
+ * model may be the caller's nominal plasma while each plant keeps its own, and the
+ * prediction carries an additive disturbance estimate d_hat[2] per scenario (in the
+ * state's units, on the model's constant offset C of NTM_MPC_Sim.m:37), corrected each
+ * step from the one-step prediction error: offset-free MPC with full state measurement.
+ * One step, per scenario:
+ *   model  k_m: the caller's ntm_physics when nominal_model is set, else the
+ *          scenario's plasma (as ntm_mpc_step*), with C1 + d_hat[0], C2 + d_hat[1].
+ *          The lift and the rollout of every LPV iteration use it, so F, the state
+ *          rows' right-hand sides and x_pred follow;
+ *   plant  k_p: the scenario's plasma when a generator with a spread is attached, else
+ *          the caller's; x_next = plant step of k_p at (x_k, U[0]) plus the generator's
+ *          disturbance, exactly as ntm_mpc_step*.  The plant never sees d_hat;
+ *   e      = x_next - m, m the one-step map of k_m WITHOUT d_hat at (x_k, U[0]) from
+ *          rho(x_k), no disturbance (the same expressions as the plant step);
+ *   d_hat[i] <- fma(gain, e[i] - d_hat[i], d_hat[i]): one fused multiply-add of the
+ *          rounded difference, so every implementation agrees bit for bit (gain 0
+ *          freezes d_hat, gain 1 is the deadbeat estimate).  A component whose e is not
+ *          finite keeps its value.
+ * With nominal_model = 0, gain = 0 and d_hat = 0 the step is ntm_mpc_step_ws's (computed
+ * by the runtime-N kernels: every horizon runs on them here, N = 10, 20 and 50 included,
+ * as for ntm_mpc_step_dual, so the results agree with the specialised kernels' to the
+ * parity tolerances, not bit for bit).  The literal switches D4, D6 and D13
+ * (NTM_LITERAL_*) return NTM_E_UNSUPPORTED; NTM_RHO1_SQUARED is allowed.
+ * NTM_E_INVALID: NULL obs, reserved != 0, gain outside [0, 1] or NaN, NULL d_hat. */
+typedef struct {
+    int32_t nominal_model;  /* 1: the controller's model is the caller's ntm_physics; the
+                               generator's j_BS / w_dep spreads are the plant's alone.
+                               0: model = the scenario's plasma, as ntm_mpc_step*        */
+    int32_t reserved;       /* must be 0                                                 */
+    double  gain;           /* estimator gain in [0, 1]; 0 freezes d_hat at its input    */
+} ntm_observer;
+/* ntm_mpc_step_ws with the observer: d_hat[2] per scenario is required, in/out.  When
+ * stepping by hand under nominal_model, the initial rho must come from the nominal
+ * model too: call ntm_mpc_init* with no generator attached (ntm_ctx_set_scenarios(NULL)),
+ * then attach it. */
+int ntm_mpc_step_obs(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg,
+                     const ntm_observer* obs, int64_t B, const double* x_k, double* rho,
+                     double* U_old, double* d_hat, double* U, double* x_pred,
+                     double* x_next, int32_t* exitflag, int32_t* inner_iters,
+                     int32_t* active_ws);
+int ntm_mpc_step_obs_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg,
+                            const ntm_observer* obs, int64_t B, const double* x_k,
+                            double* rho, double* U_old, double* d_hat, double* U,
+                            double* x_pred, double* x_next, int32_t* exitflag,
+                            int32_t* inner_iters, int32_t* active_ws, void* stream);
+/* ntm_mpc_run with the observer, d_hat kept on chip across the k_sim steps.  d0[2] per
+ * scenario is the initial estimate (NULL: zeros).  dk[2(k_sim+1)] per scenario (2 x
+ * (k_sim+1), may be NULL): column 0 is d0, column k+1 the estimate after step k.  The
+ * initial Rho = repmat(rho(x0)) comes from the model (the nominal one under
+ * nominal_model). */
+int ntm_mpc_run_obs(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg,
+                    const ntm_observer* obs, int64_t B, int32_t k_sim, const double* x0,
+                    const double* d0, double* xk, double* uk, double* Uk, double* wpred,
+                    double* dk, int32_t* exitflag, int32_t* inner_iters);
+int ntm_mpc_run_obs_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg,
+                           const ntm_observer* obs, int64_t B, int32_t k_sim,
+                           const double* x0, const double* d0, double* xk, double* uk,
+                           double* Uk, double* wpred, double* dk, int32_t* exitflag,
+                           int32_t* inner_iters, void* stream);
 
 #ifdef __cplusplus
 }

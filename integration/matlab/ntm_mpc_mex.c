@@ -30,6 +30,19 @@
  *   [xk, uk, Uk, wpred, exitflag, iters] = ntm_mpc_mex('run', x0, k_sim, cfg)
  *       outputs 2(k_sim+1)-by-B, k_sim-by-B, N k_sim-by-B, (N+1) k_sim-by-B,
  *       k_sim-by-B, k_sim-by-B (per scenario column: xk(:), uk, Uk(:), ...)
+ *   [U, x_pred, x_next, exitflag, iters, rho, Uold, ws, d_hat] = ...
+ *       ntm_mpc_mex('step_obs', x_k, rho, Uold, d_hat, obs[, cfg[, ws]])
+ *       'step' with plant-model mismatch and the disturbance estimate
+ *       (ntm_mpc_step_obs, ABI v6): obs is a struct with nominal_model (1: the
+ *       controller's model is the nominal plasma, the 'scenarios' spreads are the
+ *       plants' alone) and gain in [0, 1]; d_hat 2-by-B is the carried estimate
+ *       (zeros to start), returned updated as output 9.  Under nominal_model call
+ *       'init' before 'scenarios', so that the initial rho is the nominal model's.
+ *   [xk, uk, Uk, wpred, exitflag, iters, dk] = ...
+ *       ntm_mpc_mex('run_obs', x0, k_sim, obs[, cfg[, d0]])
+ *       'run' with the observer (ntm_mpc_run_obs): d0 2-by-B the initial estimate
+ *       (omitted: zeros); dk 2(k_sim+1)-by-B, column 1 of each scenario's
+ *       2-by-(k_sim+1) history is d0, column k+1 the estimate after step k.
  *   ntm_mpc_mex('scenarios', gen)                               
  *       gen struct with any of seed, first_id, k0, sigma_w, sigma_omega,
  *       jbs_spread, wdep_spread (ntm_scenario_gen): per-scenario plasma and
@@ -206,6 +219,88 @@ static void do_run(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     }
 }
 
+/* obs struct with any of nominal_model, gain (ntm_observer); missing fields are 0 */
+static ntm_observer read_obs(const mxArray* s) {
+    ntm_observer o;
+    if (!s || !mxIsStruct(s)) mexErrMsgIdAndTxt("ntm:arg", "obs must be a struct with nominal_model and gain");
+    memset(&o, 0, sizeof o);
+    o.nominal_model = scalar_field(s, "nominal_model", 0.0) != 0.0;
+    o.gain = scalar_field(s, "gain", 0.0);
+    return o;
+}
+
+/* 'step' with the observer (ntm_mpc_step_obs): d_hat goes in after Uold and comes
+ * back, updated, as output 9 */
+static void do_step_obs(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    if (nrhs < 6) mexErrMsgIdAndTxt("ntm:arg", "usage: ntm_mpc_mex('step_obs', x_k, rho, Uold, d_hat, obs[, cfg[, ws]])");
+    const ntm_observer o = read_obs(prhs[5]);
+    const ntm_config c = read_cfg(nrhs > 6 ? prhs[6] : NULL);
+    ntm_physics p;
+    ntm_physics_default(&p);
+    const size_t B = mxGetN(prhs[1]), N = (size_t)c.N;
+    const double* x = in_matrix(prhs[1], 2, B, "x_k");
+    in_matrix(prhs[2], 3 * N, B, "rho");
+    in_matrix(prhs[3], N, B, "Uold");
+    in_matrix(prhs[4], 2, B, "d_hat");
+    mxArray* rho = mxDuplicateArray(prhs[2]);
+    mxArray* uold = mxDuplicateArray(prhs[3]);
+    mxArray* dh = mxDuplicateArray(prhs[4]);
+    mxArray* U = mxCreateDoubleMatrix(N, B, mxREAL);
+    mxArray* xp = mxCreateDoubleMatrix(2 * (N + 1), B, mxREAL);
+    mxArray* xn = mxCreateDoubleMatrix(2, B, mxREAL);
+    mxArray* fl = mxCreateNumericMatrix(1, B, mxINT32_CLASS, mxREAL);
+    mxArray* it = mxCreateNumericMatrix(1, B, mxINT32_CLASS, mxREAL);
+    mxArray* ws = NULL;
+    if (nrhs > 7) {
+        const mxArray* w = prhs[7];
+        if (!mxIsInt32(w) || mxGetM(w) != 2 * (N + 1) || mxGetN(w) != B)
+            mexErrMsgIdAndTxt("ntm:arg", "ws must be an int32 %d-by-%d array", (int)(2 * (N + 1)), (int)B);
+        ws = mxDuplicateArray(w);
+    } else {
+        ws = mxCreateNumericMatrix(2 * (N + 1), B, mxINT32_CLASS, mxREAL);
+        int32_t* wp = mxGetInt32s(ws);
+        for (size_t i = 0; i < B * 2 * (N + 1); ++i) wp[i] = -1;
+    }
+    check(ntm_mpc_step_obs(ctx(), &p, &c, &o, (int64_t)B, x, mxGetDoubles(rho), mxGetDoubles(uold), mxGetDoubles(dh),
+                           mxGetDoubles(U), mxGetDoubles(xp), mxGetDoubles(xn), mxGetInt32s(fl), mxGetInt32s(it),
+                           mxGetInt32s(ws)),
+          "ntm_mpc_step_obs");
+    mxArray* outs[9] = {U, xp, xn, fl, it, rho, uold, ws, dh};
+    for (int i = 0; i < 9; ++i) {
+        if (i < (nlhs > 0 ? nlhs : 1)) plhs[i] = outs[i];
+        else mxDestroyArray(outs[i]);
+    }
+}
+
+/* 'run' with the observer (ntm_mpc_run_obs): dk is output 7 */
+static void do_run_obs(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    if (nrhs < 4) mexErrMsgIdAndTxt("ntm:arg", "usage: ntm_mpc_mex('run_obs', x0, k_sim, obs[, cfg[, d0]])");
+    const ntm_observer o = read_obs(prhs[3]);
+    const ntm_config c = read_cfg(nrhs > 4 ? prhs[4] : NULL);
+    ntm_physics p;
+    ntm_physics_default(&p);
+    const size_t B = mxGetN(prhs[1]), N = (size_t)c.N;
+    const double* x0 = in_matrix(prhs[1], 2, B, "x0");
+    const double* d0 = nrhs > 5 ? in_matrix(prhs[5], 2, B, "d0") : NULL;
+    const int k = (int)mxGetScalar(prhs[2]);
+    if (k < 1) mexErrMsgIdAndTxt("ntm:arg", "k_sim must be >= 1");
+    mxArray* xk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
+    mxArray* uk = mxCreateDoubleMatrix((size_t)k, B, mxREAL);
+    mxArray* Uk = mxCreateDoubleMatrix(N * (size_t)k, B, mxREAL);
+    mxArray* wp = mxCreateDoubleMatrix((N + 1) * (size_t)k, B, mxREAL);
+    mxArray* fl = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
+    mxArray* it = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
+    mxArray* dk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
+    check(ntm_mpc_run_obs(ctx(), &p, &c, &o, (int64_t)B, k, x0, d0, mxGetDoubles(xk), mxGetDoubles(uk),
+                          mxGetDoubles(Uk), mxGetDoubles(wp), mxGetDoubles(dk), mxGetInt32s(fl), mxGetInt32s(it)),
+          "ntm_mpc_run_obs");
+    mxArray* outs[7] = {xk, uk, Uk, wp, fl, it, dk};
+    for (int i = 0; i < 7; ++i) {
+        if (i < (nlhs > 0 ? nlhs : 1)) plhs[i] = outs[i];
+        else mxDestroyArray(outs[i]);
+    }
+}
+
 static void do_scenarios(int nrhs, const mxArray* prhs[]) {
     if (nrhs < 2 || (mxIsDouble(prhs[1]) && mxGetNumberOfElements(prhs[1]) == 0)) {
         check(ntm_ctx_set_scenarios(ctx(), NULL), "ntm_ctx_set_scenarios");
@@ -233,6 +328,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (!strcmp(cmd, "step")) do_step(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "init")) do_init(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "run")) do_run(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "step_obs")) do_step_obs(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "run_obs")) do_run_obs(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "scenarios")) do_scenarios(nrhs, prhs);
     else if (!strcmp(cmd, "close")) release();
     else mexErrMsgIdAndTxt("ntm:arg", "unknown command '%s'", cmd);

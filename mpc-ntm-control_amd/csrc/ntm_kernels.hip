@@ -768,6 +768,42 @@ int launch_step_dual(ntm_ctx* ctx, const Prob& pb, int64_t B, const double* x_k,
                        x_pred, x_next, exitflag, inner_iters, active_ws, lambda, rho_qp);
     return check_hip(ctx, hipGetLastError(), "k_mpc_step_dual launch");
 }
+template <int P>
+int launch_step_obs(ntm_ctx* ctx, const Prob& pb, int64_t B, const double* x_k, double* rho, double* U_old, double* U,
+                    double* x_pred, double* x_next, int32_t* exitflag, int32_t* inner_iters, int32_t* active_ws,
+                    double* d_hat, const ntm_observer* obs, hipStream_t st) {
+    constexpr int G = 64 / P;
+    const size_t lds = (size_t)G * ws_bytes(pb.N, false);
+    if (int rc = set_lds(ctx, k_mpc_step_obs<P>, lds)) return rc;
+    const int64_t blocks = (B + G - 1) / G;
+    hipLaunchKernelGGL((k_mpc_step_obs<P>), dim3((unsigned)blocks), dim3(64), lds, st, pb, B, x_k, rho, U_old, U,
+                       x_pred, x_next, exitflag, inner_iters, active_ws, d_hat, (int)(obs->nominal_model != 0),
+                       obs->gain);
+    return check_hip(ctx, hipGetLastError(), "k_mpc_step_obs launch");
+}
+template <int P>
+int launch_run_obs(ntm_ctx* ctx, const Prob& pb, int64_t B, int k_sim, const double* x0, const double* d0, double* xk,
+                   double* uk, double* Uk, double* wpred, double* dk, int32_t* exitflag, int32_t* inner_iters,
+                   const ntm_observer* obs, hipStream_t st) {
+    constexpr int G = 64 / P;
+    const size_t lds = (size_t)G * ws_bytes(pb.N, false);
+    if (int rc = set_lds(ctx, k_mpc_run_obs<P>, lds)) return rc;
+    const int64_t blocks = (B + G - 1) / G;
+    hipLaunchKernelGGL((k_mpc_run_obs<P>), dim3((unsigned)blocks), dim3(64), lds, st, pb, B, k_sim, x0, d0, xk, uk, Uk,
+                       wpred, dk, exitflag, inner_iters, (int)(obs->nominal_model != 0), obs->gain);
+    return check_hip(ctx, hipGetLastError(), "k_mpc_run_obs launch");
+}
+// the observer entry points' own checks (after validate): the options, and the literal
+// switches they do not take (D4 / D6 lift another model, D13's plant drops the offset
+// the estimate corrects)
+int validate_obs(ntm_ctx* ctx, const ntm_config* c, const ntm_observer* obs) {
+    if (!obs) return fail(ctx, NTM_E_INVALID, "null observer");
+    if (obs->reserved != 0) return fail(ctx, NTM_E_INVALID, "observer: reserved must be 0");
+    if (!(obs->gain >= 0.0 && obs->gain <= 1.0)) return fail(ctx, NTM_E_INVALID, "observer: gain must be in [0, 1]");
+    if (c->flags & (NTM_LITERAL_PHI_RIGHTMUL | NTM_LITERAL_GAMMA_INDEX | NTM_LITERAL_PLANT_NO_C))
+        return fail(ctx, NTM_E_UNSUPPORTED, "observer: the literal D4 / D6 / D13 switches are not supported");
+    return NTM_OK;
+}
 int rows_of(const ntm_config* c) {
     return c->mode == NTM_MODE_NONE ? 0
            : c->mode == NTM_MODE_BOX ? 2 * c->N
@@ -1063,6 +1099,143 @@ int ntm_mpc_step_dual(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* c
         {rho_qp, drq, (size_t)3 * N * B * 8}};
     for (auto& o : outs)
         if (o.h && o.d && o.n && (rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H")))
+            return rc;
+    return check_hip(ctx, hipStreamSynchronize(st), "sync");
+}
+
+int ntm_mpc_step_obs_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_observer* obs,
+                            int64_t B, const double* x_k, double* rho, double* U_old, double* d_hat, double* U,
+                            double* x_pred, double* x_next, int32_t* exitflag, int32_t* inner_iters,
+                            int32_t* active_ws, void* stream) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B);
+    if (rc) return rc;
+    if ((rc = validate_obs(ctx, cfg, obs))) return rc;
+    if (!d_hat) return fail(ctx, NTM_E_INVALID, "null d_hat");
+    if (B == 0) return NTM_OK;
+    if (!x_k || !rho || !U_old || !U || !x_pred || !x_next || !exitflag || !inner_iters)
+        return fail(ctx, NTM_E_INVALID, "null array");
+    Prob pb = make_prob(phys, cfg);
+    pb.stats = ctx->stats;
+    if (ctx->gen_on) attach_gen(ctx->gen, phys, cfg, pb);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // every horizon on the runtime-N kernels (the observer is compiled into those only)
+    const int P = lanes_for(cfg->N);
+#define CALL(P_) \
+    launch_step_obs<P_>(ctx, pb, B, x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters, active_ws, d_hat, obs, st)
+    return P == 16 ? CALL(16) : (P == 32 ? CALL(32) : CALL(64));
+#undef CALL
+}
+
+int ntm_mpc_step_obs(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_observer* obs, int64_t B,
+                     const double* x_k, double* rho, double* U_old, double* d_hat, double* U, double* x_pred,
+                     double* x_next, int32_t* exitflag, int32_t* inner_iters, int32_t* active_ws) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B);
+    if (rc) return rc;
+    if ((rc = validate_obs(ctx, cfg, obs))) return rc;
+    if (!d_hat) return fail(ctx, NTM_E_INVALID, "null d_hat");
+    if (B == 0) return NTM_OK;
+    if (!x_k || !rho || !U_old || !U || !x_pred || !x_next || !exitflag || !inner_iters)
+        return fail(ctx, NTM_E_INVALID, "null array");
+    const int N = cfg->N;
+    size_t bx = al(2 * B * 8), brho = al(3 * N * B * 8), bu = al(N * B * 8), bxp = al(2 * (N + 1) * B * 8),
+           bi = al(B * 4), bws = active_ws ? al(2 * (N + 1) * B * 4) : 0;
+    rc = ensure_buf(ctx, bx * 3 + brho + bu * 2 + bxp + bi * 2 + bws);
+    if (rc) return rc;
+    char* p = static_cast<char*>(ctx->dbuf);
+    double* dx = (double*)p; p += bx;
+    double* drho = (double*)p; p += brho;
+    double* duo = (double*)p; p += bu;
+    double* dU = (double*)p; p += bu;
+    double* dxp = (double*)p; p += bxp;
+    double* dxn = (double*)p; p += bx;
+    double* ddh = (double*)p; p += bx;
+    int32_t* dfl = (int32_t*)p; p += bi;
+    int32_t* dit = (int32_t*)p; p += bi;
+    int32_t* dws = active_ws ? (int32_t*)p : nullptr;
+    hipStream_t st = ctx->stream;
+    const size_t wsb = 2 * (size_t)(N + 1) * B * 4;
+    if ((rc = check_hip(ctx, hipMemcpyAsync(dx, x_k, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
+    if ((rc = check_hip(ctx, hipMemcpyAsync(drho, rho, 3 * N * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
+    if ((rc = check_hip(ctx, hipMemcpyAsync(duo, U_old, N * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
+    if ((rc = check_hip(ctx, hipMemcpyAsync(ddh, d_hat, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
+    if (dws && (rc = check_hip(ctx, hipMemcpyAsync(dws, active_ws, wsb, hipMemcpyHostToDevice, st), "H2D")))
+        return rc;
+    rc = ntm_mpc_step_obs_device(ctx, phys, cfg, obs, B, dx, drho, duo, ddh, dU, dxp, dxn, dfl, dit, dws, st);
+    if (rc) return rc;
+    struct { void* h; const void* d; size_t n; } outs[] = {
+        {rho, drho, (size_t)3 * N * B * 8}, {U_old, duo, (size_t)N * B * 8}, {d_hat, ddh, (size_t)2 * B * 8},
+        {U, dU, (size_t)N * B * 8}, {x_pred, dxp, (size_t)2 * (N + 1) * B * 8}, {x_next, dxn, (size_t)2 * B * 8},
+        {exitflag, dfl, (size_t)B * 4}, {inner_iters, dit, (size_t)B * 4}, {active_ws, dws, wsb}};
+    for (auto& o : outs)
+        if (o.h && o.d && o.n && (rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H")))
+            return rc;
+    return check_hip(ctx, hipStreamSynchronize(st), "sync");
+}
+
+int ntm_mpc_run_obs_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_observer* obs,
+                           int64_t B, int32_t k_sim, const double* x0, const double* d0, double* xk, double* uk,
+                           double* Uk, double* wpred, double* dk, int32_t* exitflag, int32_t* inner_iters,
+                           void* stream) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B);
+    if (rc) return rc;
+    if ((rc = validate_obs(ctx, cfg, obs))) return rc;
+    if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
+    if (B == 0) return NTM_OK;
+    if (!x0) return fail(ctx, NTM_E_INVALID, "null x0");
+    Prob pb = make_prob(phys, cfg);
+    pb.stats = ctx->stats;
+    if (ctx->gen_on) attach_gen(ctx->gen, phys, cfg, pb);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int P = lanes_for(cfg->N);
+#define CALL(P_) \
+    launch_run_obs<P_>(ctx, pb, B, k_sim, x0, d0, xk, uk, Uk, wpred, dk, exitflag, inner_iters, obs, st)
+    return P == 16 ? CALL(16) : (P == 32 ? CALL(32) : CALL(64));
+#undef CALL
+}
+
+int ntm_mpc_run_obs(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_observer* obs, int64_t B,
+                    int32_t k_sim, const double* x0, const double* d0, double* xk, double* uk, double* Uk,
+                    double* wpred, double* dk, int32_t* exitflag, int32_t* inner_iters) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B);
+    if (rc) return rc;
+    if ((rc = validate_obs(ctx, cfg, obs))) return rc;
+    if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
+    if (B == 0) return NTM_OK;
+    if (!x0) return fail(ctx, NTM_E_INVALID, "null x0");
+    const int N = cfg->N;
+    size_t b0 = al(2 * B * 8), bxk = al(2 * (size_t)(k_sim + 1) * B * 8), buk = al((size_t)k_sim * B * 8),
+           bUk = al((size_t)N * k_sim * B * 8), bwp = al((size_t)(N + 1) * k_sim * B * 8),
+           bi = al((size_t)k_sim * B * 4);
+    rc = ensure_buf(ctx, 2 * b0 + 2 * bxk + buk + bUk + bwp + 2 * bi);
+    if (rc) return rc;
+    char* p = static_cast<char*>(ctx->dbuf);
+    double* dx0 = (double*)p; p += b0;
+    double* dd0 = (double*)p; p += b0;
+    double* dxk = (double*)p; p += bxk;
+    double* ddk = (double*)p; p += bxk;
+    double* duk = (double*)p; p += buk;
+    double* dUk = (double*)p; p += bUk;
+    double* dwp = (double*)p; p += bwp;
+    int32_t* dfl = (int32_t*)p; p += bi;
+    int32_t* dit = (int32_t*)p;
+    hipStream_t st = ctx->stream;
+    if ((rc = check_hip(ctx, hipMemcpyAsync(dx0, x0, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
+    if (d0 && (rc = check_hip(ctx, hipMemcpyAsync(dd0, d0, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
+    rc = ntm_mpc_run_obs_device(ctx, phys, cfg, obs, B, k_sim, dx0, d0 ? dd0 : nullptr, xk ? dxk : nullptr,
+                                uk ? duk : nullptr, Uk ? dUk : nullptr, wpred ? dwp : nullptr, dk ? ddk : nullptr,
+                                exitflag ? dfl : nullptr, inner_iters ? dit : nullptr, st);
+    if (rc) return rc;
+    struct { void* h; void* d; size_t n; } outs[] = {
+        {xk, dxk, 2 * (size_t)(k_sim + 1) * B * 8}, {uk, duk, (size_t)k_sim * B * 8},
+        {Uk, dUk, (size_t)N * k_sim * B * 8},        {wpred, dwp, (size_t)(N + 1) * k_sim * B * 8},
+        {dk, ddk, 2 * (size_t)(k_sim + 1) * B * 8}, {exitflag, dfl, (size_t)k_sim * B * 4},
+        {inner_iters, dit, (size_t)k_sim * B * 4}};
+    for (auto& o : outs)
+        if (o.h && o.n && (rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H")))
             return rc;
     return check_hip(ctx, hipStreamSynchronize(st), "sync");
 }

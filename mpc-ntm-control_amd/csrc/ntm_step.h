@@ -355,6 +355,156 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, NN, FAR)) void k_mpc_run(
     }
 }
 
+// Plant-model mismatch and the offset-free disturbance estimate (ntm_mpc_step_obs /
+// ntm_mpc_run_obs).  Siblings of the runtime-N kernels, as k_mpc_step_dual is, and for
+// its reason: the estimate and the options are kernel arguments, and the model's
+// per-scenario coefficients are four more live values, neither of which the existing
+// instantiations should pay for.  Every horizon runs here (N = 10, 20 and 50 included,
+// like step_dual, Ru != 0 and mode 3 at N = 20).
+//   model  k_m = (nominal ? the launch's plasma : the scenario's), C + d_hat: the lift
+//          and the rollout of every LPV iteration (WSObs, scn_coef's overload);
+//   plant  k_p = the scenario's plasma (a generator with a spread), else the launch's;
+//          it never sees d_hat;
+//   e      = x_next - (k_m's one-step map from rho(x_k) without d_hat, no disturbance);
+//   d_hat <- obs_update(gain, e, d_hat).
+// The carved workspace and the model of scenario s of the launch, d = its estimate
+template <class W>
+__device__ __forceinline__ void obs_model(W& w, const Coef& km, double d0, double d1) {
+    w.mC1 = km.C1 + d0;
+    w.mC2 = km.C2 + d1;
+    w.mbc = km.bc;
+    w.mwdep = km.wdep;
+}
+// The model's one-step map from rho(x_k), without the estimate and without a disturbance:
+// plant_step's own expressions on the model's coefficients.  Its inputs pass through an
+// empty asm first, so the compiler sees values unrelated to the plant step's: sharing
+// rho1, rho2, a11 x0, ... between the two would change how the plant step's sums are
+// fused into multiply-adds, and x_next would no longer be k_mpc_step_dual's bit for bit
+__device__ __forceinline__ void model_step(const Prob& pb, const Coef& km, double x0, double x1, double u, double& m0,
+                                           double& m1) {
+    asm volatile("" : "+v"(x0), "+v"(x1), "+v"(u));
+    plant_step<false>(pb, km, x0, x1, u, m0, m1);
+}
+__device__ __forceinline__ WSObs ws_carve_obs(char* base, int N) {
+    WSObs w;
+    w.N_rt = N;
+    w.base = reinterpret_cast<double*>(base);
+    w.far = nullptr;
+    w.mC1 = w.mC2 = w.mbc = w.mwdep = 0.0;
+    return w;
+}
+
+template <int P>
+__global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_step_obs(
+    Prob pb, int64_t B, const double* __restrict__ x_k, double* __restrict__ rho, double* __restrict__ U_old,
+    double* __restrict__ U, double* __restrict__ x_pred, double* __restrict__ x_next, int32_t* __restrict__ exitflag,
+    int32_t* __restrict__ inner_iters, int32_t* __restrict__ active_ws, double* __restrict__ d_hat, int nominal,
+    double gain) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int G = 64 / P;
+    const int g = threadIdx.x / P, l = threadIdx.x % P;
+    const int64_t s = xcd_swizzle(blockIdx.x, gridDim.x) * G + g;
+    const int N = pb.N;
+    if (s >= B) return;
+    WSObs w = ws_carve_obs(smem + g * ws_bytes(N, false), N);
+    const double x0 = x_k[2 * s], x1 = x_k[2 * s + 1];
+    const double d0 = d_hat[2 * s], d1 = d_hat[2 * s + 1];
+    const int64_t gid = pb.g.first_id + s;
+    const Coef kp = plant_coef(pb, gid);
+    const Coef km = nominal ? pb.k : kp;
+    obs_model(w, km, d0, d1);
+    if (active_ws) {
+        load_candidates<P>(pb, w, B, s, active_ws, l);
+    } else if (l < 2) {
+        w.cand()[l * (N + 1) + N] = -1;
+    }
+    load_state<P>(w, B, s, rho, U_old, l);
+    int its;
+    int flag = mpc_step_dev<P>(pb, w, x0, x1, l, &its, B, s);
+    store_record<P>(rho + s * (3 * N), w.rho(), 3 * N, l);
+    store_record<P>(U_old + s * N, w.Uold(), N, l);
+    store_record<P>(U + s * N, w.U(), N, l);
+    store_record<P>(x_pred + s * (2 * (N + 1)), w.xp(), 2 * (N + 1), l);
+    {
+        const double u0 = w.U()[0];
+        double n0, n1, m0, m1;
+        plant_step<true>(pb, kp, x0, x1, u0, n0, n1, gid, pb.g.k0);
+        model_step(pb, km, x0, x1, u0, m0, m1);
+        const double e0 = obs_update(gain, n0 - m0, d0), e1 = obs_update(gain, n1 - m1, d1);
+        if (l < 2) {
+            x_next[2 * s + l] = l ? n1 : n0;
+            d_hat[2 * s + l] = l ? e1 : e0;
+        }
+    }
+    if (l == 0) {
+        exitflag[s] = flag;
+        inner_iters[s] = its;
+    }
+    if (active_ws)
+        for (int e = l; e < 2 * (N + 1); e += P) active_ws[s * (2 * (N + 1)) + e] = w.cand()[e];
+}
+
+// k_mpc_run<P, 0> with the estimate carried on chip: d0v (2 per scenario, null: zeros),
+// dk (2(k_sim+1) per scenario, may be null): column 0 the initial estimate, column k+1
+// the estimate after step k.  Rho = repmat(rho(x0)) comes from the model.
+template <int P>
+__global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_run_obs(
+    Prob pb, int64_t B, int k_sim, const double* __restrict__ x0v, const double* __restrict__ d0v, double* xk,
+    double* uk, double* Uk, double* wpred, double* dk, int32_t* exitflag, int32_t* inner_iters, int nominal,
+    double gain) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int G = 64 / P;
+    const int g = threadIdx.x / P, l = threadIdx.x % P;
+    const int64_t s = xcd_swizzle(blockIdx.x, gridDim.x) * G + g;
+    const int N = pb.N;
+    if (s >= B) return;
+    WSObs w = ws_carve_obs(smem + g * ws_bytes(N, false), N);
+    double x0 = x0v[2 * s], x1 = x0v[2 * s + 1];
+    double d0 = d0v ? d0v[2 * s] : 0.0, d1 = d0v ? d0v[2 * s + 1] : 0.0;
+    const int64_t gid = pb.g.first_id + s;
+    const Coef kp = plant_coef(pb, gid);
+    const Coef km = nominal ? pb.k : kp;
+    obs_model(w, km, d0, d1);
+    if (l < 2) w.cand()[l * (N + 1) + N] = -1;
+    {   // Rho = repmat(rho(x0), 1, N) (NTM_MPC_Sim.m:63-65); Uold = +inf (D14)
+        double r1, r2, r3;
+        rho_eval(km, x0, x1, r1, r2, r3);
+        if (l < N) {
+            w.rho()[3 * l] = r1;
+            w.rho()[3 * l + 1] = r2;
+            w.rho()[3 * l + 2] = r3;
+            w.Uold()[l] = kInf;
+        }
+        NTM_WSYNC();
+    }
+    const int64_t xs = s * 2 * (int64_t)(k_sim + 1);
+    if (xk && l == 0) { xk[xs] = x0; xk[xs + 1] = x1; }
+    if (dk && l == 0) { dk[xs] = d0; dk[xs + 1] = d1; }
+    for (int kk = 0; kk < k_sim; ++kk) {
+        int its;
+        int flag = mpc_step_dev<P>(pb, w, x0, x1, l, &its, B, s);
+        if (Uk && l < N) Uk[(s * k_sim + kk) * N + l] = w.U()[l];
+        if (wpred) for (int i = l; i <= N; i += P) wpred[(s * k_sim + kk) * (N + 1) + i] = w.xp()[2 * i];
+        const double u0 = w.U()[0];
+        double n0, n1, m0, m1;
+        plant_step<true>(pb, kp, x0, x1, u0, n0, n1, gid, pb.g.k0 + kk);
+        model_step(pb, km, x0, x1, u0, m0, m1);
+        d0 = obs_update(gain, n0 - m0, d0);
+        d1 = obs_update(gain, n1 - m1, d1);
+        if (l == 0) {
+            if (uk) uk[s * k_sim + kk] = u0;
+            if (exitflag) exitflag[s * k_sim + kk] = flag;
+            if (inner_iters) inner_iters[s * k_sim + kk] = its;
+            if (xk) { xk[xs + 2 * kk + 2] = n0; xk[xs + 2 * kk + 3] = n1; }
+            if (dk) { dk[xs + 2 * kk + 2] = d0; dk[xs + 2 * kk + 3] = d1; }
+        }
+        x0 = n0;
+        x1 = n1;
+        NTM_WSYNC();
+        obs_model(w, km, d0, d1);
+    }
+}
+
 }  // namespace
 
 // Launchers of one horizon's one-wave-per-scenario kernels (grid of one 64-lane

@@ -416,4 +416,45 @@ __device__ __forceinline__ void scn_store(const Prob& pb, const W& w, int64_t gi
     }
 }
 
+// The observer kernels' workspace (k_mpc_step_obs / k_mpc_run_obs, ntm_step.h): the
+// runtime-N generator layout, plus the controller's model in lanes.  There the model is
+// no longer the plant: it may be the nominal plasma while the plant is the scenario's
+// (ntm_observer.nominal_model), and its offset C carries the disturbance estimate
+// (C + d_hat), so it needs a per-scenario C2 besides scn()'s three values.  Every lane of
+// a scenario's group holds the same four values (at P < 64 a wave runs several scenarios,
+// so they are vector registers); the LDS layout is WS<0, true, false>'s, untouched.
+// The lift and the rollout read their coefficients through scn_coef(pb, w) alone, so the
+// overload below is all it takes to run them on this model; every other workspace type
+// keeps the template above, and with it the code it had.
+struct WSObs : WS<0, true, false> {
+    double mC1, mC2, mbc, mwdep;
+};
+__device__ __forceinline__ Coef scn_coef(const Prob& pb, const WSObs& w) {
+    Coef k = pb.k;
+    k.C1 = w.mC1;
+    k.C2 = w.mC2;
+    k.bc = w.mbc;
+    k.wdep = w.mwdep;
+    return k;
+}
+// scenario gid's plant: the generator's plasma when a spread is attached (scn_store's
+// values: the same function on the same inputs), else the launch's
+__device__ __forceinline__ Coef plant_coef(const Prob& pb, int64_t gid) {
+    Coef k = pb.k;
+    if (gen_phys(pb)) {
+        Prob q = pb;
+        gen_apply_physics(q, gid);
+        k.C1 = q.k.C1;
+        k.bc = q.k.bc;
+        k.wdep = q.k.wdep;
+    }
+    return k;
+}
+// d_hat <- d_hat + gain (e - d_hat), as one fused multiply-add of the rounded difference
+// (include/ntm_mpc.h states it; fixed here so every implementation agrees bit for bit);
+// a component whose innovation is not finite keeps its estimate
+__device__ __forceinline__ double obs_update(double gain, double e, double d) {
+    return isfinite(e) ? fma(gain, e - d, d) : d;
+}
+
 }  // namespace ntm

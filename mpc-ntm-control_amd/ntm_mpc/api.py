@@ -121,6 +121,20 @@ class ScenarioGen:
                               float(self.wdep_spread))
 
 
+@dataclass
+class Observer:
+    """ntm_observer: plant-model mismatch and the offset-free disturbance estimate.
+    ``nominal_model``: the controller's model is this controller's Physics and the
+    generator's j_BS / w_dep spreads are the plant's alone (False: model = the
+    scenario's plasma, as step / run).  ``gain`` in [0, 1]: d_hat <- d_hat +
+    gain (e - d_hat) from the one-step prediction error e; 0 freezes d_hat."""
+    nominal_model: bool = False
+    gain: float = 0.0
+
+    def to_c(self) -> L.NtmObserver:
+        return L.NtmObserver(1 if self.nominal_model else 0, 0, float(self.gain))
+
+
 def scenario_sample(gen: ScenarioGen, B: int, k: int = 0) -> np.ndarray:
     """(B, 4) host-side samples of the generator for scenarios gen.first_id + s: j_BS
     factor, w_dep factor, n_w(k), n_omega(k) (ntm_scenario_sample; no GPU needed)."""
@@ -585,6 +599,105 @@ class NtmMpc:
         for staged, dst, src in ((rho_st, rho, rh), (uo_st, U_old, uo), (ws_st, active_ws, ws)):
             if staged:
                 dst[...] = src
+        return out
+
+    # ------------------------------------------------------------ plant-model mismatch, disturbance estimate
+    def step_obs(self, x_k: torch.Tensor, rho: torch.Tensor, U_old: torch.Tensor, d_hat: torch.Tensor,
+                 obs: Observer, cfg: Config | None = None, active_ws: torch.Tensor | None = None):
+        """step() with the observer (ntm_mpc_step_obs_device): the model is the nominal
+        plasma under ``obs.nominal_model`` and carries the disturbance estimate
+        ``d_hat`` (2, B), which is updated in place like ``rho`` and ``U_old`` and
+        also returned as ``d_hat`` in the dict.  Every horizon runs on the runtime-N
+        kernels here, as for step_dual."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x_k.shape[1]
+        xk, _ = _dev_arg(x_k, (2, Bn), name="x_k")
+        rh, rho_st = _dev_arg(rho, (3 * N, Bn), name="rho")
+        uo, uo_st = _dev_arg(U_old, (N, Bn), name="U_old")
+        dh, dh_st = _dev_arg(d_hat, (2, Bn), name="d_hat")
+        ws, ws_st = (None, False) if active_ws is None else _dev_arg(active_ws, (2 * (N + 1), Bn), torch.int32,
+                                                                     "active_ws")
+        out = {"U": self._empty(N, Bn), "x_pred": self._empty(2 * (N + 1), Bn), "x_next": self._empty(2, Bn),
+               "exitflag": self._empty(Bn, dtype=torch.int32), "inner_iters": self._empty(Bn, dtype=torch.int32)}
+        rc = self.lib.ntm_mpc_step_obs_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
+                                              C.byref(obs.to_c()), Bn, _ptr(xk), _ptr(rh), _ptr(uo), _ptr(dh),
+                                              _ptr(out["U"]), _ptr(out["x_pred"]), _ptr(out["x_next"]),
+                                              _ptr(out["exitflag"]), _ptr(out["inner_iters"]), _ptr(ws),
+                                              self._stream())
+        self._raise(rc, "ntm_mpc_step_obs_device")
+        for staged, dst, src in ((rho_st, rho, rh), (uo_st, U_old, uo), (dh_st, d_hat, dh), (ws_st, active_ws, ws)):
+            if staged:
+                dst.copy_(src)
+        out["d_hat"] = d_hat
+        return out
+
+    def step_obs_host(self, x_k: np.ndarray, rho: np.ndarray, U_old: np.ndarray, d_hat: np.ndarray, obs: Observer,
+                      cfg: Config | None = None, active_ws: np.ndarray | None = None):
+        """ntm_mpc_step_obs with host arrays (the MEX path): step_host with the observer;
+        ``d_hat`` (2, B) is updated in place and returned as ``d_hat``."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x_k.shape[1]
+        xk, _ = _host_arg(x_k, (2, Bn), name="x_k")
+        rh, rho_st = _host_arg(rho, (3 * N, Bn), name="rho")
+        uo, uo_st = _host_arg(U_old, (N, Bn), name="U_old")
+        dh, dh_st = _host_arg(d_hat, (2, Bn), name="d_hat")
+        ws, ws_st = (None, False) if active_ws is None else _host_arg(active_ws, (2 * (N + 1), Bn), np.int32,
+                                                                      "active_ws")
+        out = {"U": _host_empty(N, Bn), "x_pred": _host_empty(2 * (N + 1), Bn), "x_next": _host_empty(2, Bn),
+               "exitflag": np.empty(Bn, np.int32), "inner_iters": np.empty(Bn, np.int32)}
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))          # noqa: E731
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))           # noqa: E731
+        rc = self.lib.ntm_mpc_step_obs(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
+                                       C.byref(obs.to_c()), Bn, dp(xk), dp(rh), dp(uo), dp(dh), dp(out["U"]),
+                                       dp(out["x_pred"]), dp(out["x_next"]), ip(out["exitflag"]),
+                                       ip(out["inner_iters"]), None if ws is None else ip(ws))
+        self._raise(rc, "ntm_mpc_step_obs")
+        for staged, dst, src in ((rho_st, rho, rh), (uo_st, U_old, uo), (dh_st, d_hat, dh), (ws_st, active_ws, ws)):
+            if staged:
+                dst[...] = src
+        out["d_hat"] = d_hat
+        return out
+
+    def run_obs(self, x0: torch.Tensor, obs: Observer, k_sim: int = 20, cfg: Config | None = None,
+                d0: torch.Tensor | None = None):
+        """run() with the observer (ntm_mpc_run_obs_device), d_hat kept on chip.  ``d0``
+        (2, B) is the initial estimate (None: zeros).  Returns run()'s dict plus ``dk``
+        (2(k_sim+1), B): column 0 is d0, column k+1 the estimate after step k."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x0.shape[1]
+        x0, _ = _dev_arg(x0, (2, Bn), name="x0")
+        if d0 is not None:
+            d0, _ = _dev_arg(d0, (2, Bn), name="d0")
+        out = {"xk": self._empty(2 * (k_sim + 1), Bn), "uk": self._empty(k_sim, Bn), "Uk": self._empty(N * k_sim, Bn),
+               "wpred": self._empty((N + 1) * k_sim, Bn), "dk": self._empty(2 * (k_sim + 1), Bn),
+               "exitflag": self._empty(k_sim, Bn, dtype=torch.int32),
+               "inner_iters": self._empty(k_sim, Bn, dtype=torch.int32)}
+        rc = self.lib.ntm_mpc_run_obs_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
+                                             C.byref(obs.to_c()), Bn, k_sim, _ptr(x0), _ptr(d0), _ptr(out["xk"]),
+                                             _ptr(out["uk"]), _ptr(out["Uk"]), _ptr(out["wpred"]), _ptr(out["dk"]),
+                                             _ptr(out["exitflag"]), _ptr(out["inner_iters"]), self._stream())
+        self._raise(rc, "ntm_mpc_run_obs_device")
+        return out
+
+    def run_obs_host(self, x0: np.ndarray, obs: Observer, k_sim: int = 20, cfg: Config | None = None,
+                     d0: np.ndarray | None = None):
+        """ntm_mpc_run_obs with host arrays: run_host with the observer, plus ``dk``."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x0.shape[1]
+        x0, _ = _host_arg(x0, (2, Bn), name="x0")
+        if d0 is not None:
+            d0, _ = _host_arg(d0, (2, Bn), name="d0")
+        out = {"xk": _host_empty(2 * (k_sim + 1), Bn), "uk": _host_empty(k_sim, Bn),
+               "Uk": _host_empty(N * k_sim, Bn), "wpred": _host_empty((N + 1) * k_sim, Bn),
+               "dk": _host_empty(2 * (k_sim + 1), Bn),
+               "exitflag": _host_empty(k_sim, Bn, dtype=np.int32), "inner_iters": _host_empty(k_sim, Bn, dtype=np.int32)}
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))          # noqa: E731
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))           # noqa: E731
+        rc = self.lib.ntm_mpc_run_obs(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
+                                      C.byref(obs.to_c()), Bn, k_sim, dp(x0), None if d0 is None else dp(d0),
+                                      dp(out["xk"]), dp(out["uk"]), dp(out["Uk"]), dp(out["wpred"]), dp(out["dk"]),
+                                      ip(out["exitflag"]), ip(out["inner_iters"]))
+        self._raise(rc, "ntm_mpc_run_obs")
         return out
 
     def step_kkt(self, x_k: torch.Tensor, rho_qp: torch.Tensor, U: torch.Tensor, lam: torch.Tensor | None,
