@@ -37,7 +37,8 @@
 extern "C" {
 #endif
 
-#define NTM_MPC_ABI_VERSION 6   /* v6: ntm_observer, ntm_mpc_step_obs / run_obs (additive);
+#define NTM_MPC_ABI_VERSION 7   /* v7: ntm_estimator, ntm_mpc_step_est / run_est, ntm_meas_sample (additive);
+                                   v6: ntm_observer, ntm_mpc_step_obs / run_obs (additive);
                                    v5: ntm_config.Ru (input weight); v4: ntm_scenario_gen */
 #define NTM_MAX_N 64
 
@@ -404,6 +405,77 @@ int ntm_mpc_run_obs_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_conf
                            const double* x0, const double* d0, double* xk, double* uk,
                            double* Uk, double* wpred, double* dk, int32_t* exitflag,
                            int32_t* inner_iters, void* stream);
+
+/* ---- measurement noise and a filtered state estimate: output feedback (ABI v7) ---- */
+/* The observer entry points above plan from the plant's true state and correct d_hat
+ * from the true x_next.  Here the controller sees a noisy measurement only, and three
+ * values are carried per scenario: the plant's state x, the estimate x_hat[2] and d_hat[2].
+ * One step, per scenario (global id first_id + s, time index k = k0 of the attached
+ * generator, k0 + kk inside a run):
+ *   controller: the MPC step of ntm_mpc_step_obs (model k_m with C + d_hat in every LPV
+ *          iteration) FROM x_hat, not from x: U, x_pred, rho, U_old, the flag and the
+ *          iteration count, so the scheduling rho comes from the estimate;
+ *   plant  x_next = plant step of k_p at (x, U[0]) plus the generator's disturbance,
+ *          exactly as ntm_mpc_step_obs.  It never sees x_hat, d_hat or the measurement noise;
+ *   y[i]   = x_next[i] + sigma_y[i] n(seed, id, k, 2 + i): the generator's next two
+ *          normal channels (sub-channels 8..15; ntm_meas_sample returns them).  The term
+ *          is skipped when sigma_y[i] == 0, as a zero sigma_w is;
+ *   m      = k_m's one-step map WITHOUT d_hat and without disturbance at (x_hat, U[0])
+ *          from rho(x_hat);
+ *   iota[i] = (y[i] - m[i]) - d_hat[i], with the old d_hat;
+ *   d_hat[i] <- fma(gain[i], (y[i] - m[i]) - d_hat[i], d_hat[i]), kept where y[i] - m[i]
+ *          is not finite (ntm_observer's update);
+ *   x_hat[i] <- fma(-kappa[i], iota[i], y[i]), one rounding: (1 - kappa) y + kappa (m +
+ *          d_hat).  Where iota[i] is not finite, x_hat[i] <- y[i].
+ * With sigma_y = 0, kappa = 0, gain[0] == gain[1] and x_hat == x on input the step is
+ * ntm_mpc_step_obs's bit for bit and x_hat comes out equal to x_next.  Every horizon runs
+ * on the runtime-N kernels.  The literal switches D4, D6 and D13 return
+ * NTM_E_UNSUPPORTED; NTM_RHO1_SQUARED is allowed.  NTM_E_INVALID: NULL est, x_hat or
+ * d_hat, reserved != 0, a gain or kappa outside [0, 1] or NaN, a sigma_y negative or not
+ * finite, sigma_y != 0 with no generator attached (there is then no seed; a generator
+ * with all-zero sigmas and spreads is enough). */
+typedef struct {
+    int32_t nominal_model;  /* as ntm_observer                                            */
+    int32_t reserved;       /* must be 0                                                  */
+    double  gain[2];        /* d_hat gain per component (w, omega), in [0, 1]             */
+    double  kappa[2];       /* trust in the model per component, in [0, 1]: 0 = x_hat is
+                               the measurement                                            */
+    double  sigma_y[2];     /* measurement noise std: w [m], omega [rad/s]; finite, >= 0  */
+} ntm_estimator;
+/* ntm_mpc_step_obs with the estimator.  x_k[2] per scenario is the plant's true state
+ * (input); x_hat[2] per scenario is required, in/out, and must not overlap x_k; y[2] per
+ * scenario is the measurement of x_next (output, may be NULL). */
+int ntm_mpc_step_est(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg,
+                     const ntm_estimator* est, int64_t B, const double* x_k, double* rho,
+                     double* U_old, double* d_hat, double* x_hat, double* U, double* x_pred,
+                     double* x_next, double* y, int32_t* exitflag, int32_t* inner_iters,
+                     int32_t* active_ws);
+int ntm_mpc_step_est_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg,
+                            const ntm_estimator* est, int64_t B, const double* x_k,
+                            double* rho, double* U_old, double* d_hat, double* x_hat,
+                            double* U, double* x_pred, double* x_next, double* y,
+                            int32_t* exitflag, int32_t* inner_iters, int32_t* active_ws,
+                            void* stream);
+/* ntm_mpc_run_obs with the estimator; x, x_hat and d_hat stay on chip across the k_sim
+ * steps.  xhat0[2] per scenario is the initial estimate (NULL: x0).  xhk[2(k_sim+1)] per
+ * scenario (may be NULL): column 0 is the initial estimate, column k+1 the estimate after
+ * step k.  yk[2 k_sim] per scenario (may be NULL): column k is the measurement of step
+ * k's x_next.  The initial Rho = repmat(rho(xhat0)) comes from the model. */
+int ntm_mpc_run_est(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg,
+                    const ntm_estimator* est, int64_t B, int32_t k_sim, const double* x0,
+                    const double* d0, const double* xhat0, double* xk, double* uk,
+                    double* Uk, double* wpred, double* dk, double* xhk, double* yk,
+                    int32_t* exitflag, int32_t* inner_iters);
+int ntm_mpc_run_est_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg,
+                           const ntm_estimator* est, int64_t B, int32_t k_sim,
+                           const double* x0, const double* d0, const double* xhat0,
+                           double* xk, double* uk, double* Uk, double* wpred, double* dk,
+                           double* xhk, double* yk, int32_t* exitflag,
+                           int32_t* inner_iters, void* stream);
+/* Host-side unit samples of the measurement noise for scenarios first_id .. first_id + B
+ * - 1 at time index k (out2: 2 per scenario: n(id, k, 2), n(id, k, 3)); the sibling of
+ * ntm_scenario_sample, the same code the kernels run. */
+void ntm_meas_sample(const ntm_scenario_gen* gen, int64_t B, int32_t k, double* out2);
 
 #ifdef __cplusplus
 }

@@ -43,6 +43,20 @@
  *       'run' with the observer (ntm_mpc_run_obs): d0 2-by-B the initial estimate
  *       (omitted: zeros); dk 2(k_sim+1)-by-B, column 1 of each scenario's
  *       2-by-(k_sim+1) history is d0, column k+1 the estimate after step k.
+ *   [U, x_pred, x_next, exitflag, iters, rho, Uold, ws, d_hat, x_hat, y] = ...
+ *       ntm_mpc_mex('step_est', x_k, rho, Uold, d_hat, x_hat, est[, cfg[, ws]])
+ *       'step_obs' with output feedback (ntm_mpc_step_est, ABI v7): the controller
+ *       plans from the estimate x_hat 2-by-B while the plant steps from its true
+ *       state x_k; est is a struct with any of nominal_model, gain, kappa, sigma_y
+ *       (ntm_estimator; the last three [w omega] pairs, a scalar sets both, missing
+ *       fields are 0).  d_hat and x_hat come back updated as outputs 9 and 10, y
+ *       2-by-B is the noisy measurement of x_next.  sigma_y ~= 0 needs 'scenarios'
+ *       (any gen struct, all zeros included) for the seed.
+ *   [xk, uk, Uk, wpred, exitflag, iters, dk, xhk, yk] = ...
+ *       ntm_mpc_mex('run_est', x0, k_sim, est[, cfg[, d0[, xhat0]]])
+ *       'run_obs' with the estimator (ntm_mpc_run_est): d0 and xhat0 2-by-B
+ *       (omitted or []: zeros, x0); xhk 2(k_sim+1)-by-B, the estimate's history
+ *       from xhat0 on; yk 2 k_sim-by-B, the measurements.
  *   ntm_mpc_mex('scenarios', gen)                               
  *       gen struct with any of seed, first_id, k0, sigma_w, sigma_omega,
  *       jbs_spread, wdep_spread (ntm_scenario_gen): per-scenario plasma and
@@ -301,6 +315,116 @@ static void do_run_obs(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[
     }
 }
 
+/* est struct with any of nominal_model, gain, kappa, sigma_y (ntm_estimator); the last
+ * three are [w omega] pairs, a scalar sets both components; missing fields are 0 */
+static void pair_field(const mxArray* s, const char* name, double* dst) {
+    const mxArray* f = mxGetField(s, 0, name);
+    dst[0] = dst[1] = 0.0;
+    if (!f) return;
+    const size_t n = mxIsDouble(f) ? mxGetNumberOfElements(f) : 0;
+    if (n != 1 && n != 2) mexErrMsgIdAndTxt("ntm:arg", "est.%s must have 1 or 2 doubles", name);
+    dst[0] = mxGetDoubles(f)[0];
+    dst[1] = mxGetDoubles(f)[n - 1];
+}
+
+static ntm_estimator read_est(const mxArray* s) {
+    ntm_estimator e;
+    if (!s || !mxIsStruct(s))
+        mexErrMsgIdAndTxt("ntm:arg", "est must be a struct with nominal_model, gain, kappa and sigma_y");
+    memset(&e, 0, sizeof e);
+    e.nominal_model = scalar_field(s, "nominal_model", 0.0) != 0.0;
+    pair_field(s, "gain", e.gain);
+    pair_field(s, "kappa", e.kappa);
+    pair_field(s, "sigma_y", e.sigma_y);
+    return e;
+}
+
+/* 'step_obs' with the estimator (ntm_mpc_step_est): x_hat goes in after d_hat; d_hat,
+ * x_hat and the measurement y are outputs 9 to 11 */
+static void do_step_est(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    if (nrhs < 7)
+        mexErrMsgIdAndTxt("ntm:arg", "usage: ntm_mpc_mex('step_est', x_k, rho, Uold, d_hat, x_hat, est[, cfg[, ws]])");
+    const ntm_estimator e = read_est(prhs[6]);
+    const ntm_config c = read_cfg(nrhs > 7 ? prhs[7] : NULL);
+    ntm_physics p;
+    ntm_physics_default(&p);
+    const size_t B = mxGetN(prhs[1]), N = (size_t)c.N;
+    const double* x = in_matrix(prhs[1], 2, B, "x_k");
+    in_matrix(prhs[2], 3 * N, B, "rho");
+    in_matrix(prhs[3], N, B, "Uold");
+    in_matrix(prhs[4], 2, B, "d_hat");
+    in_matrix(prhs[5], 2, B, "x_hat");
+    mxArray* rho = mxDuplicateArray(prhs[2]);
+    mxArray* uold = mxDuplicateArray(prhs[3]);
+    mxArray* dh = mxDuplicateArray(prhs[4]);
+    mxArray* xh = mxDuplicateArray(prhs[5]);
+    mxArray* U = mxCreateDoubleMatrix(N, B, mxREAL);
+    mxArray* xp = mxCreateDoubleMatrix(2 * (N + 1), B, mxREAL);
+    mxArray* xn = mxCreateDoubleMatrix(2, B, mxREAL);
+    mxArray* y = mxCreateDoubleMatrix(2, B, mxREAL);
+    mxArray* fl = mxCreateNumericMatrix(1, B, mxINT32_CLASS, mxREAL);
+    mxArray* it = mxCreateNumericMatrix(1, B, mxINT32_CLASS, mxREAL);
+    mxArray* ws = NULL;
+    if (nrhs > 8) {
+        const mxArray* w = prhs[8];
+        if (!mxIsInt32(w) || mxGetM(w) != 2 * (N + 1) || mxGetN(w) != B)
+            mexErrMsgIdAndTxt("ntm:arg", "ws must be an int32 %d-by-%d array", (int)(2 * (N + 1)), (int)B);
+        ws = mxDuplicateArray(w);
+    } else {
+        ws = mxCreateNumericMatrix(2 * (N + 1), B, mxINT32_CLASS, mxREAL);
+        int32_t* wp = mxGetInt32s(ws);
+        for (size_t i = 0; i < B * 2 * (N + 1); ++i) wp[i] = -1;
+    }
+    check(ntm_mpc_step_est(ctx(), &p, &c, &e, (int64_t)B, x, mxGetDoubles(rho), mxGetDoubles(uold), mxGetDoubles(dh),
+                           mxGetDoubles(xh), mxGetDoubles(U), mxGetDoubles(xp), mxGetDoubles(xn), mxGetDoubles(y),
+                           mxGetInt32s(fl), mxGetInt32s(it), mxGetInt32s(ws)),
+          "ntm_mpc_step_est");
+    mxArray* outs[11] = {U, xp, xn, fl, it, rho, uold, ws, dh, xh, y};
+    for (int i = 0; i < 11; ++i) {
+        if (i < (nlhs > 0 ? nlhs : 1)) plhs[i] = outs[i];
+        else mxDestroyArray(outs[i]);
+    }
+}
+
+/* an optional 2-by-B input: omitted or [] gives NULL */
+static const double* opt_matrix(int nrhs, const mxArray* prhs[], int i, size_t B, const char* name) {
+    if (nrhs <= i || (mxIsDouble(prhs[i]) && mxGetNumberOfElements(prhs[i]) == 0)) return NULL;
+    return in_matrix(prhs[i], 2, B, name);
+}
+
+/* 'run_obs' with the estimator (ntm_mpc_run_est): dk, xhk and yk are outputs 7 to 9 */
+static void do_run_est(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    if (nrhs < 4) mexErrMsgIdAndTxt("ntm:arg", "usage: ntm_mpc_mex('run_est', x0, k_sim, est[, cfg[, d0[, xhat0]]])");
+    const ntm_estimator e = read_est(prhs[3]);
+    const ntm_config c = read_cfg(nrhs > 4 ? prhs[4] : NULL);
+    ntm_physics p;
+    ntm_physics_default(&p);
+    const size_t B = mxGetN(prhs[1]), N = (size_t)c.N;
+    const double* x0 = in_matrix(prhs[1], 2, B, "x0");
+    const double* d0 = opt_matrix(nrhs, prhs, 5, B, "d0");
+    const double* h0 = opt_matrix(nrhs, prhs, 6, B, "xhat0");
+    const int k = (int)mxGetScalar(prhs[2]);
+    if (k < 1) mexErrMsgIdAndTxt("ntm:arg", "k_sim must be >= 1");
+    mxArray* xk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
+    mxArray* uk = mxCreateDoubleMatrix((size_t)k, B, mxREAL);
+    mxArray* Uk = mxCreateDoubleMatrix(N * (size_t)k, B, mxREAL);
+    mxArray* wp = mxCreateDoubleMatrix((N + 1) * (size_t)k, B, mxREAL);
+    mxArray* fl = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
+    mxArray* it = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
+    mxArray* dk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
+    mxArray* xhk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
+    mxArray* yk = mxCreateDoubleMatrix(2 * (size_t)k, B, mxREAL);
+    check(ntm_mpc_run_est(ctx(), &p, &c, &e, (int64_t)B, k, x0, d0, h0, mxGetDoubles(xk), mxGetDoubles(uk),
+                          mxGetDoubles(Uk), mxGetDoubles(wp), mxGetDoubles(dk), mxGetDoubles(xhk), mxGetDoubles(yk),
+                          mxGetInt32s(fl), mxGetInt32s(it)),
+          "ntm_mpc_run_est");
+    mxArray* outs[9] = {xk, uk, Uk, wp, fl, it, dk, xhk, yk};
+    for (int i = 0; i < 9; ++i) {
+        if (i < (nlhs > 0 ? nlhs : 1)) plhs[i] = outs[i];
+        else mxDestroyArray(outs[i]);
+    }
+}
+
 static void do_scenarios(int nrhs, const mxArray* prhs[]) {
     if (nrhs < 2 || (mxIsDouble(prhs[1]) && mxGetNumberOfElements(prhs[1]) == 0)) {
         check(ntm_ctx_set_scenarios(ctx(), NULL), "ntm_ctx_set_scenarios");
@@ -330,6 +454,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     else if (!strcmp(cmd, "run")) do_run(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "step_obs")) do_step_obs(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "run_obs")) do_run_obs(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "step_est")) do_step_est(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "run_est")) do_run_est(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "scenarios")) do_scenarios(nrhs, prhs);
     else if (!strcmp(cmd, "close")) release();
     else mexErrMsgIdAndTxt("ntm:arg", "unknown command '%s'", cmd);

@@ -804,6 +804,60 @@ int validate_obs(ntm_ctx* ctx, const ntm_config* c, const ntm_observer* obs) {
         return fail(ctx, NTM_E_UNSUPPORTED, "observer: the literal D4 / D6 / D13 switches are not supported");
     return NTM_OK;
 }
+EstOpt est_opt(const ntm_estimator* est) {
+    EstOpt eo;
+    eo.nominal = est->nominal_model != 0;
+    eo.pad = 0;
+    for (int i = 0; i < 2; ++i) {
+        eo.gain[i] = est->gain[i];
+        eo.kappa[i] = est->kappa[i];
+        eo.sy[i] = est->sigma_y[i];
+    }
+    return eo;
+}
+template <int P>
+int launch_step_est(ntm_ctx* ctx, const Prob& pb, int64_t B, const double* x_k, double* rho, double* U_old, double* U,
+                    double* x_pred, double* x_next, int32_t* exitflag, int32_t* inner_iters, int32_t* active_ws,
+                    double* d_hat, double* x_hat, double* y, const ntm_estimator* est, hipStream_t st) {
+    constexpr int G = 64 / P;
+    const size_t lds = (size_t)G * ws_bytes(pb.N, false);
+    if (int rc = set_lds(ctx, k_mpc_step_est<P>, lds)) return rc;
+    const int64_t blocks = (B + G - 1) / G;
+    hipLaunchKernelGGL((k_mpc_step_est<P>), dim3((unsigned)blocks), dim3(64), lds, st, pb, B, x_k, rho, U_old, U,
+                       x_pred, x_next, exitflag, inner_iters, active_ws, d_hat, x_hat, y, est_opt(est));
+    return check_hip(ctx, hipGetLastError(), "k_mpc_step_est launch");
+}
+template <int P>
+int launch_run_est(ntm_ctx* ctx, const Prob& pb, int64_t B, int k_sim, const double* x0, const double* d0,
+                   const double* xhat0, double* xk, double* uk, double* Uk, double* wpred, double* dk, double* xhk,
+                   double* yk, int32_t* exitflag, int32_t* inner_iters, const ntm_estimator* est, hipStream_t st) {
+    constexpr int G = 64 / P;
+    const size_t lds = (size_t)G * ws_bytes(pb.N, false);
+    if (int rc = set_lds(ctx, k_mpc_run_est<P>, lds)) return rc;
+    const int64_t blocks = (B + G - 1) / G;
+    hipLaunchKernelGGL((k_mpc_run_est<P>), dim3((unsigned)blocks), dim3(64), lds, st, pb, B, k_sim, x0, d0, xhat0, xk,
+                       uk, Uk, wpred, dk, xhk, yk, exitflag, inner_iters, est_opt(est));
+    return check_hip(ctx, hipGetLastError(), "k_mpc_run_est launch");
+}
+// the estimator entry points' own checks (after validate): the options, the literal
+// switches the observer entry points refuse too, and a seed for the measurement noise
+int validate_est(ntm_ctx* ctx, const ntm_config* c, const ntm_estimator* est) {
+    if (!est) return fail(ctx, NTM_E_INVALID, "null estimator");
+    if (est->reserved != 0) return fail(ctx, NTM_E_INVALID, "estimator: reserved must be 0");
+    for (int i = 0; i < 2; ++i) {
+        if (!(est->gain[i] >= 0.0 && est->gain[i] <= 1.0))
+            return fail(ctx, NTM_E_INVALID, "estimator: gain must be in [0, 1]");
+        if (!(est->kappa[i] >= 0.0 && est->kappa[i] <= 1.0))
+            return fail(ctx, NTM_E_INVALID, "estimator: kappa must be in [0, 1]");
+        if (!std::isfinite(est->sigma_y[i]) || est->sigma_y[i] < 0.0)
+            return fail(ctx, NTM_E_INVALID, "estimator: sigma_y must be finite and >= 0");
+    }
+    if ((est->sigma_y[0] != 0.0 || est->sigma_y[1] != 0.0) && !ctx->gen_on)
+        return fail(ctx, NTM_E_INVALID, "estimator: sigma_y != 0 needs a generator (ntm_ctx_set_scenarios) for its seed");
+    if (c->flags & (NTM_LITERAL_PHI_RIGHTMUL | NTM_LITERAL_GAMMA_INDEX | NTM_LITERAL_PLANT_NO_C))
+        return fail(ctx, NTM_E_UNSUPPORTED, "estimator: the literal D4 / D6 / D13 switches are not supported");
+    return NTM_OK;
+}
 int rows_of(const ntm_config* c) {
     return c->mode == NTM_MODE_NONE ? 0
            : c->mode == NTM_MODE_BOX ? 2 * c->N
@@ -1004,6 +1058,15 @@ void ntm_scenario_sample(const ntm_scenario_gen* gen, int64_t B, int32_t k, doub
         out4[4 * s + 1] = gen_factor(gen->seed, id, 1, gen->wdep_spread);
         out4[4 * s + 2] = gen_normal(gen->seed, id, (uint32_t)k, 0);
         out4[4 * s + 3] = gen_normal(gen->seed, id, (uint32_t)k, 1);
+    }
+}
+
+void ntm_meas_sample(const ntm_scenario_gen* gen, int64_t B, int32_t k, double* out2) {
+    // the measurement noise's unit samples: the generator's normal channels 2 and 3
+    for (int64_t s = 0; s < B; ++s) {
+        const int64_t id = gen->first_id + s;
+        out2[2 * s] = gen_normal(gen->seed, id, (uint32_t)k, 2);
+        out2[2 * s + 1] = gen_normal(gen->seed, id, (uint32_t)k, 3);
     }
 }
 
@@ -1233,6 +1296,161 @@ int ntm_mpc_run_obs(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg
         {xk, dxk, 2 * (size_t)(k_sim + 1) * B * 8}, {uk, duk, (size_t)k_sim * B * 8},
         {Uk, dUk, (size_t)N * k_sim * B * 8},        {wpred, dwp, (size_t)(N + 1) * k_sim * B * 8},
         {dk, ddk, 2 * (size_t)(k_sim + 1) * B * 8}, {exitflag, dfl, (size_t)k_sim * B * 4},
+        {inner_iters, dit, (size_t)k_sim * B * 4}};
+    for (auto& o : outs)
+        if (o.h && o.n && (rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H")))
+            return rc;
+    return check_hip(ctx, hipStreamSynchronize(st), "sync");
+}
+
+int ntm_mpc_step_est_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est,
+                            int64_t B, const double* x_k, double* rho, double* U_old, double* d_hat, double* x_hat,
+                            double* U, double* x_pred, double* x_next, double* y, int32_t* exitflag,
+                            int32_t* inner_iters, int32_t* active_ws, void* stream) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B);
+    if (rc) return rc;
+    if ((rc = validate_est(ctx, cfg, est))) return rc;
+    if (!d_hat) return fail(ctx, NTM_E_INVALID, "null d_hat");
+    if (!x_hat) return fail(ctx, NTM_E_INVALID, "null x_hat");
+    if (B == 0) return NTM_OK;
+    if (!x_k || !rho || !U_old || !U || !x_pred || !x_next || !exitflag || !inner_iters)
+        return fail(ctx, NTM_E_INVALID, "null array");
+    Prob pb = make_prob(phys, cfg);
+    pb.stats = ctx->stats;
+    if (ctx->gen_on) attach_gen(ctx->gen, phys, cfg, pb);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // every horizon on the runtime-N kernels (the estimator is compiled into those only)
+    const int P = lanes_for(cfg->N);
+#define CALL(P_)                                                                                                  \
+    launch_step_est<P_>(ctx, pb, B, x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters, active_ws, d_hat, \
+                        x_hat, y, est, st)
+    return P == 16 ? CALL(16) : (P == 32 ? CALL(32) : CALL(64));
+#undef CALL
+}
+
+int ntm_mpc_step_est(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est, int64_t B,
+                     const double* x_k, double* rho, double* U_old, double* d_hat, double* x_hat, double* U,
+                     double* x_pred, double* x_next, double* y, int32_t* exitflag, int32_t* inner_iters,
+                     int32_t* active_ws) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B);
+    if (rc) return rc;
+    if ((rc = validate_est(ctx, cfg, est))) return rc;
+    if (!d_hat) return fail(ctx, NTM_E_INVALID, "null d_hat");
+    if (!x_hat) return fail(ctx, NTM_E_INVALID, "null x_hat");
+    if (B == 0) return NTM_OK;
+    if (!x_k || !rho || !U_old || !U || !x_pred || !x_next || !exitflag || !inner_iters)
+        return fail(ctx, NTM_E_INVALID, "null array");
+    const int N = cfg->N;
+    size_t bx = al(2 * B * 8), brho = al(3 * N * B * 8), bu = al(N * B * 8), bxp = al(2 * (N + 1) * B * 8),
+           bi = al(B * 4), bws = active_ws ? al(2 * (N + 1) * B * 4) : 0;
+    rc = ensure_buf(ctx, bx * 5 + brho + bu * 2 + bxp + bi * 2 + bws);
+    if (rc) return rc;
+    char* p = static_cast<char*>(ctx->dbuf);
+    double* dx = (double*)p; p += bx;
+    double* drho = (double*)p; p += brho;
+    double* duo = (double*)p; p += bu;
+    double* dU = (double*)p; p += bu;
+    double* dxp = (double*)p; p += bxp;
+    double* dxn = (double*)p; p += bx;
+    double* ddh = (double*)p; p += bx;
+    double* dxh = (double*)p; p += bx;
+    double* dy = (double*)p; p += bx;
+    int32_t* dfl = (int32_t*)p; p += bi;
+    int32_t* dit = (int32_t*)p; p += bi;
+    int32_t* dws = active_ws ? (int32_t*)p : nullptr;
+    hipStream_t st = ctx->stream;
+    const size_t wsb = 2 * (size_t)(N + 1) * B * 4;
+    if ((rc = check_hip(ctx, hipMemcpyAsync(dx, x_k, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
+    if ((rc = check_hip(ctx, hipMemcpyAsync(drho, rho, 3 * N * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
+    if ((rc = check_hip(ctx, hipMemcpyAsync(duo, U_old, N * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
+    if ((rc = check_hip(ctx, hipMemcpyAsync(ddh, d_hat, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
+    if ((rc = check_hip(ctx, hipMemcpyAsync(dxh, x_hat, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
+    if (dws && (rc = check_hip(ctx, hipMemcpyAsync(dws, active_ws, wsb, hipMemcpyHostToDevice, st), "H2D")))
+        return rc;
+    rc = ntm_mpc_step_est_device(ctx, phys, cfg, est, B, dx, drho, duo, ddh, dxh, dU, dxp, dxn, y ? dy : nullptr, dfl,
+                                 dit, dws, st);
+    if (rc) return rc;
+    struct { void* h; const void* d; size_t n; } outs[] = {
+        {rho, drho, (size_t)3 * N * B * 8}, {U_old, duo, (size_t)N * B * 8}, {d_hat, ddh, (size_t)2 * B * 8},
+        {x_hat, dxh, (size_t)2 * B * 8}, {U, dU, (size_t)N * B * 8}, {x_pred, dxp, (size_t)2 * (N + 1) * B * 8},
+        {x_next, dxn, (size_t)2 * B * 8}, {y, dy, (size_t)2 * B * 8}, {exitflag, dfl, (size_t)B * 4},
+        {inner_iters, dit, (size_t)B * 4}, {active_ws, dws, wsb}};
+    for (auto& o : outs)
+        if (o.h && o.d && o.n && (rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H")))
+            return rc;
+    return check_hip(ctx, hipStreamSynchronize(st), "sync");
+}
+
+int ntm_mpc_run_est_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est,
+                           int64_t B, int32_t k_sim, const double* x0, const double* d0, const double* xhat0,
+                           double* xk, double* uk, double* Uk, double* wpred, double* dk, double* xhk, double* yk,
+                           int32_t* exitflag, int32_t* inner_iters, void* stream) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B);
+    if (rc) return rc;
+    if ((rc = validate_est(ctx, cfg, est))) return rc;
+    if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
+    if (B == 0) return NTM_OK;
+    if (!x0) return fail(ctx, NTM_E_INVALID, "null x0");
+    Prob pb = make_prob(phys, cfg);
+    pb.stats = ctx->stats;
+    if (ctx->gen_on) attach_gen(ctx->gen, phys, cfg, pb);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int P = lanes_for(cfg->N);
+#define CALL(P_)                                                                                              \
+    launch_run_est<P_>(ctx, pb, B, k_sim, x0, d0, xhat0, xk, uk, Uk, wpred, dk, xhk, yk, exitflag, inner_iters, \
+                       est, st)
+    return P == 16 ? CALL(16) : (P == 32 ? CALL(32) : CALL(64));
+#undef CALL
+}
+
+int ntm_mpc_run_est(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est, int64_t B,
+                    int32_t k_sim, const double* x0, const double* d0, const double* xhat0, double* xk, double* uk,
+                    double* Uk, double* wpred, double* dk, double* xhk, double* yk, int32_t* exitflag,
+                    int32_t* inner_iters) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B);
+    if (rc) return rc;
+    if ((rc = validate_est(ctx, cfg, est))) return rc;
+    if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
+    if (B == 0) return NTM_OK;
+    if (!x0) return fail(ctx, NTM_E_INVALID, "null x0");
+    const int N = cfg->N;
+    size_t b0 = al(2 * B * 8), bxk = al(2 * (size_t)(k_sim + 1) * B * 8), buk = al((size_t)k_sim * B * 8),
+           bUk = al((size_t)N * k_sim * B * 8), bwp = al((size_t)(N + 1) * k_sim * B * 8),
+           byk = al(2 * (size_t)k_sim * B * 8), bi = al((size_t)k_sim * B * 4);
+    rc = ensure_buf(ctx, 3 * b0 + 3 * bxk + buk + bUk + bwp + byk + 2 * bi);
+    if (rc) return rc;
+    char* p = static_cast<char*>(ctx->dbuf);
+    double* dx0 = (double*)p; p += b0;
+    double* dd0 = (double*)p; p += b0;
+    double* dh0 = (double*)p; p += b0;
+    double* dxk = (double*)p; p += bxk;
+    double* ddk = (double*)p; p += bxk;
+    double* dxhk = (double*)p; p += bxk;
+    double* duk = (double*)p; p += buk;
+    double* dUk = (double*)p; p += bUk;
+    double* dwp = (double*)p; p += bwp;
+    double* dyk = (double*)p; p += byk;
+    int32_t* dfl = (int32_t*)p; p += bi;
+    int32_t* dit = (int32_t*)p;
+    hipStream_t st = ctx->stream;
+    if ((rc = check_hip(ctx, hipMemcpyAsync(dx0, x0, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
+    if (d0 && (rc = check_hip(ctx, hipMemcpyAsync(dd0, d0, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
+    if (xhat0 && (rc = check_hip(ctx, hipMemcpyAsync(dh0, xhat0, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D")))
+        return rc;
+    rc = ntm_mpc_run_est_device(ctx, phys, cfg, est, B, k_sim, dx0, d0 ? dd0 : nullptr, xhat0 ? dh0 : nullptr,
+                                xk ? dxk : nullptr, uk ? duk : nullptr, Uk ? dUk : nullptr, wpred ? dwp : nullptr,
+                                dk ? ddk : nullptr, xhk ? dxhk : nullptr, yk ? dyk : nullptr,
+                                exitflag ? dfl : nullptr, inner_iters ? dit : nullptr, st);
+    if (rc) return rc;
+    struct { void* h; void* d; size_t n; } outs[] = {
+        {xk, dxk, 2 * (size_t)(k_sim + 1) * B * 8},  {uk, duk, (size_t)k_sim * B * 8},
+        {Uk, dUk, (size_t)N * k_sim * B * 8},         {wpred, dwp, (size_t)(N + 1) * k_sim * B * 8},
+        {dk, ddk, 2 * (size_t)(k_sim + 1) * B * 8},  {xhk, dxhk, 2 * (size_t)(k_sim + 1) * B * 8},
+        {yk, dyk, 2 * (size_t)k_sim * B * 8},         {exitflag, dfl, (size_t)k_sim * B * 4},
         {inner_iters, dit, (size_t)k_sim * B * 4}};
     for (auto& o : outs)
         if (o.h && o.n && (rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H")))

@@ -505,6 +505,142 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_run
     }
 }
 
+// Output feedback (ntm_mpc_step_est / ntm_mpc_run_est): the observer kernels with a
+// noisy measurement and a fixed-gain state filter.  Three values are carried per
+// scenario: the plant's state x, the estimate x_hat and d_hat.
+//   controller: the observer step (model k_m, C + d_hat) planned FROM x_hat;
+//   plant  x_next = k_p's step at (x, U[0]) + disturbance; it never sees x_hat, d_hat
+//          or the measurement noise;
+//   y      = x_next + sy n(gid, k, 2 + i)                            (est_measure);
+//   m      = k_m's one-step map at (x_hat, U[0]) from rho(x_hat), without d_hat;
+//   d_hat, x_hat <- est_update(gain, kappa, y, m, ...).
+// With sy = 0, kappa = 0, gain[0] == gain[1] and x_hat == x this is k_mpc_step_obs's
+// step bit for bit (x_hat = y = x_next): the plant step and the model's map are the same
+// calls on the same values, and model_step keeps them apart for the compiler.
+template <int P>
+__global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_step_est(
+    Prob pb, int64_t B, const double* __restrict__ x_k, double* __restrict__ rho, double* __restrict__ U_old,
+    double* __restrict__ U, double* __restrict__ x_pred, double* __restrict__ x_next, int32_t* __restrict__ exitflag,
+    int32_t* __restrict__ inner_iters, int32_t* __restrict__ active_ws, double* __restrict__ d_hat,
+    double* __restrict__ x_hat, double* __restrict__ y, EstOpt eo) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int G = 64 / P;
+    const int g = threadIdx.x / P, l = threadIdx.x % P;
+    const int64_t s = xcd_swizzle(blockIdx.x, gridDim.x) * G + g;
+    const int N = pb.N;
+    if (s >= B) return;
+    WSObs w = ws_carve_obs(smem + g * ws_bytes(N, false), N);
+    const double x0 = x_k[2 * s], x1 = x_k[2 * s + 1];
+    const double h0 = x_hat[2 * s], h1 = x_hat[2 * s + 1];
+    double d0 = d_hat[2 * s], d1 = d_hat[2 * s + 1];
+    const int64_t gid = pb.g.first_id + s;
+    const Coef kp = plant_coef(pb, gid);
+    const Coef km = eo.nominal ? pb.k : kp;
+    obs_model(w, km, d0, d1);
+    if (active_ws) {
+        load_candidates<P>(pb, w, B, s, active_ws, l);
+    } else if (l < 2) {
+        w.cand()[l * (N + 1) + N] = -1;
+    }
+    load_state<P>(w, B, s, rho, U_old, l);
+    int its;
+    int flag = mpc_step_dev<P>(pb, w, h0, h1, l, &its, B, s);
+    store_record<P>(rho + s * (3 * N), w.rho(), 3 * N, l);
+    store_record<P>(U_old + s * N, w.Uold(), N, l);
+    store_record<P>(U + s * N, w.U(), N, l);
+    store_record<P>(x_pred + s * (2 * (N + 1)), w.xp(), 2 * (N + 1), l);
+    {
+        const double u0 = w.U()[0];
+        double n0, n1, m0, m1, e0, e1;
+        plant_step<true>(pb, kp, x0, x1, u0, n0, n1, gid, pb.g.k0);
+        model_step(pb, km, h0, h1, u0, m0, m1);
+        const double y0 = est_measure(pb, eo.sy[0], n0, gid, pb.g.k0, 2);
+        const double y1 = est_measure(pb, eo.sy[1], n1, gid, pb.g.k0, 3);
+        est_update(eo.gain[0], eo.kappa[0], y0, m0, d0, e0);
+        est_update(eo.gain[1], eo.kappa[1], y1, m1, d1, e1);
+        if (l < 2) {
+            x_next[2 * s + l] = l ? n1 : n0;
+            d_hat[2 * s + l] = l ? d1 : d0;
+            x_hat[2 * s + l] = l ? e1 : e0;
+            if (y) y[2 * s + l] = l ? y1 : y0;
+        }
+    }
+    if (l == 0) {
+        exitflag[s] = flag;
+        inner_iters[s] = its;
+    }
+    if (active_ws)
+        for (int e = l; e < 2 * (N + 1); e += P) active_ws[s * (2 * (N + 1)) + e] = w.cand()[e];
+}
+
+// k_mpc_run_obs with the measurement and the filter, x, x_hat and d_hat carried on chip:
+// h0v (2 per scenario, null: x0), xhk (2(k_sim+1) per scenario, may be null): column 0
+// the initial estimate, column k+1 the estimate after step k; yk (2 k_sim per scenario,
+// may be null): the measurement of step k.  Rho = repmat(rho(x_hat0)) comes from the model.
+template <int P>
+__global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_run_est(
+    Prob pb, int64_t B, int k_sim, const double* __restrict__ x0v, const double* __restrict__ d0v,
+    const double* __restrict__ h0v, double* xk, double* uk, double* Uk, double* wpred, double* dk, double* xhk,
+    double* yk, int32_t* exitflag, int32_t* inner_iters, EstOpt eo) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int G = 64 / P;
+    const int g = threadIdx.x / P, l = threadIdx.x % P;
+    const int64_t s = xcd_swizzle(blockIdx.x, gridDim.x) * G + g;
+    const int N = pb.N;
+    if (s >= B) return;
+    WSObs w = ws_carve_obs(smem + g * ws_bytes(N, false), N);
+    double x0 = x0v[2 * s], x1 = x0v[2 * s + 1];
+    double h0 = h0v ? h0v[2 * s] : x0, h1 = h0v ? h0v[2 * s + 1] : x1;
+    double d0 = d0v ? d0v[2 * s] : 0.0, d1 = d0v ? d0v[2 * s + 1] : 0.0;
+    const int64_t gid = pb.g.first_id + s;
+    const Coef kp = plant_coef(pb, gid);
+    const Coef km = eo.nominal ? pb.k : kp;
+    obs_model(w, km, d0, d1);
+    if (l < 2) w.cand()[l * (N + 1) + N] = -1;
+    {   // Rho = repmat(rho(x_hat0), 1, N) (NTM_MPC_Sim.m:63-65); Uold = +inf (D14)
+        double r1, r2, r3;
+        rho_eval(km, h0, h1, r1, r2, r3);
+        if (l < N) {
+            w.rho()[3 * l] = r1;
+            w.rho()[3 * l + 1] = r2;
+            w.rho()[3 * l + 2] = r3;
+            w.Uold()[l] = kInf;
+        }
+        NTM_WSYNC();
+    }
+    const int64_t xs = s * 2 * (int64_t)(k_sim + 1);
+    if (xk && l == 0) { xk[xs] = x0; xk[xs + 1] = x1; }
+    if (dk && l == 0) { dk[xs] = d0; dk[xs + 1] = d1; }
+    if (xhk && l == 0) { xhk[xs] = h0; xhk[xs + 1] = h1; }
+    for (int kk = 0; kk < k_sim; ++kk) {
+        int its;
+        int flag = mpc_step_dev<P>(pb, w, h0, h1, l, &its, B, s);
+        if (Uk && l < N) Uk[(s * k_sim + kk) * N + l] = w.U()[l];
+        if (wpred) for (int i = l; i <= N; i += P) wpred[(s * k_sim + kk) * (N + 1) + i] = w.xp()[2 * i];
+        const double u0 = w.U()[0];
+        double n0, n1, m0, m1;
+        plant_step<true>(pb, kp, x0, x1, u0, n0, n1, gid, pb.g.k0 + kk);
+        model_step(pb, km, h0, h1, u0, m0, m1);
+        const double y0 = est_measure(pb, eo.sy[0], n0, gid, pb.g.k0 + kk, 2);
+        const double y1 = est_measure(pb, eo.sy[1], n1, gid, pb.g.k0 + kk, 3);
+        est_update(eo.gain[0], eo.kappa[0], y0, m0, d0, h0);
+        est_update(eo.gain[1], eo.kappa[1], y1, m1, d1, h1);
+        if (l == 0) {
+            if (uk) uk[s * k_sim + kk] = u0;
+            if (exitflag) exitflag[s * k_sim + kk] = flag;
+            if (inner_iters) inner_iters[s * k_sim + kk] = its;
+            if (xk) { xk[xs + 2 * kk + 2] = n0; xk[xs + 2 * kk + 3] = n1; }
+            if (dk) { dk[xs + 2 * kk + 2] = d0; dk[xs + 2 * kk + 3] = d1; }
+            if (xhk) { xhk[xs + 2 * kk + 2] = h0; xhk[xs + 2 * kk + 3] = h1; }
+            if (yk) { yk[(s * k_sim + kk) * 2] = y0; yk[(s * k_sim + kk) * 2 + 1] = y1; }
+        }
+        x0 = n0;
+        x1 = n1;
+        NTM_WSYNC();
+        obs_model(w, km, d0, d1);
+    }
+}
+
 }  // namespace
 
 // Launchers of one horizon's one-wave-per-scenario kernels (grid of one 64-lane

@@ -457,4 +457,26 @@ __device__ __forceinline__ double obs_update(double gain, double e, double d) {
     return isfinite(e) ? fma(gain, e - d, d) : d;
 }
 
+// Output feedback (k_mpc_step_est / k_mpc_run_est, ntm_step.h): ntm_estimator as the
+// kernels take it, one by-value argument.  sy = the measurement noise's standard
+// deviations; the samples are the generator's normal channels 2 and 3 at the plant
+// step's (seed, global id, time index)
+struct EstOpt {
+    int nominal, pad;
+    double gain[2], kappa[2], sy[2];
+};
+// y = x_next + sy n(gid, kt, 2 + i); a zero sy skips the draw, as plant_step skips a zero sigma
+__device__ __forceinline__ double est_measure(const Prob& pb, double sy, double xn, int64_t gid, int kt, uint32_t ch) {
+    return sy != 0.0 ? xn + sy * gen_normal(pb.g.seed, gid, (uint32_t)kt, ch) : xn;
+}
+// One component of the estimator's update from the measurement y and the model's one-step
+// prediction m (without d_hat): r = y - m, iota = r - d_hat (the old one);
+// d_hat <- obs_update(gain, r, d_hat); x_hat <- fma(-kappa, iota, y), one rounding
+// (= (1 - kappa) y + kappa (m + d_hat)), and y itself where iota is not finite
+__device__ __forceinline__ void est_update(double gain, double kappa, double y, double m, double& d, double& xh) {
+    const double r = y - m, iota = r - d;
+    d = obs_update(gain, r, d);
+    xh = isfinite(iota) ? fma(-kappa, iota, y) : y;
+}
+
 }  // namespace ntm

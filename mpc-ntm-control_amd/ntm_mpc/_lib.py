@@ -14,7 +14,7 @@ LIB_PATH = Path(os.environ.get("NTM_MPC_LIB", PKG_ROOT / "lib" / "libntm_mpc.so"
 
 MAX_N = 64
 MODE_NONE, MODE_BOX, MODE_FULL, MODE_FULL_DU = 0, 1, 2, 3
-ABI_VERSION = 6          # include/ntm_mpc.h NTM_MPC_ABI_VERSION
+ABI_VERSION = 7          # include/ntm_mpc.h NTM_MPC_ABI_VERSION
 LITERAL_PHI_RIGHTMUL, LITERAL_GAMMA_INDEX, LITERAL_PLANT_NO_C, RHO1_SQUARED = 1, 2, 4, 8
 EXIT_OPTIMAL, EXIT_MAXITER, EXIT_INFEASIBLE, EXIT_NONFINITE = 1, 0, -2, -7
 NTM_OK = 0
@@ -53,12 +53,19 @@ class NtmObserver(C.Structure):
     _fields_ = [("nominal_model", C.c_int32), ("reserved", C.c_int32), ("gain", C.c_double)]
 
 
+class NtmEstimator(C.Structure):
+    """ntm_estimator — measurement noise and the filtered state estimate (include/ntm_mpc.h)."""
+    _fields_ = [("nominal_model", C.c_int32), ("reserved", C.c_int32), ("gain", C.c_double * 2),
+                ("kappa", C.c_double * 2), ("sigma_y", C.c_double * 2)]
+
+
 _DP = C.POINTER(C.c_double)
 _IP = C.POINTER(C.c_int32)
 _V = C.c_void_p
 _PHY = C.POINTER(NtmPhysics)
 _CFG = C.POINTER(NtmConfig)
 _OBS = C.POINTER(NtmObserver)
+_EST = C.POINTER(NtmEstimator)
 
 # name -> (restype, argtypes)
 EXPORTS = {
@@ -109,11 +116,20 @@ EXPORTS = {
                                   _IP, _IP]),
     "ntm_mpc_run_obs_device": (C.c_int, [C.c_void_p, _PHY, _CFG, _OBS, C.c_int64, C.c_int32, _V, _V, _V, _V, _V, _V,
                                          _V, _V, _V, _V]),
+    "ntm_mpc_step_est": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, C.c_int64, _DP, _DP, _DP, _DP, _DP, _DP, _DP, _DP, _DP,
+                                   _IP, _IP, _IP]),
+    "ntm_mpc_step_est_device": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, C.c_int64, _V, _V, _V, _V, _V, _V, _V, _V, _V,
+                                          _V, _V, _V, _V]),
+    "ntm_mpc_run_est": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, C.c_int64, C.c_int32, _DP, _DP, _DP, _DP, _DP, _DP, _DP,
+                                  _DP, _DP, _DP, _IP, _IP]),
+    "ntm_mpc_run_est_device": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, C.c_int64, C.c_int32, _V, _V, _V, _V, _V, _V,
+                                         _V, _V, _V, _V, _V, _V, _V]),
     "ntm_qp_kkt_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V]),
     "ntm_mpc_kkt_device": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, _V, _V, _V, _V, _V, _V]),
     "ntm_scenarios_x0": (None, [C.c_uint64, C.c_int64, C.c_int64, _DP]),
     "ntm_ctx_set_scenarios": (C.c_int, [C.c_void_p, C.POINTER(NtmScenarioGen)]),
     "ntm_scenario_sample": (None, [C.POINTER(NtmScenarioGen), C.c_int64, C.c_int32, _DP]),
+    "ntm_meas_sample": (None, [C.POINTER(NtmScenarioGen), C.c_int64, C.c_int32, _DP]),
 }
 
 _lib = None

@@ -135,6 +135,39 @@ class Observer:
         return L.NtmObserver(1 if self.nominal_model else 0, 0, float(self.gain))
 
 
+def _pair(v) -> tuple:
+    """A scalar (both components) or a (w, omega) pair as two floats."""
+    a = np.broadcast_to(np.asarray(v, dtype=float), (2,))
+    return float(a[0]), float(a[1])
+
+
+@dataclass
+class Estimator:
+    """ntm_estimator: output feedback, a noisy measurement and a fixed-gain state filter
+    next to the disturbance estimate.  ``nominal_model`` as Observer.  ``gain``, ``kappa``
+    and ``sigma_y`` are (w, omega) pairs (a scalar sets both): d_hat's gain in [0, 1];
+    the trust in the model in [0, 1] (0: x_hat is the measurement); the measurement
+    noise's standard deviation in m and rad/s (non-zero needs an attached ScenarioGen)."""
+    nominal_model: bool = False
+    gain: tuple = (0.0, 0.0)
+    kappa: tuple = (0.0, 0.0)
+    sigma_y: tuple = (0.0, 0.0)
+
+    def to_c(self) -> L.NtmEstimator:
+        d2 = C.c_double * 2
+        return L.NtmEstimator(1 if self.nominal_model else 0, 0, d2(*_pair(self.gain)), d2(*_pair(self.kappa)),
+                              d2(*_pair(self.sigma_y)))
+
+
+def meas_sample(gen: ScenarioGen, B: int, k: int = 0) -> np.ndarray:
+    """(B, 2) host-side unit samples of the measurement noise for scenarios
+    gen.first_id + s at time index k: the generator's normal channels 2 (w) and 3
+    (omega) (ntm_meas_sample; no GPU needed)."""
+    out = np.zeros((B, 2))
+    L.load().ntm_meas_sample(C.byref(gen.to_c()), B, k, out.ctypes.data_as(C.POINTER(C.c_double)))
+    return out
+
+
 def scenario_sample(gen: ScenarioGen, B: int, k: int = 0) -> np.ndarray:
     """(B, 4) host-side samples of the generator for scenarios gen.first_id + s: j_BS
     factor, w_dep factor, n_w(k), n_omega(k) (ntm_scenario_sample; no GPU needed)."""
@@ -698,6 +731,121 @@ class NtmMpc:
                                       dp(out["xk"]), dp(out["uk"]), dp(out["Uk"]), dp(out["wpred"]), dp(out["dk"]),
                                       ip(out["exitflag"]), ip(out["inner_iters"]))
         self._raise(rc, "ntm_mpc_run_obs")
+        return out
+
+    # ------------------------------------------------------------ measurement noise, filtered state estimate
+    def step_est(self, x_k: torch.Tensor, rho: torch.Tensor, U_old: torch.Tensor, d_hat: torch.Tensor,
+                 x_hat: torch.Tensor, est: Estimator, cfg: Config | None = None,
+                 active_ws: torch.Tensor | None = None):
+        """step_obs() with output feedback (ntm_mpc_step_est_device): the controller plans
+        from the estimate ``x_hat`` (2, B) while the plant steps from its true state
+        ``x_k``; ``x_hat`` and ``d_hat`` are updated in place from the noisy measurement
+        ``y`` of ``x_next`` and are also returned in the dict, with ``y``."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x_k.shape[1]
+        xk, _ = _dev_arg(x_k, (2, Bn), name="x_k")
+        rh, rho_st = _dev_arg(rho, (3 * N, Bn), name="rho")
+        uo, uo_st = _dev_arg(U_old, (N, Bn), name="U_old")
+        dh, dh_st = _dev_arg(d_hat, (2, Bn), name="d_hat")
+        xh, xh_st = _dev_arg(x_hat, (2, Bn), name="x_hat")
+        ws, ws_st = (None, False) if active_ws is None else _dev_arg(active_ws, (2 * (N + 1), Bn), torch.int32,
+                                                                     "active_ws")
+        out = {"U": self._empty(N, Bn), "x_pred": self._empty(2 * (N + 1), Bn), "x_next": self._empty(2, Bn),
+               "y": self._empty(2, Bn), "exitflag": self._empty(Bn, dtype=torch.int32),
+               "inner_iters": self._empty(Bn, dtype=torch.int32)}
+        rc = self.lib.ntm_mpc_step_est_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
+                                              C.byref(est.to_c()), Bn, _ptr(xk), _ptr(rh), _ptr(uo), _ptr(dh),
+                                              _ptr(xh), _ptr(out["U"]), _ptr(out["x_pred"]), _ptr(out["x_next"]),
+                                              _ptr(out["y"]), _ptr(out["exitflag"]), _ptr(out["inner_iters"]),
+                                              _ptr(ws), self._stream())
+        self._raise(rc, "ntm_mpc_step_est_device")
+        for staged, dst, src in ((rho_st, rho, rh), (uo_st, U_old, uo), (dh_st, d_hat, dh), (xh_st, x_hat, xh),
+                                 (ws_st, active_ws, ws)):
+            if staged:
+                dst.copy_(src)
+        out["d_hat"], out["x_hat"] = d_hat, x_hat
+        return out
+
+    def step_est_host(self, x_k: np.ndarray, rho: np.ndarray, U_old: np.ndarray, d_hat: np.ndarray,
+                      x_hat: np.ndarray, est: Estimator, cfg: Config | None = None,
+                      active_ws: np.ndarray | None = None):
+        """ntm_mpc_step_est with host arrays (the MEX path): ``d_hat`` and ``x_hat`` (2, B)
+        are updated in place and returned in the dict, with the measurement ``y``."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x_k.shape[1]
+        xk, _ = _host_arg(x_k, (2, Bn), name="x_k")
+        rh, rho_st = _host_arg(rho, (3 * N, Bn), name="rho")
+        uo, uo_st = _host_arg(U_old, (N, Bn), name="U_old")
+        dh, dh_st = _host_arg(d_hat, (2, Bn), name="d_hat")
+        xh, xh_st = _host_arg(x_hat, (2, Bn), name="x_hat")
+        ws, ws_st = (None, False) if active_ws is None else _host_arg(active_ws, (2 * (N + 1), Bn), np.int32,
+                                                                      "active_ws")
+        out = {"U": _host_empty(N, Bn), "x_pred": _host_empty(2 * (N + 1), Bn), "x_next": _host_empty(2, Bn),
+               "y": _host_empty(2, Bn), "exitflag": np.empty(Bn, np.int32), "inner_iters": np.empty(Bn, np.int32)}
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))          # noqa: E731
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))           # noqa: E731
+        rc = self.lib.ntm_mpc_step_est(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
+                                       C.byref(est.to_c()), Bn, dp(xk), dp(rh), dp(uo), dp(dh), dp(xh), dp(out["U"]),
+                                       dp(out["x_pred"]), dp(out["x_next"]), dp(out["y"]), ip(out["exitflag"]),
+                                       ip(out["inner_iters"]), None if ws is None else ip(ws))
+        self._raise(rc, "ntm_mpc_step_est")
+        for staged, dst, src in ((rho_st, rho, rh), (uo_st, U_old, uo), (dh_st, d_hat, dh), (xh_st, x_hat, xh),
+                                 (ws_st, active_ws, ws)):
+            if staged:
+                dst[...] = src
+        out["d_hat"], out["x_hat"] = d_hat, x_hat
+        return out
+
+    def run_est(self, x0: torch.Tensor, est: Estimator, k_sim: int = 20, cfg: Config | None = None,
+                d0: torch.Tensor | None = None, xhat0: torch.Tensor | None = None):
+        """run_obs() with output feedback (ntm_mpc_run_est_device): x, x_hat and d_hat stay
+        on chip.  ``xhat0`` (2, B) is the initial estimate (None: x0).  Returns run_obs()'s
+        dict plus ``xhk`` (2(k_sim+1), B), column 0 the initial estimate, and ``yk``
+        (2 k_sim, B), the measurements."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x0.shape[1]
+        x0, _ = _dev_arg(x0, (2, Bn), name="x0")
+        if d0 is not None:
+            d0, _ = _dev_arg(d0, (2, Bn), name="d0")
+        if xhat0 is not None:
+            xhat0, _ = _dev_arg(xhat0, (2, Bn), name="xhat0")
+        out = {"xk": self._empty(2 * (k_sim + 1), Bn), "uk": self._empty(k_sim, Bn), "Uk": self._empty(N * k_sim, Bn),
+               "wpred": self._empty((N + 1) * k_sim, Bn), "dk": self._empty(2 * (k_sim + 1), Bn),
+               "xhk": self._empty(2 * (k_sim + 1), Bn), "yk": self._empty(2 * k_sim, Bn),
+               "exitflag": self._empty(k_sim, Bn, dtype=torch.int32),
+               "inner_iters": self._empty(k_sim, Bn, dtype=torch.int32)}
+        rc = self.lib.ntm_mpc_run_est_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
+                                             C.byref(est.to_c()), Bn, k_sim, _ptr(x0), _ptr(d0), _ptr(xhat0),
+                                             _ptr(out["xk"]), _ptr(out["uk"]), _ptr(out["Uk"]), _ptr(out["wpred"]),
+                                             _ptr(out["dk"]), _ptr(out["xhk"]), _ptr(out["yk"]),
+                                             _ptr(out["exitflag"]), _ptr(out["inner_iters"]), self._stream())
+        self._raise(rc, "ntm_mpc_run_est_device")
+        return out
+
+    def run_est_host(self, x0: np.ndarray, est: Estimator, k_sim: int = 20, cfg: Config | None = None,
+                     d0: np.ndarray | None = None, xhat0: np.ndarray | None = None):
+        """ntm_mpc_run_est with host arrays: run_obs_host with the estimator, plus ``xhk``
+        and ``yk``."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x0.shape[1]
+        x0, _ = _host_arg(x0, (2, Bn), name="x0")
+        if d0 is not None:
+            d0, _ = _host_arg(d0, (2, Bn), name="d0")
+        if xhat0 is not None:
+            xhat0, _ = _host_arg(xhat0, (2, Bn), name="xhat0")
+        out = {"xk": _host_empty(2 * (k_sim + 1), Bn), "uk": _host_empty(k_sim, Bn),
+               "Uk": _host_empty(N * k_sim, Bn), "wpred": _host_empty((N + 1) * k_sim, Bn),
+               "dk": _host_empty(2 * (k_sim + 1), Bn), "xhk": _host_empty(2 * (k_sim + 1), Bn),
+               "yk": _host_empty(2 * k_sim, Bn),
+               "exitflag": _host_empty(k_sim, Bn, dtype=np.int32), "inner_iters": _host_empty(k_sim, Bn, dtype=np.int32)}
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))          # noqa: E731
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))           # noqa: E731
+        nul = lambda a: None if a is None else dp(a)                    # noqa: E731
+        rc = self.lib.ntm_mpc_run_est(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
+                                      C.byref(est.to_c()), Bn, k_sim, dp(x0), nul(d0), nul(xhat0), dp(out["xk"]),
+                                      dp(out["uk"]), dp(out["Uk"]), dp(out["wpred"]), dp(out["dk"]), dp(out["xhk"]),
+                                      dp(out["yk"]), ip(out["exitflag"]), ip(out["inner_iters"]))
+        self._raise(rc, "ntm_mpc_run_est")
         return out
 
     def step_kkt(self, x_k: torch.Tensor, rho_qp: torch.Tensor, U: torch.Tensor, lam: torch.Tensor | None,
