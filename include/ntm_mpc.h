@@ -38,9 +38,12 @@ extern "C" {
 #endif
 
 #define NTM_MPC_ABI_VERSION 7   /* v7: ntm_estimator, ntm_mpc_step_est / run_est, ntm_meas_sample (additive);
+                                   still 7: ntm_mpc_run_from / run_est_from (additive, NTM_MPC_HAS_RUN_FROM);
                                    v6: ntm_observer, ntm_mpc_step_obs / run_obs (additive);
                                    v5: ntm_config.Ru (input weight); v4: ntm_scenario_gen */
 #define NTM_MAX_N 64
+/* ntm_mpc_run_from* / ntm_mpc_run_est_from* exist (added without an ABI bump) */
+#define NTM_MPC_HAS_RUN_FROM 1
 
 /* Physics constants, NTM_MPC_Sim.m:5-22 (same names and units). */
 typedef struct {
@@ -197,6 +200,36 @@ int ntm_mpc_run_device(ntm_ctx* ctx, const ntm_physics* phys,
                        const double* x0, double* xk, double* uk, double* Uk,
                        double* wpred, int32_t* exitflag, int32_t* inner_iters,
                        void* stream);
+
+/* ntm_mpc_run from a carried state instead of x0: the same fused closed-loop kernels
+ * with the controller state in and out, so a loop can be run in chunks (bounded
+ * histories, a cfg / phys / generator that changes between chunks, checkpoint and
+ * restart).  Per scenario, in/out and all required: x[2], rho[3N], U_old[N],
+ * active_ws[2(N+1)] (the layouts of ntm_mpc_step_ws).  On return they hold the state
+ * after step k_sim-1: x is the last plant state, the rest what a next call (or
+ * ntm_mpc_step_ws) continues from.  Histories as ntm_mpc_run (any may be NULL); xk
+ * column 0 is the input x.  k_sim = 0: nothing changes, xk column 0 is written.
+ *  - The first call of a loop takes ntm_mpc_init's rho / U_old and active_ws all -1:
+ *    exactly what ntm_mpc_run sets up inline.  k_sim steps in one call and the same
+ *    steps split over several calls give the same bits, histories and state.
+ *  - The generator's k0 is the caller's to advance between calls
+ *    (ntm_ctx_set_scenarios): time index k0 + kk is used as in ntm_mpc_run.
+ *  - cfg, phys and the generator may differ from call to call as long as N does not.
+ *    Entries of active_ws that are not a valid active set under the new mode are
+ *    ignored, as in ntm_mpc_step_ws; a caller who changes mode may reset them to -1.
+ *  - Validation is ntm_mpc_run's; in addition a NULL state pointer is NTM_E_INVALID.
+ *    x must not overlap xk.
+ *  - The build is chosen as for ntm_mpc_run (ntm_ctx_step_build describes it), and the
+ *    counters of ntm_ctx_set_stats accumulate across calls. */
+int ntm_mpc_run_from(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg,
+                     int64_t B, int32_t k_sim, double* x, double* rho, double* U_old,
+                     int32_t* active_ws, double* xk, double* uk, double* Uk,
+                     double* wpred, int32_t* exitflag, int32_t* inner_iters);
+int ntm_mpc_run_from_device(ntm_ctx* ctx, const ntm_physics* phys,
+                            const ntm_config* cfg, int64_t B, int32_t k_sim, double* x,
+                            double* rho, double* U_old, int32_t* active_ws, double* xk,
+                            double* uk, double* Uk, double* wpred, int32_t* exitflag,
+                            int32_t* inner_iters, void* stream);
 
 /* ---- function level: one entry per reference function (device ptrs) --- */
 /* rho1.m / rho2.m / rho3.m at x[2] -> rho[3]. */
@@ -472,6 +505,27 @@ int ntm_mpc_run_est_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_conf
                            double* xk, double* uk, double* Uk, double* wpred, double* dk,
                            double* xhk, double* yk, int32_t* exitflag,
                            int32_t* inner_iters, void* stream);
+/* ntm_mpc_run_est from a carried state (see ntm_mpc_run_from, whose rules hold here):
+ * additionally d_hat[2] and x_hat[2] per scenario, in/out and required; est may differ
+ * from call to call too.  For the first call of a loop under nominal_model, ntm_mpc_init
+ * runs with no generator attached and from x_hat, as ntm_mpc_step_obs documents.
+ * Validation is ntm_mpc_run_est's plus NTM_E_INVALID for a NULL state pointer; x, x_hat
+ * and d_hat must not overlap xk, xhk, dk or each other.  The observer loop needs no
+ * entry point of its own: with sigma_y = 0, kappa = 0, gain[0] == gain[1] and
+ * x_hat == x this is ntm_mpc_run_obs continued, bit for bit. */
+int ntm_mpc_run_est_from(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg,
+                         const ntm_estimator* est, int64_t B, int32_t k_sim, double* x,
+                         double* rho, double* U_old, int32_t* active_ws, double* d_hat,
+                         double* x_hat, double* xk, double* uk, double* Uk, double* wpred,
+                         double* dk, double* xhk, double* yk, int32_t* exitflag,
+                         int32_t* inner_iters);
+int ntm_mpc_run_est_from_device(ntm_ctx* ctx, const ntm_physics* phys,
+                                const ntm_config* cfg, const ntm_estimator* est, int64_t B,
+                                int32_t k_sim, double* x, double* rho, double* U_old,
+                                int32_t* active_ws, double* d_hat, double* x_hat, double* xk,
+                                double* uk, double* Uk, double* wpred, double* dk,
+                                double* xhk, double* yk, int32_t* exitflag,
+                                int32_t* inner_iters, void* stream);
 /* Host-side unit samples of the measurement noise for scenarios first_id .. first_id + B
  * - 1 at time index k (out2: 2 per scenario: n(id, k, 2), n(id, k, 3)); the sibling of
  * ntm_scenario_sample, the same code the kernels run. */

@@ -57,6 +57,18 @@
  *       'run_obs' with the estimator (ntm_mpc_run_est): d0 and xhat0 2-by-B
  *       (omitted or []: zeros, x0); xhk 2(k_sim+1)-by-B, the estimate's history
  *       from xhat0 on; yk 2 k_sim-by-B, the measurements.
+ *   [xk, uk, Uk, wpred, exitflag, iters, x, rho, Uold, ws] = ...
+ *       ntm_mpc_mex('run_from', x, rho, Uold, ws, k_sim[, cfg])
+ *       'run' from a carried state (ntm_mpc_run_from, NTM_MPC_HAS_RUN_FROM): x 2-by-B,
+ *       rho, Uold and the int32 ws as for 'step' (a loop's first call: 'init' and -1
+ *       everywhere); they come back as outputs 7 to 10 holding the state after the
+ *       last step, to be passed to the next call, so a loop can run in chunks with
+ *       cfg or 'scenarios' changed in between (advance gen.k0 by the steps done).
+ *       k_sim >= 0; the histories are those of 'run', xk's first column the input x.
+ *   [xk, uk, Uk, wpred, exitflag, iters, dk, xhk, yk, x, rho, Uold, ws, d_hat, x_hat] = ...
+ *       ntm_mpc_mex('run_est_from', x, rho, Uold, ws, d_hat, x_hat, k_sim, est[, cfg])
+ *       'run_est' from a carried state (ntm_mpc_run_est_from): d_hat and x_hat 2-by-B
+ *       are carried too; the state comes back as outputs 10 to 15.
  *   ntm_mpc_mex('scenarios', gen)                               
  *       gen struct with any of seed, first_id, k0, sigma_w, sigma_omega,
  *       jbs_spread, wdep_spread (ntm_scenario_gen): per-scenario plasma and
@@ -425,6 +437,95 @@ static void do_run_est(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[
     }
 }
 
+/* the int32 2(N+1)-by-B warm-start workspace of the resumable loops (required there) */
+static void in_ws(const mxArray* w, size_t N, size_t B) {
+    if (!mxIsInt32(w) || mxGetM(w) != 2 * (N + 1) || mxGetN(w) != B)
+        mexErrMsgIdAndTxt("ntm:arg", "ws must be an int32 %d-by-%d array", (int)(2 * (N + 1)), (int)B);
+}
+
+static int in_ksim(const mxArray* a) {
+    if (!mxIsDouble(a) || mxGetNumberOfElements(a) != 1 || !(mxGetScalar(a) >= 0))
+        mexErrMsgIdAndTxt("ntm:arg", "k_sim must be a scalar >= 0");
+    return (int)mxGetScalar(a);
+}
+
+/* 'run' from a carried state (ntm_mpc_run_from): the state is outputs 7 to 10 */
+static void do_run_from(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    if (nrhs < 6) mexErrMsgIdAndTxt("ntm:arg", "usage: ntm_mpc_mex('run_from', x, rho, Uold, ws, k_sim[, cfg])");
+    const ntm_config c = read_cfg(nrhs > 6 ? prhs[6] : NULL);
+    ntm_physics p;
+    ntm_physics_default(&p);
+    const size_t B = mxGetN(prhs[1]), N = (size_t)c.N;
+    in_matrix(prhs[1], 2, B, "x");
+    in_matrix(prhs[2], 3 * N, B, "rho");
+    in_matrix(prhs[3], N, B, "Uold");
+    in_ws(prhs[4], N, B);
+    const int k = in_ksim(prhs[5]);
+    mxArray* x = mxDuplicateArray(prhs[1]);
+    mxArray* rho = mxDuplicateArray(prhs[2]);
+    mxArray* uold = mxDuplicateArray(prhs[3]);
+    mxArray* ws = mxDuplicateArray(prhs[4]);
+    mxArray* xk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
+    mxArray* uk = mxCreateDoubleMatrix((size_t)k, B, mxREAL);
+    mxArray* Uk = mxCreateDoubleMatrix(N * (size_t)k, B, mxREAL);
+    mxArray* wp = mxCreateDoubleMatrix((N + 1) * (size_t)k, B, mxREAL);
+    mxArray* fl = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
+    mxArray* it = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
+    check(ntm_mpc_run_from(ctx(), &p, &c, (int64_t)B, k, mxGetDoubles(x), mxGetDoubles(rho), mxGetDoubles(uold),
+                           mxGetInt32s(ws), mxGetDoubles(xk), mxGetDoubles(uk), mxGetDoubles(Uk), mxGetDoubles(wp),
+                           mxGetInt32s(fl), mxGetInt32s(it)),
+          "ntm_mpc_run_from");
+    mxArray* outs[10] = {xk, uk, Uk, wp, fl, it, x, rho, uold, ws};
+    for (int i = 0; i < 10; ++i) {
+        if (i < (nlhs > 0 ? nlhs : 1)) plhs[i] = outs[i];
+        else mxDestroyArray(outs[i]);
+    }
+}
+
+/* 'run_est' from a carried state (ntm_mpc_run_est_from): the state is outputs 10 to 15 */
+static void do_run_est_from(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    if (nrhs < 9)
+        mexErrMsgIdAndTxt("ntm:arg",
+                          "usage: ntm_mpc_mex('run_est_from', x, rho, Uold, ws, d_hat, x_hat, k_sim, est[, cfg])");
+    const ntm_estimator e = read_est(prhs[8]);
+    const ntm_config c = read_cfg(nrhs > 9 ? prhs[9] : NULL);
+    ntm_physics p;
+    ntm_physics_default(&p);
+    const size_t B = mxGetN(prhs[1]), N = (size_t)c.N;
+    in_matrix(prhs[1], 2, B, "x");
+    in_matrix(prhs[2], 3 * N, B, "rho");
+    in_matrix(prhs[3], N, B, "Uold");
+    in_ws(prhs[4], N, B);
+    in_matrix(prhs[5], 2, B, "d_hat");
+    in_matrix(prhs[6], 2, B, "x_hat");
+    const int k = in_ksim(prhs[7]);
+    mxArray* x = mxDuplicateArray(prhs[1]);
+    mxArray* rho = mxDuplicateArray(prhs[2]);
+    mxArray* uold = mxDuplicateArray(prhs[3]);
+    mxArray* ws = mxDuplicateArray(prhs[4]);
+    mxArray* dh = mxDuplicateArray(prhs[5]);
+    mxArray* xh = mxDuplicateArray(prhs[6]);
+    mxArray* xk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
+    mxArray* uk = mxCreateDoubleMatrix((size_t)k, B, mxREAL);
+    mxArray* Uk = mxCreateDoubleMatrix(N * (size_t)k, B, mxREAL);
+    mxArray* wp = mxCreateDoubleMatrix((N + 1) * (size_t)k, B, mxREAL);
+    mxArray* fl = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
+    mxArray* it = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
+    mxArray* dk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
+    mxArray* xhk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
+    mxArray* yk = mxCreateDoubleMatrix(2 * (size_t)k, B, mxREAL);
+    check(ntm_mpc_run_est_from(ctx(), &p, &c, &e, (int64_t)B, k, mxGetDoubles(x), mxGetDoubles(rho), mxGetDoubles(uold),
+                               mxGetInt32s(ws), mxGetDoubles(dh), mxGetDoubles(xh), mxGetDoubles(xk), mxGetDoubles(uk),
+                               mxGetDoubles(Uk), mxGetDoubles(wp), mxGetDoubles(dk), mxGetDoubles(xhk),
+                               mxGetDoubles(yk), mxGetInt32s(fl), mxGetInt32s(it)),
+          "ntm_mpc_run_est_from");
+    mxArray* outs[15] = {xk, uk, Uk, wp, fl, it, dk, xhk, yk, x, rho, uold, ws, dh, xh};
+    for (int i = 0; i < 15; ++i) {
+        if (i < (nlhs > 0 ? nlhs : 1)) plhs[i] = outs[i];
+        else mxDestroyArray(outs[i]);
+    }
+}
+
 static void do_scenarios(int nrhs, const mxArray* prhs[]) {
     if (nrhs < 2 || (mxIsDouble(prhs[1]) && mxGetNumberOfElements(prhs[1]) == 0)) {
         check(ntm_ctx_set_scenarios(ctx(), NULL), "ntm_ctx_set_scenarios");
@@ -456,6 +557,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     else if (!strcmp(cmd, "run_obs")) do_run_obs(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "step_est")) do_step_est(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "run_est")) do_run_est(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "run_from")) do_run_from(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "run_est_from")) do_run_est_from(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "scenarios")) do_scenarios(nrhs, prhs);
     else if (!strcmp(cmd, "close")) release();
     else mexErrMsgIdAndTxt("ntm:arg", "unknown command '%s'", cmd);

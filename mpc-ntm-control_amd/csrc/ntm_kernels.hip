@@ -701,6 +701,45 @@ int launch_run(ntm_ctx* ctx, Prob pb, int64_t B, int k_sim, const double* x0, do
     }
 }
 
+// launch_run's dispatch for k_mpc_run_from (ntm_mpc_run_from): the same builds by the
+// same rules, with the carried state in place of x0
+template <int P, int NN>
+int launch_run_from(ntm_ctx* ctx, Prob pb, int64_t B, int k_sim, double* x, double* rho, double* U_old,
+                    int32_t* active_ws, double* xk, double* uk, double* Uk, double* wpred, int32_t* exitflag,
+                    int32_t* inner_iters, hipStream_t st) {
+    constexpr int G = 64 / P;
+#ifndef NTM_SINGLE_TU
+    if constexpr (P == 64 && (NN == 20 || NN == 50)) {   // ntm_n20.hip, ntm_n50.hip
+        const bool near = small_batch<NN>(ctx, B);
+        const size_t lds = (size_t)G * ws_bytes(pb.N, ws_far(NN) && !near);
+        if (lds > 160 * 1024) return fail(ctx, NTM_E_UNSUPPORTED, "LDS workspace exceeds 160 KiB");
+        if (!near)
+            if (int rc = attach_far<NN>(ctx, pb, B, st)) return rc;
+#define NTM_RF_ARGS pb, B, k_sim, x, rho, U_old, active_ws, xk, uk, Uk, wpred, exitflag, inner_iters, lds, st
+        const hipError_t e =
+            NN == 50 ? (pb.mode == NTM_MODE_FULL_DU ? ntm_launch_run_from_n50m3(NTM_RF_ARGS)
+                                                    : ntm_launch_run_from_n50(NTM_RF_ARGS))
+            : near   ? (one_wave_batch<NN>(ctx, B) ? ntm_launch_run_from_n20near1w(NTM_RF_ARGS)
+                                                   : ntm_launch_run_from_n20near(NTM_RF_ARGS))
+                     : ntm_launch_run_from_n20(NTM_RF_ARGS);
+#undef NTM_RF_ARGS
+        const int rc = check_hip(ctx, e, "k_mpc_run_from<64,NN> launch");
+        return near ? rc : far_release<NN>(ctx, rc, st);
+    } else
+#endif
+    {
+    const size_t lds = static_lds<P, NN>() ? 0 : (size_t)G * ws_bytes(pb.N, ws_far(NN));
+    if (int rc = attach_far<NN>(ctx, pb, B, st)) return rc;
+    int rc = set_lds(ctx, k_mpc_run_from<P, NN>, lds);
+    if (rc) return rc;
+    int64_t blocks = (B + G - 1) / G;
+    if (blocks == 0) return NTM_OK;
+    hipLaunchKernelGGL((k_mpc_run_from<P, NN>), dim3((unsigned)blocks), dim3(64), lds, st, pb, B, k_sim, x, rho, U_old,
+                       active_ws, xk, uk, Uk, wpred, exitflag, inner_iters);
+    return far_release<NN>(ctx, check_hip(ctx, hipGetLastError(), "k_mpc_run_from launch"), st);
+    }
+}
+
 // hot-path dispatch: compile-time horizons for the BASELINE configs (N = 10,
 // 20, 50), a runtime-N kernel for every other horizon
 bool force_generic() {
@@ -838,6 +877,19 @@ int launch_run_est(ntm_ctx* ctx, const Prob& pb, int64_t B, int k_sim, const dou
     hipLaunchKernelGGL((k_mpc_run_est<P>), dim3((unsigned)blocks), dim3(64), lds, st, pb, B, k_sim, x0, d0, xhat0, xk,
                        uk, Uk, wpred, dk, xhk, yk, exitflag, inner_iters, est_opt(est));
     return check_hip(ctx, hipGetLastError(), "k_mpc_run_est launch");
+}
+template <int P>
+int launch_run_est_from(ntm_ctx* ctx, const Prob& pb, int64_t B, int k_sim, double* x, double* rho, double* U_old,
+                        int32_t* active_ws, double* d_hat, double* x_hat, double* xk, double* uk, double* Uk,
+                        double* wpred, double* dk, double* xhk, double* yk, int32_t* exitflag, int32_t* inner_iters,
+                        const ntm_estimator* est, hipStream_t st) {
+    constexpr int G = 64 / P;
+    const size_t lds = (size_t)G * ws_bytes(pb.N, false);
+    if (int rc = set_lds(ctx, k_mpc_run_est_from<P>, lds)) return rc;
+    const int64_t blocks = (B + G - 1) / G;
+    hipLaunchKernelGGL((k_mpc_run_est_from<P>), dim3((unsigned)blocks), dim3(64), lds, st, pb, B, k_sim, x, rho, U_old,
+                       active_ws, d_hat, x_hat, xk, uk, Uk, wpred, dk, xhk, yk, exitflag, inner_iters, est_opt(est));
+    return check_hip(ctx, hipGetLastError(), "k_mpc_run_est_from launch");
 }
 // the estimator entry points' own checks (after validate): the options, the literal
 // switches the observer entry points refuse too, and a seed for the measurement noise
@@ -1569,6 +1621,160 @@ int ntm_mpc_run(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, in
         {exitflag, dfl, (size_t)k_sim * B * 4},      {inner_iters, dit, (size_t)k_sim * B * 4}};
     for (auto& o : outs)
         if (o.h && (rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H")))
+            return rc;
+    return check_hip(ctx, hipStreamSynchronize(st), "sync");
+}
+
+int ntm_mpc_run_from_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, int64_t B, int32_t k_sim,
+                            double* x, double* rho, double* U_old, int32_t* active_ws, double* xk, double* uk,
+                            double* Uk, double* wpred, int32_t* exitflag, int32_t* inner_iters, void* stream) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B);
+    if (rc) return rc;
+    if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
+    if (!x || !rho || !U_old || !active_ws) return fail(ctx, NTM_E_INVALID, "null state array");
+    if (B == 0) return NTM_OK;
+    Prob pb = make_prob(phys, cfg);
+    pb.stats = ctx->stats;
+    if (ctx->gen_on) attach_gen(ctx->gen, phys, cfg, pb);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define CALL(P, NN) \
+    launch_run_from<P, NN>(ctx, pb, B, k_sim, x, rho, U_old, active_ws, xk, uk, Uk, wpred, exitflag, inner_iters, st)
+    return NTM_DISPATCH_P(cfg->N, use_generic(cfg), CALL);
+#undef CALL
+}
+
+// host staging of the carried state: {host, device, bytes} of each in/out array
+struct StateBuf { void* h; void* d; size_t n; };
+
+int ntm_mpc_run_from(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, int64_t B, int32_t k_sim,
+                     double* x, double* rho, double* U_old, int32_t* active_ws, double* xk, double* uk, double* Uk,
+                     double* wpred, int32_t* exitflag, int32_t* inner_iters) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B);
+    if (rc) return rc;
+    if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
+    if (!x || !rho || !U_old || !active_ws) return fail(ctx, NTM_E_INVALID, "null state array");
+    if (B == 0) return NTM_OK;
+    const int N = cfg->N;
+    size_t b0 = al(2 * B * 8), brho = al((size_t)3 * N * B * 8), bu = al((size_t)N * B * 8),
+           bws = al(2 * (size_t)(N + 1) * B * 4), bxk = al(2 * (size_t)(k_sim + 1) * B * 8),
+           buk = al((size_t)k_sim * B * 8), bUk = al((size_t)N * k_sim * B * 8),
+           bwp = al((size_t)(N + 1) * k_sim * B * 8), bi = al((size_t)k_sim * B * 4);
+    rc = ensure_buf(ctx, b0 + brho + bu + bws + bxk + buk + bUk + bwp + 2 * bi);
+    if (rc) return rc;
+    char* p = static_cast<char*>(ctx->dbuf);
+    double* dx = (double*)p; p += b0;
+    double* drho = (double*)p; p += brho;
+    double* duo = (double*)p; p += bu;
+    int32_t* dws = (int32_t*)p; p += bws;
+    double* dxk = (double*)p; p += bxk;
+    double* duk = (double*)p; p += buk;
+    double* dUk = (double*)p; p += bUk;
+    double* dwp = (double*)p; p += bwp;
+    int32_t* dfl = (int32_t*)p; p += bi;
+    int32_t* dit = (int32_t*)p;
+    hipStream_t st = ctx->stream;
+    const StateBuf state[] = {{x, dx, 2 * (size_t)B * 8}, {rho, drho, (size_t)3 * N * B * 8},
+                              {U_old, duo, (size_t)N * B * 8}, {active_ws, dws, 2 * (size_t)(N + 1) * B * 4}};
+    for (auto& o : state)
+        if ((rc = check_hip(ctx, hipMemcpyAsync(o.d, o.h, o.n, hipMemcpyHostToDevice, st), "H2D"))) return rc;
+    rc = ntm_mpc_run_from_device(ctx, phys, cfg, B, k_sim, dx, drho, duo, dws, xk ? dxk : nullptr, uk ? duk : nullptr,
+                                 Uk ? dUk : nullptr, wpred ? dwp : nullptr, exitflag ? dfl : nullptr,
+                                 inner_iters ? dit : nullptr, st);
+    if (rc) return rc;
+    for (auto& o : state)
+        if ((rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H"))) return rc;
+    struct { void* h; void* d; size_t n; } outs[] = {
+        {xk, dxk, 2 * (size_t)(k_sim + 1) * B * 8}, {uk, duk, (size_t)k_sim * B * 8},
+        {Uk, dUk, (size_t)N * k_sim * B * 8},        {wpred, dwp, (size_t)(N + 1) * k_sim * B * 8},
+        {exitflag, dfl, (size_t)k_sim * B * 4},      {inner_iters, dit, (size_t)k_sim * B * 4}};
+    for (auto& o : outs)
+        if (o.h && o.n && (rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H")))
+            return rc;
+    return check_hip(ctx, hipStreamSynchronize(st), "sync");
+}
+
+int ntm_mpc_run_est_from_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est,
+                                int64_t B, int32_t k_sim, double* x, double* rho, double* U_old, int32_t* active_ws,
+                                double* d_hat, double* x_hat, double* xk, double* uk, double* Uk, double* wpred,
+                                double* dk, double* xhk, double* yk, int32_t* exitflag, int32_t* inner_iters,
+                                void* stream) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B);
+    if (rc) return rc;
+    if ((rc = validate_est(ctx, cfg, est))) return rc;
+    if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
+    if (!x || !rho || !U_old || !active_ws || !d_hat || !x_hat) return fail(ctx, NTM_E_INVALID, "null state array");
+    if (B == 0) return NTM_OK;
+    Prob pb = make_prob(phys, cfg);
+    pb.stats = ctx->stats;
+    if (ctx->gen_on) attach_gen(ctx->gen, phys, cfg, pb);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int P = lanes_for(cfg->N);
+#define CALL(P_)                                                                                                  \
+    launch_run_est_from<P_>(ctx, pb, B, k_sim, x, rho, U_old, active_ws, d_hat, x_hat, xk, uk, Uk, wpred, dk, xhk, \
+                            yk, exitflag, inner_iters, est, st)
+    return P == 16 ? CALL(16) : (P == 32 ? CALL(32) : CALL(64));
+#undef CALL
+}
+
+int ntm_mpc_run_est_from(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est,
+                         int64_t B, int32_t k_sim, double* x, double* rho, double* U_old, int32_t* active_ws,
+                         double* d_hat, double* x_hat, double* xk, double* uk, double* Uk, double* wpred, double* dk,
+                         double* xhk, double* yk, int32_t* exitflag, int32_t* inner_iters) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B);
+    if (rc) return rc;
+    if ((rc = validate_est(ctx, cfg, est))) return rc;
+    if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
+    if (!x || !rho || !U_old || !active_ws || !d_hat || !x_hat) return fail(ctx, NTM_E_INVALID, "null state array");
+    if (B == 0) return NTM_OK;
+    const int N = cfg->N;
+    size_t b0 = al(2 * B * 8), brho = al((size_t)3 * N * B * 8), bu = al((size_t)N * B * 8),
+           bws = al(2 * (size_t)(N + 1) * B * 4), bxk = al(2 * (size_t)(k_sim + 1) * B * 8),
+           buk = al((size_t)k_sim * B * 8), bUk = al((size_t)N * k_sim * B * 8),
+           bwp = al((size_t)(N + 1) * k_sim * B * 8), byk = al(2 * (size_t)k_sim * B * 8),
+           bi = al((size_t)k_sim * B * 4);
+    rc = ensure_buf(ctx, 3 * b0 + brho + bu + bws + 3 * bxk + buk + bUk + bwp + byk + 2 * bi);
+    if (rc) return rc;
+    char* p = static_cast<char*>(ctx->dbuf);
+    double* dx = (double*)p; p += b0;
+    double* ddh = (double*)p; p += b0;
+    double* dxh = (double*)p; p += b0;
+    double* drho = (double*)p; p += brho;
+    double* duo = (double*)p; p += bu;
+    int32_t* dws = (int32_t*)p; p += bws;
+    double* dxk = (double*)p; p += bxk;
+    double* ddk = (double*)p; p += bxk;
+    double* dxhk = (double*)p; p += bxk;
+    double* duk = (double*)p; p += buk;
+    double* dUk = (double*)p; p += bUk;
+    double* dwp = (double*)p; p += bwp;
+    double* dyk = (double*)p; p += byk;
+    int32_t* dfl = (int32_t*)p; p += bi;
+    int32_t* dit = (int32_t*)p;
+    hipStream_t st = ctx->stream;
+    const StateBuf state[] = {{x, dx, 2 * (size_t)B * 8},     {d_hat, ddh, 2 * (size_t)B * 8},
+                              {x_hat, dxh, 2 * (size_t)B * 8}, {rho, drho, (size_t)3 * N * B * 8},
+                              {U_old, duo, (size_t)N * B * 8}, {active_ws, dws, 2 * (size_t)(N + 1) * B * 4}};
+    for (auto& o : state)
+        if ((rc = check_hip(ctx, hipMemcpyAsync(o.d, o.h, o.n, hipMemcpyHostToDevice, st), "H2D"))) return rc;
+    rc = ntm_mpc_run_est_from_device(ctx, phys, cfg, est, B, k_sim, dx, drho, duo, dws, ddh, dxh, xk ? dxk : nullptr,
+                                     uk ? duk : nullptr, Uk ? dUk : nullptr, wpred ? dwp : nullptr,
+                                     dk ? ddk : nullptr, xhk ? dxhk : nullptr, yk ? dyk : nullptr,
+                                     exitflag ? dfl : nullptr, inner_iters ? dit : nullptr, st);
+    if (rc) return rc;
+    for (auto& o : state)
+        if ((rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H"))) return rc;
+    struct { void* h; void* d; size_t n; } outs[] = {
+        {xk, dxk, 2 * (size_t)(k_sim + 1) * B * 8},  {uk, duk, (size_t)k_sim * B * 8},
+        {Uk, dUk, (size_t)N * k_sim * B * 8},         {wpred, dwp, (size_t)(N + 1) * k_sim * B * 8},
+        {dk, ddk, 2 * (size_t)(k_sim + 1) * B * 8},  {xhk, dxhk, 2 * (size_t)(k_sim + 1) * B * 8},
+        {yk, dyk, 2 * (size_t)k_sim * B * 8},         {exitflag, dfl, (size_t)k_sim * B * 4},
+        {inner_iters, dit, (size_t)k_sim * B * 4}};
+    for (auto& o : outs)
+        if (o.h && o.n && (rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H")))
             return rc;
     return check_hip(ctx, hipStreamSynchronize(st), "sync");
 }

@@ -24,7 +24,7 @@
 #undef NTM_CH
 #define NTM_CH NTM_N20_CH
 // Round 13: mode 3 at N = 20 runs on the runtime-N kernels (host dispatch; the launchers
-// below refuse it), so the three kernels of this unit are compiled without input-rate
+// below refuse it), so the kernels of this unit are compiled without input-rate
 // rows (rate_rows in ntm_ws.h).  `mode` is a launch value, so the compiler had kept every
 // rate arm and restored the spilled eight-dword kernel-argument tuple that holds `du`
 // wherever one stood: in the benchmark's kernel 9,446 -> 8,809 static VALU instructions,

@@ -53,7 +53,9 @@ __device__ __forceinline__ int64_t xcd_swizzle(int64_t b, int64_t nb) {
 // only a hint (every candidate is re-solved exactly and KKT-certified), but it
 // comes from the caller, so each slot is validated before use: count in
 // [0, N], ids in [0, rows), no repeats; anything else disables the slot.
-template <int P, class W>
+// RUN (k_mpc_run_from): an empty set in mode 0 is kept, as qp_phase leaves it from one
+// step of k_mpc_run to the next, so a chunk boundary does not change the path taken.
+template <int P, class W, bool RUN = false>
 __device__ __forceinline__ void load_candidates(const Prob& pb, const W& w, int64_t B, int64_t s, const int32_t* ws, int l) {
     const int N = w.n();
     const int nrows = StructRows(pb).rows();
@@ -66,6 +68,7 @@ __device__ __forceinline__ void load_candidates(const Prob& pb, const W& w, int6
         const int q = uni<P>(c[N]);
         if (q < 0) continue;
         bool bad = q > N || nrows == 0;
+        if constexpr (RUN) bad = q > N || (nrows == 0 && q > 0);
         if (!bad) {
             int lb = 0;
             if (l < q) lb = (c[l] < 0 || c[l] >= nrows) ? 1 : 0;
@@ -355,6 +358,66 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, NN, FAR)) void k_mpc_run(
     }
 }
 
+// k_mpc_run from a carried state and back to it (ntm_mpc_run_from): x[2], rho[3N],
+// U_old[N] and active_ws[2(N+1)] per scenario, in/out, in ntm_mpc_step_ws's layouts.
+// A sibling kernel and not a flag of k_mpc_run, for k_mpc_step_dual's reason: more
+// kernel arguments on the template would change every existing instantiation's
+// argument block.  The inline initialisation is replaced by load_candidates /
+// load_state as in k_mpc_step; the loop body is k_mpc_run's; what the next step would
+// read from the workspace (rho, U_old, the two candidate sets) and the plant state go
+// back to HBM after the last step.  k_sim = 0 stores nothing but xk's column 0.
+template <int P, int NN, bool FAR = ws_far(NN)>
+__global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, NN, FAR)) void k_mpc_run_from(
+    Prob pb, int64_t B, int k_sim, double* __restrict__ x, double* __restrict__ rho, double* __restrict__ U_old,
+    int32_t* __restrict__ active_ws, double* xk, double* uk, double* Uk, double* wpred, int32_t* exitflag,
+    int32_t* inner_iters) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int G = 64 / P;
+    const int g = threadIdx.x / P, l = threadIdx.x % P;
+    const int64_t s = xcd_swizzle(blockIdx.x, gridDim.x) * G + g;
+    const int N = NN > 0 ? NN : pb.N;
+    if (s >= B) return;
+    char* sbase = smem + g * ws_bytes(N, FAR);
+    if constexpr (static_lds<P, NN>()) {
+        __shared__ __attribute__((aligned(16))) char smem_s[ws_bytes(NN > 0 ? NN : 1, FAR)];
+        sbase = smem_s;
+    }
+    auto w = ws_carve<NN, true, FAR>(sbase, N, &pb, s);
+    double x0 = x[2 * s], x1 = x[2 * s + 1];
+    load_candidates<P, decltype(w), true>(pb, w, B, s, active_ws, l);
+    load_state<P>(w, B, s, rho, U_old, l);
+    scn_store(pb, w, pb.g.first_id + s, l);           // this scenario's plasma (generator)
+    NTM_WSYNC();
+    if (xk && l == 0) { xk[s * 2 * (k_sim + 1)] = x0; xk[s * 2 * (k_sim + 1) + 1] = x1; }
+    for (int kk = 0; kk < k_sim; ++kk) {
+        int its;
+        int flag = mpc_step_dev<P>(pb, w, x0, x1, l, &its, B, s);
+        if (Uk && l < N) Uk[(s * k_sim + kk) * N + l] = w.U()[l];
+        if (wpred) for (int i = l; i <= N; i += P) wpred[(s * k_sim + kk) * (N + 1) + i] = w.xp()[2 * i];
+        double n0, n1;
+        plant_step<true>(pb, scn_coef(pb, w), x0, x1, w.U()[0], n0, n1, pb.g.first_id + s, pb.g.k0 + kk);
+        if (l == 0) {
+            if (uk) uk[s * k_sim + kk] = w.U()[0];
+            if (exitflag) exitflag[s * k_sim + kk] = flag;
+            if (inner_iters) inner_iters[s * k_sim + kk] = its;
+            if (xk) { xk[s * 2 * (k_sim + 1) + 2 * kk + 2] = n0; xk[s * 2 * (k_sim + 1) + 2 * kk + 3] = n1; }
+        }
+        x0 = n0;
+        x1 = n1;
+        NTM_WSYNC();
+    }
+    if (k_sim > 0) {
+        store_record<P>(rho + s * (3 * N), w.rho(), 3 * N, l);
+        store_record<P>(U_old + s * N, w.Uold(), N, l);
+        for (int e = l; e < 2 * (N + 1); e += P) active_ws[s * (2 * (N + 1)) + e] = w.cand()[e];
+        if (is16(x)) {
+            if (l == 0) *reinterpret_cast<double2*>(x + 2 * s) = make_double2(x0, x1);
+        } else if (l < 2) {
+            x[2 * s + l] = l ? x1 : x0;
+        }
+    }
+}
+
 // Plant-model mismatch and the offset-free disturbance estimate (ntm_mpc_step_obs /
 // ntm_mpc_run_obs).  Siblings of the runtime-N kernels, as k_mpc_step_dual is, and for
 // its reason: the estimate and the options are kernel arguments, and the model's
@@ -641,6 +704,75 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_run
     }
 }
 
+// k_mpc_run_est from a carried state and back to it (ntm_mpc_run_est_from), the sibling
+// k_mpc_run_from is of k_mpc_run: x, rho, U_old, active_ws, d_hat[2] and x_hat[2] per
+// scenario, in/out.  The model is built from the loaded d_hat.  With sy = 0, kappa = 0,
+// equal gains and x_hat == x it continues k_mpc_run_obs.
+template <int P>
+__global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_run_est_from(
+    Prob pb, int64_t B, int k_sim, double* __restrict__ x, double* __restrict__ rho, double* __restrict__ U_old,
+    int32_t* __restrict__ active_ws, double* __restrict__ d_hat, double* __restrict__ x_hat, double* xk, double* uk,
+    double* Uk, double* wpred, double* dk, double* xhk, double* yk, int32_t* exitflag, int32_t* inner_iters,
+    EstOpt eo) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int G = 64 / P;
+    const int g = threadIdx.x / P, l = threadIdx.x % P;
+    const int64_t s = xcd_swizzle(blockIdx.x, gridDim.x) * G + g;
+    const int N = pb.N;
+    if (s >= B) return;
+    WSObs w = ws_carve_obs(smem + g * ws_bytes(N, false), N);
+    double x0 = x[2 * s], x1 = x[2 * s + 1];
+    double h0 = x_hat[2 * s], h1 = x_hat[2 * s + 1];
+    double d0 = d_hat[2 * s], d1 = d_hat[2 * s + 1];
+    const int64_t gid = pb.g.first_id + s;
+    const Coef kp = plant_coef(pb, gid);
+    const Coef km = eo.nominal ? pb.k : kp;
+    obs_model(w, km, d0, d1);
+    load_candidates<P, WSObs, true>(pb, w, B, s, active_ws, l);
+    load_state<P>(w, B, s, rho, U_old, l);
+    const int64_t xs = s * 2 * (int64_t)(k_sim + 1);
+    if (xk && l == 0) { xk[xs] = x0; xk[xs + 1] = x1; }
+    if (dk && l == 0) { dk[xs] = d0; dk[xs + 1] = d1; }
+    if (xhk && l == 0) { xhk[xs] = h0; xhk[xs + 1] = h1; }
+    for (int kk = 0; kk < k_sim; ++kk) {
+        int its;
+        int flag = mpc_step_dev<P>(pb, w, h0, h1, l, &its, B, s);
+        if (Uk && l < N) Uk[(s * k_sim + kk) * N + l] = w.U()[l];
+        if (wpred) for (int i = l; i <= N; i += P) wpred[(s * k_sim + kk) * (N + 1) + i] = w.xp()[2 * i];
+        const double u0 = w.U()[0];
+        double n0, n1, m0, m1;
+        plant_step<true>(pb, kp, x0, x1, u0, n0, n1, gid, pb.g.k0 + kk);
+        model_step(pb, km, h0, h1, u0, m0, m1);
+        const double y0 = est_measure(pb, eo.sy[0], n0, gid, pb.g.k0 + kk, 2);
+        const double y1 = est_measure(pb, eo.sy[1], n1, gid, pb.g.k0 + kk, 3);
+        est_update(eo.gain[0], eo.kappa[0], y0, m0, d0, h0);
+        est_update(eo.gain[1], eo.kappa[1], y1, m1, d1, h1);
+        if (l == 0) {
+            if (uk) uk[s * k_sim + kk] = u0;
+            if (exitflag) exitflag[s * k_sim + kk] = flag;
+            if (inner_iters) inner_iters[s * k_sim + kk] = its;
+            if (xk) { xk[xs + 2 * kk + 2] = n0; xk[xs + 2 * kk + 3] = n1; }
+            if (dk) { dk[xs + 2 * kk + 2] = d0; dk[xs + 2 * kk + 3] = d1; }
+            if (xhk) { xhk[xs + 2 * kk + 2] = h0; xhk[xs + 2 * kk + 3] = h1; }
+            if (yk) { yk[(s * k_sim + kk) * 2] = y0; yk[(s * k_sim + kk) * 2 + 1] = y1; }
+        }
+        x0 = n0;
+        x1 = n1;
+        NTM_WSYNC();
+        obs_model(w, km, d0, d1);
+    }
+    if (k_sim > 0) {
+        store_record<P>(rho + s * (3 * N), w.rho(), 3 * N, l);
+        store_record<P>(U_old + s * N, w.Uold(), N, l);
+        for (int e = l; e < 2 * (N + 1); e += P) active_ws[s * (2 * (N + 1)) + e] = w.cand()[e];
+        if (l < 2) {
+            x[2 * s + l] = l ? x1 : x0;
+            d_hat[2 * s + l] = l ? d1 : d0;
+            x_hat[2 * s + l] = l ? h1 : h0;
+        }
+    }
+}
+
 }  // namespace
 
 // Launchers of one horizon's one-wave-per-scenario kernels (grid of one 64-lane
@@ -695,6 +827,19 @@ hipError_t ntm_launch_run_v(const ntm::Prob& pb, int64_t B, int k_sim, const dou
                        wpred, exitflag, inner_iters);
     return hipGetLastError();
 }
+template <int NN, bool FAR>
+hipError_t ntm_launch_run_from_v(const ntm::Prob& pb, int64_t B, int k_sim, double* x, double* rho, double* U_old,
+                                 int32_t* active_ws, double* xk, double* uk, double* Uk, double* wpred,
+                                 int32_t* exitflag, int32_t* inner_iters, size_t lds, hipStream_t st) {
+    if (!ntm_mode_built<NN, FAR>(pb)) return hipErrorInvalidValue;
+    if (static_lds<64, NN>()) lds = 0;                 // the workspace is the kernel's static LDS
+    hipError_t e = ntm_lds_opt_in(k_mpc_run_from<64, NN, FAR>, lds);
+    if (e != hipSuccess) return e;
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL((k_mpc_run_from<64, NN, FAR>), dim3((unsigned)B), dim3(64), lds, st, pb, B, k_sim, x, rho,
+                       U_old, active_ws, xk, uk, Uk, wpred, exitflag, inner_iters);
+    return hipGetLastError();
+}
 }  // namespace
 // One translation unit per (horizon, layout): ntm_n20.hip (far), ntm_n20near.hip (the
 // all-LDS N = 20 build for small batches, its own batch settings), ntm_n50.hip (far,
@@ -705,7 +850,11 @@ hipError_t ntm_launch_run_v(const ntm::Prob& pb, int64_t B, int k_sim, const dou
                                       int32_t* inner_iters, int32_t* active_ws, size_t lds, hipStream_t st);       \
     hipError_t ntm_launch_run_##NAME(const ntm::Prob& pb, int64_t B, int k_sim, const double* x0, double* xk,     \
                                      double* uk, double* Uk, double* wpred, int32_t* exitflag,                     \
-                                     int32_t* inner_iters, size_t lds, hipStream_t st);
+                                     int32_t* inner_iters, size_t lds, hipStream_t st);                            \
+    hipError_t ntm_launch_run_from_##NAME(const ntm::Prob& pb, int64_t B, int k_sim, double* x, double* rho,      \
+                                          double* U_old, int32_t* active_ws, double* xk, double* uk, double* Uk,   \
+                                          double* wpred, int32_t* exitflag, int32_t* inner_iters, size_t lds,      \
+                                          hipStream_t st);
 #define NTM_DEFINE_LAYOUT_LAUNCHERS(NAME, NNV, FARV)                                                               \
     hipError_t ntm_launch_step_##NAME(const ntm::Prob& pb, int64_t B, const double* x_k, double* rho,             \
                                       double* U_old, double* U, double* x_pred, double* x_next, int32_t* exitflag, \
@@ -717,6 +866,13 @@ hipError_t ntm_launch_run_v(const ntm::Prob& pb, int64_t B, int k_sim, const dou
                                      double* uk, double* Uk, double* wpred, int32_t* exitflag,                     \
                                      int32_t* inner_iters, size_t lds, hipStream_t st) {                           \
         return ntm_launch_run_v<NNV, FARV>(pb, B, k_sim, x0, xk, uk, Uk, wpred, exitflag, inner_iters, lds, st);  \
+    }                                                                                                              \
+    hipError_t ntm_launch_run_from_##NAME(const ntm::Prob& pb, int64_t B, int k_sim, double* x, double* rho,      \
+                                          double* U_old, int32_t* active_ws, double* xk, double* uk, double* Uk,   \
+                                          double* wpred, int32_t* exitflag, int32_t* inner_iters, size_t lds,      \
+                                          hipStream_t st) {                                                        \
+        return ntm_launch_run_from_v<NNV, FARV>(pb, B, k_sim, x, rho, U_old, active_ws, xk, uk, Uk, wpred,        \
+                                                exitflag, inner_iters, lds, st);                                   \
     }
 NTM_DECLARE_LAYOUT_LAUNCHERS(n20)
 NTM_DECLARE_LAYOUT_LAUNCHERS(n20near)

@@ -124,6 +124,14 @@ EXPORTS = {
                                   _DP, _DP, _DP, _IP, _IP]),
     "ntm_mpc_run_est_device": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, C.c_int64, C.c_int32, _V, _V, _V, _V, _V, _V,
                                          _V, _V, _V, _V, _V, _V, _V]),
+    "ntm_mpc_run_from": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, C.c_int32, _DP, _DP, _DP, _IP, _DP, _DP, _DP, _DP,
+                                   _IP, _IP]),
+    "ntm_mpc_run_from_device": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V,
+                                          _V, _V, _V]),
+    "ntm_mpc_run_est_from": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, C.c_int64, C.c_int32, _DP, _DP, _DP, _IP, _DP, _DP,
+                                       _DP, _DP, _DP, _DP, _DP, _DP, _DP, _IP, _IP]),
+    "ntm_mpc_run_est_from_device": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, C.c_int64, C.c_int32, _V, _V, _V, _V, _V,
+                                              _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     "ntm_qp_kkt_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V]),
     "ntm_mpc_kkt_device": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, _V, _V, _V, _V, _V, _V]),
     "ntm_scenarios_x0": (None, [C.c_uint64, C.c_int64, C.c_int64, _DP]),
@@ -131,6 +139,10 @@ EXPORTS = {
     "ntm_scenario_sample": (None, [C.POINTER(NtmScenarioGen), C.c_int64, C.c_int32, _DP]),
     "ntm_meas_sample": (None, [C.POINTER(NtmScenarioGen), C.c_int64, C.c_int32, _DP]),
 }
+
+# additive entry points an older build of the library (one loaded through NTM_MPC_LIB, an
+# A/B against a parent commit) may lack: bound when present, see has_run_from()
+OPTIONAL = ("ntm_mpc_run_from", "ntm_mpc_run_from_device", "ntm_mpc_run_est_from", "ntm_mpc_run_est_from_device")
 
 _lib = None
 
@@ -149,6 +161,8 @@ def load(path: Path | str | None = None):
     except OSError as e:  # pragma: no cover - depends on the loader
         raise NtmLibraryError(f"cannot load {p}: {e}") from e
     for name, (res, args) in EXPORTS.items():
+        if name in OPTIONAL and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -157,6 +171,13 @@ def load(path: Path | str | None = None):
     if path is None:
         _lib = lib
     return lib
+
+
+def has_run_from(lib=None) -> bool:
+    """The loaded library has the resumable closed loops (NTM_MPC_HAS_RUN_FROM in the
+    header): ntm_mpc_run_from* / ntm_mpc_run_est_from*, detected by symbol."""
+    lib = lib or load()
+    return all(hasattr(lib, n) for n in OPTIONAL)
 
 
 def default_physics() -> NtmPhysics:

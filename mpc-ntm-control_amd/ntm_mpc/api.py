@@ -848,6 +848,106 @@ class NtmMpc:
         self._raise(rc, "ntm_mpc_run_est")
         return out
 
+    # ------------------------------------------------------------ resumable closed loops
+    def _run_out(self, k_sim, N, Bn, est=False, host=False):
+        if not L.has_run_from(self.lib):
+            raise NtmLibraryError("this build of the library has no ntm_mpc_run_from (NTM_MPC_HAS_RUN_FROM)")
+        mk = _host_empty if host else self._empty
+        i32 = np.int32 if host else torch.int32
+        out = {"xk": mk(2 * (k_sim + 1), Bn), "uk": mk(k_sim, Bn), "Uk": mk(N * k_sim, Bn),
+               "wpred": mk((N + 1) * k_sim, Bn)}
+        if est:
+            out.update(dk=mk(2 * (k_sim + 1), Bn), xhk=mk(2 * (k_sim + 1), Bn), yk=mk(2 * k_sim, Bn))
+        out.update(exitflag=mk(k_sim, Bn, dtype=i32), inner_iters=mk(k_sim, Bn, dtype=i32))
+        return out
+
+    def run_from(self, x: torch.Tensor, rho: torch.Tensor, U_old: torch.Tensor, active_ws: torch.Tensor,
+                 k_sim: int = 20, cfg: Config | None = None):
+        """run() from a carried state (ntm_mpc_run_from_device): ``x`` (2, B), ``rho``
+        (3N, B), ``U_old`` (N, B) and ``active_ws`` (2(N+1), B) int32 are updated in
+        place to the state after the last step, so the next call (or step()) continues
+        the loop; one call of k steps and any split of them give the same bits.  The
+        first call takes initial_state() and new_active_ws().  An attached generator's
+        ``k0`` is the caller's to advance between calls.  Returns run()'s dict; xk's
+        column 0 is the input ``x``."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x.shape[1]
+        state = [_dev_arg(x, (2, Bn), name="x"), _dev_arg(rho, (3 * N, Bn), name="rho"),
+                 _dev_arg(U_old, (N, Bn), name="U_old"),
+                 _dev_arg(active_ws, (2 * (N + 1), Bn), torch.int32, "active_ws")]
+        out = self._run_out(k_sim, N, Bn)
+        rc = self.lib.ntm_mpc_run_from_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()), Bn, k_sim,
+                                              *[_ptr(a) for a, _ in state], *[_ptr(v) for v in out.values()],
+                                              self._stream())
+        self._raise(rc, "ntm_mpc_run_from_device")
+        for dst, (src, staged) in zip((x, rho, U_old, active_ws), state):
+            if staged:
+                dst.copy_(src)
+        return out
+
+    def run_from_host(self, x: np.ndarray, rho: np.ndarray, U_old: np.ndarray, active_ws: np.ndarray,
+                      k_sim: int = 20, cfg: Config | None = None):
+        """ntm_mpc_run_from with host arrays (the MEX path); the state arrays are
+        updated in place."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x.shape[1]
+        state = [_host_arg(x, (2, Bn), name="x"), _host_arg(rho, (3 * N, Bn), name="rho"),
+                 _host_arg(U_old, (N, Bn), name="U_old"),
+                 _host_arg(active_ws, (2 * (N + 1), Bn), np.int32, "active_ws")]
+        out = self._run_out(k_sim, N, Bn, host=True)
+        hp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32 if a.dtype == np.int32 else C.c_double))  # noqa: E731
+        rc = self.lib.ntm_mpc_run_from(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()), Bn, k_sim,
+                                       *[hp(a) for a, _ in state], *[hp(v) for v in out.values()])
+        self._raise(rc, "ntm_mpc_run_from")
+        for dst, (src, staged) in zip((x, rho, U_old, active_ws), state):
+            if staged:
+                dst[...] = src
+        return out
+
+    def run_est_from(self, x: torch.Tensor, rho: torch.Tensor, U_old: torch.Tensor, active_ws: torch.Tensor,
+                     d_hat: torch.Tensor, x_hat: torch.Tensor, est: Estimator, k_sim: int = 20,
+                     cfg: Config | None = None):
+        """run_est() from a carried state (ntm_mpc_run_est_from_device): run_from() with
+        the estimator's ``d_hat`` and ``x_hat`` (2, B) carried too, all updated in place.
+        With sigma_y = 0, kappa = 0, equal gains and x_hat == x it continues run_obs()
+        bit for bit.  Returns run_est()'s dict."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x.shape[1]
+        state = [_dev_arg(x, (2, Bn), name="x"), _dev_arg(rho, (3 * N, Bn), name="rho"),
+                 _dev_arg(U_old, (N, Bn), name="U_old"),
+                 _dev_arg(active_ws, (2 * (N + 1), Bn), torch.int32, "active_ws"),
+                 _dev_arg(d_hat, (2, Bn), name="d_hat"), _dev_arg(x_hat, (2, Bn), name="x_hat")]
+        out = self._run_out(k_sim, N, Bn, est=True)
+        rc = self.lib.ntm_mpc_run_est_from_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
+                                                  C.byref(est.to_c()), Bn, k_sim, *[_ptr(a) for a, _ in state],
+                                                  *[_ptr(v) for v in out.values()], self._stream())
+        self._raise(rc, "ntm_mpc_run_est_from_device")
+        for dst, (src, staged) in zip((x, rho, U_old, active_ws, d_hat, x_hat), state):
+            if staged:
+                dst.copy_(src)
+        return out
+
+    def run_est_from_host(self, x: np.ndarray, rho: np.ndarray, U_old: np.ndarray, active_ws: np.ndarray,
+                          d_hat: np.ndarray, x_hat: np.ndarray, est: Estimator, k_sim: int = 20,
+                          cfg: Config | None = None):
+        """ntm_mpc_run_est_from with host arrays; the state arrays are updated in place."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x.shape[1]
+        state = [_host_arg(x, (2, Bn), name="x"), _host_arg(rho, (3 * N, Bn), name="rho"),
+                 _host_arg(U_old, (N, Bn), name="U_old"),
+                 _host_arg(active_ws, (2 * (N + 1), Bn), np.int32, "active_ws"),
+                 _host_arg(d_hat, (2, Bn), name="d_hat"), _host_arg(x_hat, (2, Bn), name="x_hat")]
+        out = self._run_out(k_sim, N, Bn, est=True, host=True)
+        hp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32 if a.dtype == np.int32 else C.c_double))  # noqa: E731
+        rc = self.lib.ntm_mpc_run_est_from(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
+                                           C.byref(est.to_c()), Bn, k_sim, *[hp(a) for a, _ in state],
+                                           *[hp(v) for v in out.values()])
+        self._raise(rc, "ntm_mpc_run_est_from")
+        for dst, (src, staged) in zip((x, rho, U_old, active_ws, d_hat, x_hat), state):
+            if staged:
+                dst[...] = src
+        return out
+
     def step_kkt(self, x_k: torch.Tensor, rho_qp: torch.Tensor, U: torch.Tensor, lam: torch.Tensor | None,
                  cfg: Config | None = None):
         """The KKT audit of an MPC step's own QP (ntm_mpc_kkt_device), rebuilt in the
