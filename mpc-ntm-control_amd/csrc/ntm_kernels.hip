@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 
 #include "ntm_device.h"
@@ -609,135 +610,42 @@ bool one_wave_batch(const ntm_ctx* ctx, int64_t B) {
     return B <= lim;
 }
 
+// One launch of k_mpc_step, k_mpc_run or k_mpc_run_from (what, a) on the kernels of
+// (P, NN).  The multi-TU library keeps the one-wave N = 20 and N = 50 kernels in
+// translation units of their own and picks among them here: N = 50 by mode, N = 20 by
+// batch size (small_batch, one_wave_batch); every other (P, NN), and every horizon of a
+// single-TU build, is instantiated in this unit.
 template <int P, int NN>
-int launch_step(ntm_ctx* ctx, Prob pb, int64_t B, const double* x_k, double* rho, double* U_old,
-                double* U, double* x_pred, double* x_next, int32_t* exitflag, int32_t* inner_iters,
-                int32_t* active_ws, hipStream_t st) {
+int launch_hot(ntm_ctx* ctx, Prob pb, int64_t B, Hot what, const HotArgs& a, hipStream_t st) {
     constexpr int G = 64 / P;
 #ifndef NTM_SINGLE_TU
-    if constexpr (P == 64 && (NN == 20 || NN == 50)) {   // ntm_n20.hip, ntm_n50.hip
-        const bool near = small_batch<NN>(ctx, B);
-        size_t lds = (size_t)G * ws_bytes(pb.N, ws_far(NN) && !near);
+    constexpr bool own_tu = P == 64 && (NN == 20 || NN == 50);   // ntm_n20*.hip, ntm_n50*.hip
+#else
+    constexpr bool own_tu = false;
+#endif
+    const bool near = own_tu && small_batch<NN>(ctx, B);
+    const bool far = ws_far(NN) && !near;
+    size_t lds = (size_t)G * ws_bytes(pb.N, far);
 #ifdef NTM_LDS_PAD
-        lds += NTM_LDS_PAD;   // occupancy study only (tools/occupancy_study.sh): fewer scenarios per CU
+    if (what == Hot::step) lds += NTM_LDS_PAD;   // occupancy study only (tools/occupancy_study.sh): fewer scenarios per CU
 #endif
-        if (lds > 160 * 1024) return fail(ctx, NTM_E_UNSUPPORTED, "LDS workspace exceeds 160 KiB");
-        if (!near)
-            if (int rc = attach_far<NN>(ctx, pb, B, st)) return rc;
-        const hipError_t e =
-            NN == 50 ? (pb.mode == NTM_MODE_FULL_DU
-                            ? ntm_launch_step_n50m3(pb, B, x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters,
-                                                    active_ws, lds, st)
-                            : ntm_launch_step_n50(pb, B, x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters,
-                                                  active_ws, lds, st))
-            : near   ? (one_wave_batch<NN>(ctx, B)
-                            ? ntm_launch_step_n20near1w(pb, B, x_k, rho, U_old, U, x_pred, x_next, exitflag,
-                                                        inner_iters, active_ws, lds, st)
-                            : ntm_launch_step_n20near(pb, B, x_k, rho, U_old, U, x_pred, x_next, exitflag,
-                                                      inner_iters, active_ws, lds, st))
-                     : ntm_launch_step_n20(pb, B, x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters, active_ws,
-                                           lds, st);
-        const int rc = check_hip(ctx, e, "k_mpc_step<64,NN> launch");
-        return near ? rc : far_release<NN>(ctx, rc, st);
-    } else
-#endif
-    {
-    size_t lds = (size_t)G * ws_bytes(pb.N, ws_far(NN));
-    if (int rc = attach_far<NN>(ctx, pb, B, st)) return rc;
-#ifdef NTM_LDS_PAD
-    lds += NTM_LDS_PAD;
-#endif
-    const bool gen = pb.g.phys_on || pb.g.dist_on;     // the generator's build only when it is used
-    if (static_lds<P, NN>()) lds = 0;                  // the workspace is the kernel's static LDS
-    int rc = gen ? set_lds(ctx, k_mpc_step<P, NN, true>, lds) : set_lds(ctx, k_mpc_step<P, NN, false>, lds);
-    if (rc) return rc;
-    int64_t blocks = (B + G - 1) / G;
-    if (blocks == 0) return NTM_OK;
-    if (gen)
-        hipLaunchKernelGGL((k_mpc_step<P, NN, true>), dim3((unsigned)blocks), dim3(64), lds, st, pb, B, x_k, rho,
-                           U_old, U, x_pred, x_next, exitflag, inner_iters, active_ws);
-    else
-        hipLaunchKernelGGL((k_mpc_step<P, NN, false>), dim3((unsigned)blocks), dim3(64), lds, st, pb, B, x_k, rho,
-                           U_old, U, x_pred, x_next, exitflag, inner_iters, active_ws);
-    return far_release<NN>(ctx, check_hip(ctx, hipGetLastError(), "k_mpc_step launch"), st);
+    if (lds > 160 * 1024) return fail(ctx, NTM_E_UNSUPPORTED, "LDS workspace exceeds 160 KiB");
+    if (far)
+        if (int rc = attach_far<NN>(ctx, pb, B, st)) return rc;
+    hipError_t e;
+    if constexpr (own_tu) {
+        ntm_layout_launcher* const f = NN == 50 ? (pb.mode == NTM_MODE_FULL_DU ? ntm_launch_n50m3 : ntm_launch_n50)
+                                       : !near ? ntm_launch_n20
+                                               : (one_wave_batch<NN>(ctx, B) ? ntm_launch_n20near1w : ntm_launch_n20near);
+        e = f(what, pb, B, a, lds, st);
+    } else {
+        e = ntm_launch_hot<P, NN, ws_far(NN)>(what, pb, B, a, lds, st);
     }
-}
-
-template <int P, int NN>
-int launch_run(ntm_ctx* ctx, Prob pb, int64_t B, int k_sim, const double* x0, double* xk, double* uk,
-               double* Uk, double* wpred, int32_t* exitflag, int32_t* inner_iters, hipStream_t st) {
-    constexpr int G = 64 / P;
-#ifndef NTM_SINGLE_TU
-    if constexpr (P == 64 && (NN == 20 || NN == 50)) {   // ntm_n20.hip, ntm_n50.hip
-        const bool near = small_batch<NN>(ctx, B);
-        const size_t lds = (size_t)G * ws_bytes(pb.N, ws_far(NN) && !near);
-        if (lds > 160 * 1024) return fail(ctx, NTM_E_UNSUPPORTED, "LDS workspace exceeds 160 KiB");
-        if (!near)
-            if (int rc = attach_far<NN>(ctx, pb, B, st)) return rc;
-        const hipError_t e =
-            NN == 50 ? (pb.mode == NTM_MODE_FULL_DU
-                            ? ntm_launch_run_n50m3(pb, B, k_sim, x0, xk, uk, Uk, wpred, exitflag, inner_iters, lds, st)
-                            : ntm_launch_run_n50(pb, B, k_sim, x0, xk, uk, Uk, wpred, exitflag, inner_iters, lds, st))
-            : near   ? (one_wave_batch<NN>(ctx, B)
-                            ? ntm_launch_run_n20near1w(pb, B, k_sim, x0, xk, uk, Uk, wpred, exitflag, inner_iters, lds,
-                                                       st)
-                            : ntm_launch_run_n20near(pb, B, k_sim, x0, xk, uk, Uk, wpred, exitflag, inner_iters, lds,
-                                                     st))
-                     : ntm_launch_run_n20(pb, B, k_sim, x0, xk, uk, Uk, wpred, exitflag, inner_iters, lds, st);
-        const int rc = check_hip(ctx, e, "k_mpc_run<64,NN> launch");
-        return near ? rc : far_release<NN>(ctx, rc, st);
-    } else
-#endif
-    {
-    const size_t lds = static_lds<P, NN>() ? 0 : (size_t)G * ws_bytes(pb.N, ws_far(NN));
-    if (int rc = attach_far<NN>(ctx, pb, B, st)) return rc;
-    int rc = set_lds(ctx, k_mpc_run<P, NN>, lds);
-    if (rc) return rc;
-    int64_t blocks = (B + G - 1) / G;
-    if (blocks == 0) return NTM_OK;
-    hipLaunchKernelGGL((k_mpc_run<P, NN>), dim3((unsigned)blocks), dim3(64), lds, st, pb, B, k_sim, x0, xk, uk, Uk,
-                       wpred, exitflag, inner_iters);
-    return far_release<NN>(ctx, check_hip(ctx, hipGetLastError(), "k_mpc_run launch"), st);
-    }
-}
-
-// launch_run's dispatch for k_mpc_run_from (ntm_mpc_run_from): the same builds by the
-// same rules, with the carried state in place of x0
-template <int P, int NN>
-int launch_run_from(ntm_ctx* ctx, Prob pb, int64_t B, int k_sim, double* x, double* rho, double* U_old,
-                    int32_t* active_ws, double* xk, double* uk, double* Uk, double* wpred, int32_t* exitflag,
-                    int32_t* inner_iters, hipStream_t st) {
-    constexpr int G = 64 / P;
-#ifndef NTM_SINGLE_TU
-    if constexpr (P == 64 && (NN == 20 || NN == 50)) {   // ntm_n20.hip, ntm_n50.hip
-        const bool near = small_batch<NN>(ctx, B);
-        const size_t lds = (size_t)G * ws_bytes(pb.N, ws_far(NN) && !near);
-        if (lds > 160 * 1024) return fail(ctx, NTM_E_UNSUPPORTED, "LDS workspace exceeds 160 KiB");
-        if (!near)
-            if (int rc = attach_far<NN>(ctx, pb, B, st)) return rc;
-#define NTM_RF_ARGS pb, B, k_sim, x, rho, U_old, active_ws, xk, uk, Uk, wpred, exitflag, inner_iters, lds, st
-        const hipError_t e =
-            NN == 50 ? (pb.mode == NTM_MODE_FULL_DU ? ntm_launch_run_from_n50m3(NTM_RF_ARGS)
-                                                    : ntm_launch_run_from_n50(NTM_RF_ARGS))
-            : near   ? (one_wave_batch<NN>(ctx, B) ? ntm_launch_run_from_n20near1w(NTM_RF_ARGS)
-                                                   : ntm_launch_run_from_n20near(NTM_RF_ARGS))
-                     : ntm_launch_run_from_n20(NTM_RF_ARGS);
-#undef NTM_RF_ARGS
-        const int rc = check_hip(ctx, e, "k_mpc_run_from<64,NN> launch");
-        return near ? rc : far_release<NN>(ctx, rc, st);
-    } else
-#endif
-    {
-    const size_t lds = static_lds<P, NN>() ? 0 : (size_t)G * ws_bytes(pb.N, ws_far(NN));
-    if (int rc = attach_far<NN>(ctx, pb, B, st)) return rc;
-    int rc = set_lds(ctx, k_mpc_run_from<P, NN>, lds);
-    if (rc) return rc;
-    int64_t blocks = (B + G - 1) / G;
-    if (blocks == 0) return NTM_OK;
-    hipLaunchKernelGGL((k_mpc_run_from<P, NN>), dim3((unsigned)blocks), dim3(64), lds, st, pb, B, k_sim, x, rho, U_old,
-                       active_ws, xk, uk, Uk, wpred, exitflag, inner_iters);
-    return far_release<NN>(ctx, check_hip(ctx, hipGetLastError(), "k_mpc_run_from launch"), st);
-    }
+    static const char* const names[2][3] = {{"k_mpc_step launch", "k_mpc_run launch", "k_mpc_run_from launch"},
+                                            {"k_mpc_step<64,NN> launch", "k_mpc_run<64,NN> launch",
+                                             "k_mpc_run_from<64,NN> launch"}};
+    const int rc = check_hip(ctx, e, names[own_tu][(int)what]);
+    return far ? far_release<NN>(ctx, rc, st) : rc;
 }
 
 // hot-path dispatch: compile-time horizons for the BASELINE configs (N = 10,
@@ -776,11 +684,8 @@ bool use_generic(const ntm_config* c) {
                                                            : ((N) == 50 ? CALL(64, 50) : CALL(64, 0)))))
 #endif
 
-struct DevBuf {
-    ntm_ctx* ctx;
-    char* cur;
-    char* end;
-};
+// every horizon of the sibling kernels runs on the runtime-N build of its lane width
+#define NTM_DISPATCH_LANES(N, CALL) (lanes_for(N) == 16 ? CALL(16) : (lanes_for(N) == 32 ? CALL(32) : CALL(64)))
 
 int ensure_buf(ntm_ctx* ctx, size_t bytes) {
     if (ctx->dbuf_bytes >= bytes) return NTM_OK;
@@ -795,42 +700,85 @@ int ensure_buf(ntm_ctx* ctx, size_t bytes) {
 
 size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
 
-template <int P>
-int launch_step_dual(ntm_ctx* ctx, const Prob& pb, int64_t B, const double* x_k, double* rho, double* U_old, double* U,
-                     double* x_pred, double* x_next, int32_t* exitflag, int32_t* inner_iters, int32_t* active_ws,
-                     double* lambda, double* rho_qp, hipStream_t st) {
-    constexpr int G = 64 / P;
-    const size_t lds = (size_t)G * ws_bytes(pb.N, false);
-    if (int rc = set_lds(ctx, k_mpc_step_dual<P>, lds)) return rc;
-    const int64_t blocks = (B + G - 1) / G;
-    hipLaunchKernelGGL((k_mpc_step_dual<P>), dim3((unsigned)blocks), dim3(64), lds, st, pb, B, x_k, rho, U_old, U,
-                       x_pred, x_next, exitflag, inner_iters, active_ws, lambda, rho_qp);
-    return check_hip(ctx, hipGetLastError(), "k_mpc_step_dual launch");
+// Host staging (the entry points without _device): the host arrays of one call, each
+// given a block of ctx->dbuf (al-aligned, in the order listed) by stage_in, which also
+// copies the inputs over; after the _device form, stage_out copies the outputs back and
+// waits.  A null host pointer is an optional array the caller left out: it gets no block
+// and the _device form sees null (kReq: staged all the same, so a null array fails in its copy).  Each
+// array is listed with the device pointer that names its block, of the same element type.
+enum { kIn = 1, kOut = 2, kInOut = 3, kReq = 4 };
+struct Arr {
+    const void* h;
+    size_t bytes;
+    int dir;
+    void* slot;                       // the caller's device pointer, set through put (of its own type)
+    void (*put)(void* slot, void* d);
+    void* d = nullptr;
+    template <class T>
+    Arr(const T* host, T** dev, size_t bytes_, int dir_)
+        : h(host), bytes(bytes_), dir(dir_), slot(dev), put([](void* s, void* p) { *static_cast<T**>(s) = static_cast<T*>(p); }) {
+        *dev = nullptr;
+    }
+};
+template <size_t K>
+int stage_in(ntm_ctx* ctx, Arr (&arrs)[K]) {
+    size_t total = 0;
+    for (const Arr& a : arrs)
+        if (a.h || (a.dir & kReq)) total += al(a.bytes);
+    if (int rc = ensure_buf(ctx, total)) return rc;
+    char* p = static_cast<char*>(ctx->dbuf);
+    for (Arr& a : arrs) {
+        if (!a.h && !(a.dir & kReq)) continue;
+        a.d = p;
+        a.put(a.slot, p);
+        p += al(a.bytes);
+        if ((a.dir & kIn) && a.bytes)
+            if (int rc = check_hip(ctx, hipMemcpyAsync(a.d, a.h, a.bytes, hipMemcpyHostToDevice, ctx->stream), "H2D"))
+                return rc;
+    }
+    return NTM_OK;
 }
-template <int P>
-int launch_step_obs(ntm_ctx* ctx, const Prob& pb, int64_t B, const double* x_k, double* rho, double* U_old, double* U,
-                    double* x_pred, double* x_next, int32_t* exitflag, int32_t* inner_iters, int32_t* active_ws,
-                    double* d_hat, const ntm_observer* obs, hipStream_t st) {
-    constexpr int G = 64 / P;
-    const size_t lds = (size_t)G * ws_bytes(pb.N, false);
-    if (int rc = set_lds(ctx, k_mpc_step_obs<P>, lds)) return rc;
-    const int64_t blocks = (B + G - 1) / G;
-    hipLaunchKernelGGL((k_mpc_step_obs<P>), dim3((unsigned)blocks), dim3(64), lds, st, pb, B, x_k, rho, U_old, U,
-                       x_pred, x_next, exitflag, inner_iters, active_ws, d_hat, (int)(obs->nominal_model != 0),
-                       obs->gain);
-    return check_hip(ctx, hipGetLastError(), "k_mpc_step_obs launch");
+template <size_t K>
+int stage_out(ntm_ctx* ctx, int rc, const Arr (&arrs)[K]) {
+    if (rc) return rc;
+    for (const Arr& a : arrs)
+        if (a.d && (a.dir & kOut) && a.bytes)
+            if ((rc = check_hip(ctx, hipMemcpyAsync(const_cast<void*>(a.h), a.d, a.bytes, hipMemcpyDeviceToHost, ctx->stream),
+                                "D2H")))
+                return rc;
+    return check_hip(ctx, hipStreamSynchronize(ctx->stream), "sync");
 }
-template <int P>
-int launch_run_obs(ntm_ctx* ctx, const Prob& pb, int64_t B, int k_sim, const double* x0, const double* d0, double* xk,
-                   double* uk, double* Uk, double* wpred, double* dk, int32_t* exitflag, int32_t* inner_iters,
-                   const ntm_observer* obs, hipStream_t st) {
+// bytes of a launch's arrays: per step (x: any 2-vector; i: a flag; ws: active_ws) and
+// per closed loop of k steps (xk: a 2 x (k + 1) history; ik: a flag per step)
+struct Bytes {
+    size_t x, rho, u, xp, i, ws, xk, uk, Uk, wp, yk, ik;
+    Bytes(size_t N, size_t B, size_t k = 0)
+        : x(2 * B * 8), rho(3 * N * B * 8), u(N * B * 8), xp(2 * (N + 1) * B * 8), i(B * 4), ws(2 * (N + 1) * B * 4),
+          xk(2 * (k + 1) * B * 8), uk(k * B * 8), Uk(N * k * B * 8), wp((N + 1) * k * B * 8), yk(2 * k * B * 8),
+          ik(k * B * 4) {}
+};
+bool any_null(std::initializer_list<const void*> ptrs) {
+    for (const void* p : ptrs)
+        if (!p) return true;
+    return false;
+}
+
+// the launch's problem: the configuration, the context's counters and its generator
+Prob launch_prob(const ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg) {
+    Prob pb = make_prob(phys, cfg);
+    pb.stats = ctx->stats;
+    if (ctx->gen_on) attach_gen(ctx->gen, phys, cfg, pb);
+    return pb;
+}
+// One launch of a sibling kernel (k_mpc_step_dual, the observer's and the estimator's):
+// the all-LDS runtime-N workspace, blocks of 64 / P scenarios
+template <int P, typename K, typename... A>
+int launch_sibling(ntm_ctx* ctx, K kern, const char* what, const Prob& pb, int64_t B, hipStream_t st, A... args) {
     constexpr int G = 64 / P;
     const size_t lds = (size_t)G * ws_bytes(pb.N, false);
-    if (int rc = set_lds(ctx, k_mpc_run_obs<P>, lds)) return rc;
-    const int64_t blocks = (B + G - 1) / G;
-    hipLaunchKernelGGL((k_mpc_run_obs<P>), dim3((unsigned)blocks), dim3(64), lds, st, pb, B, k_sim, x0, d0, xk, uk, Uk,
-                       wpred, dk, exitflag, inner_iters, (int)(obs->nominal_model != 0), obs->gain);
-    return check_hip(ctx, hipGetLastError(), "k_mpc_run_obs launch");
+    if (int rc = set_lds(ctx, kern, lds)) return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((B + G - 1) / G)), dim3(64), lds, st, args...);
+    return check_hip(ctx, hipGetLastError(), what);
 }
 // the observer entry points' own checks (after validate): the options, and the literal
 // switches they do not take (D4 / D6 lift another model, D13's plant drops the offset
@@ -854,43 +802,6 @@ EstOpt est_opt(const ntm_estimator* est) {
     }
     return eo;
 }
-template <int P>
-int launch_step_est(ntm_ctx* ctx, const Prob& pb, int64_t B, const double* x_k, double* rho, double* U_old, double* U,
-                    double* x_pred, double* x_next, int32_t* exitflag, int32_t* inner_iters, int32_t* active_ws,
-                    double* d_hat, double* x_hat, double* y, const ntm_estimator* est, hipStream_t st) {
-    constexpr int G = 64 / P;
-    const size_t lds = (size_t)G * ws_bytes(pb.N, false);
-    if (int rc = set_lds(ctx, k_mpc_step_est<P>, lds)) return rc;
-    const int64_t blocks = (B + G - 1) / G;
-    hipLaunchKernelGGL((k_mpc_step_est<P>), dim3((unsigned)blocks), dim3(64), lds, st, pb, B, x_k, rho, U_old, U,
-                       x_pred, x_next, exitflag, inner_iters, active_ws, d_hat, x_hat, y, est_opt(est));
-    return check_hip(ctx, hipGetLastError(), "k_mpc_step_est launch");
-}
-template <int P>
-int launch_run_est(ntm_ctx* ctx, const Prob& pb, int64_t B, int k_sim, const double* x0, const double* d0,
-                   const double* xhat0, double* xk, double* uk, double* Uk, double* wpred, double* dk, double* xhk,
-                   double* yk, int32_t* exitflag, int32_t* inner_iters, const ntm_estimator* est, hipStream_t st) {
-    constexpr int G = 64 / P;
-    const size_t lds = (size_t)G * ws_bytes(pb.N, false);
-    if (int rc = set_lds(ctx, k_mpc_run_est<P>, lds)) return rc;
-    const int64_t blocks = (B + G - 1) / G;
-    hipLaunchKernelGGL((k_mpc_run_est<P>), dim3((unsigned)blocks), dim3(64), lds, st, pb, B, k_sim, x0, d0, xhat0, xk,
-                       uk, Uk, wpred, dk, xhk, yk, exitflag, inner_iters, est_opt(est));
-    return check_hip(ctx, hipGetLastError(), "k_mpc_run_est launch");
-}
-template <int P>
-int launch_run_est_from(ntm_ctx* ctx, const Prob& pb, int64_t B, int k_sim, double* x, double* rho, double* U_old,
-                        int32_t* active_ws, double* d_hat, double* x_hat, double* xk, double* uk, double* Uk,
-                        double* wpred, double* dk, double* xhk, double* yk, int32_t* exitflag, int32_t* inner_iters,
-                        const ntm_estimator* est, hipStream_t st) {
-    constexpr int G = 64 / P;
-    const size_t lds = (size_t)G * ws_bytes(pb.N, false);
-    if (int rc = set_lds(ctx, k_mpc_run_est_from<P>, lds)) return rc;
-    const int64_t blocks = (B + G - 1) / G;
-    hipLaunchKernelGGL((k_mpc_run_est_from<P>), dim3((unsigned)blocks), dim3(64), lds, st, pb, B, k_sim, x, rho, U_old,
-                       active_ws, d_hat, x_hat, xk, uk, Uk, wpred, dk, xhk, yk, exitflag, inner_iters, est_opt(est));
-    return check_hip(ctx, hipGetLastError(), "k_mpc_run_est_from launch");
-}
 // the estimator entry points' own checks (after validate): the options, the literal
 // switches the observer entry points refuse too, and a seed for the measurement noise
 int validate_est(ntm_ctx* ctx, const ntm_config* c, const ntm_estimator* est) {
@@ -909,6 +820,15 @@ int validate_est(ntm_ctx* ctx, const ntm_config* c, const ntm_estimator* est) {
     if (c->flags & (NTM_LITERAL_PHI_RIGHTMUL | NTM_LITERAL_GAMMA_INDEX | NTM_LITERAL_PLANT_NO_C))
         return fail(ctx, NTM_E_UNSUPPORTED, "estimator: the literal D4 / D6 / D13 switches are not supported");
     return NTM_OK;
+}
+// validate, then the feedback options' own checks
+int validate(ntm_ctx* ctx, const ntm_physics* p, const ntm_config* c, int64_t B, const ntm_observer* obs) {
+    const int rc = validate(ctx, p, c, B);
+    return rc ? rc : validate_obs(ctx, c, obs);
+}
+int validate(ntm_ctx* ctx, const ntm_physics* p, const ntm_config* c, int64_t B, const ntm_estimator* est) {
+    const int rc = validate(ctx, p, c, B);
+    return rc ? rc : validate_est(ctx, c, est);
 }
 int rows_of(const ntm_config* c) {
     return c->mode == NTM_MODE_NONE ? 0
@@ -1068,7 +988,7 @@ int ntm_ctx_step_layout_cfg(const ntm_ctx* ctx, const ntm_config* cfg, int64_t B
                             int32_t* horizon_template) {
     if (!ctx || !cfg || !far || !lanes || !horizon_template || cfg->N < 1 || cfg->N > NTM_MAX_N || B < 0)
         return NTM_E_INVALID;
-    // the same decisions launch_step makes: the dispatch (generic kernels for the
+    // the same decisions launch_hot makes: the dispatch (generic kernels for the
     // literal D4/D6 flags), then the N = 20 build by batch size, which only the
     // multi-TU library has (single-TU builds run the ws_far(20) layout throughout)
 #define INFO(P_, NN_) (*lanes = (P_), *horizon_template = (NN_), 0)
@@ -1129,385 +1049,10 @@ int ntm_mpc_step_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config*
                                   nullptr, stream);
 }
 
-int ntm_mpc_step_ws_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, int64_t B,
-                           const double* x_k, double* rho, double* U_old, double* U, double* x_pred, double* x_next,
-                           int32_t* exitflag, int32_t* inner_iters, int32_t* active_ws, void* stream) {
-    DeviceGuard dg(ctx);
-    int rc = validate(ctx, phys, cfg, B);
-    if (rc) return rc;
-    if (B == 0) return NTM_OK;
-    if (!x_k || !rho || !U_old || !U || !x_pred || !x_next || !exitflag || !inner_iters)
-        return fail(ctx, NTM_E_INVALID, "null array");
-    Prob pb = make_prob(phys, cfg);
-    pb.stats = ctx->stats;
-    if (ctx->gen_on) attach_gen(ctx->gen, phys, cfg, pb);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define CALL(P, NN) \
-    launch_step<P, NN>(ctx, pb, B, x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters, active_ws, st)
-    return NTM_DISPATCH_P(cfg->N, use_generic(cfg), CALL);
-#undef CALL
-}
-
-int ntm_mpc_step_dual_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, int64_t B,
-                             const double* x_k, double* rho, double* U_old, double* U, double* x_pred,
-                             double* x_next, int32_t* exitflag, int32_t* inner_iters, int32_t* active_ws,
-                             double* lambda, double* rho_qp, void* stream) {
-    DeviceGuard dg(ctx);
-    int rc = validate(ctx, phys, cfg, B);
-    if (rc) return rc;
-    if (B == 0) return NTM_OK;
-    if (!x_k || !rho || !U_old || !U || !x_pred || !x_next || !exitflag || !inner_iters || !rho_qp ||
-        (!lambda && rows_of(cfg) > 0))
-        return fail(ctx, NTM_E_INVALID, "null array");
-    Prob pb = make_prob(phys, cfg);
-    pb.stats = ctx->stats;
-    if (ctx->gen_on) attach_gen(ctx->gen, phys, cfg, pb);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    // every horizon on the runtime-N kernels (the export is compiled into those only)
-    const int P = lanes_for(cfg->N);
-#define CALL(P_) \
-    launch_step_dual<P_>(ctx, pb, B, x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters, active_ws, lambda, \
-                         rho_qp, st)
-    return P == 16 ? CALL(16) : (P == 32 ? CALL(32) : CALL(64));
-#undef CALL
-}
-
-int ntm_mpc_step_dual(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, int64_t B, const double* x_k,
-                      double* rho, double* U_old, double* U, double* x_pred, double* x_next, int32_t* exitflag,
-                      int32_t* inner_iters, int32_t* active_ws, double* lambda, double* rho_qp) {
-    DeviceGuard dg(ctx);
-    int rc = validate(ctx, phys, cfg, B);
-    if (rc) return rc;
-    if (B == 0) return NTM_OK;
-    const int N = cfg->N, m = rows_of(cfg);
-    if (!x_k || !rho || !U_old || !U || !x_pred || !x_next || !exitflag || !inner_iters || !rho_qp || (!lambda && m > 0))
-        return fail(ctx, NTM_E_INVALID, "null array");
-    size_t bx = al(2 * B * 8), brho = al(3 * N * B * 8), bu = al(N * B * 8), bxp = al(2 * (N + 1) * B * 8),
-           bi = al(B * 4), bws = active_ws ? al(2 * (N + 1) * B * 4) : 0, bl = al((size_t)m * B * 8);
-    rc = ensure_buf(ctx, bx * 2 + brho * 2 + bu * 2 + bxp + bi * 2 + bws + bl);
-    if (rc) return rc;
-    char* p = static_cast<char*>(ctx->dbuf);
-    double* dx = (double*)p; p += bx;
-    double* drho = (double*)p; p += brho;
-    double* duo = (double*)p; p += bu;
-    double* dU = (double*)p; p += bu;
-    double* dxp = (double*)p; p += bxp;
-    double* dxn = (double*)p; p += bx;
-    double* drq = (double*)p; p += brho;
-    double* dl = (double*)p; p += bl;
-    int32_t* dfl = (int32_t*)p; p += bi;
-    int32_t* dit = (int32_t*)p; p += bi;
-    int32_t* dws = active_ws ? (int32_t*)p : nullptr;
-    hipStream_t st = ctx->stream;
-    const size_t wsb = 2 * (size_t)(N + 1) * B * 4;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(dx, x_k, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(drho, rho, 3 * N * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(duo, U_old, N * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    if (dws && (rc = check_hip(ctx, hipMemcpyAsync(dws, active_ws, wsb, hipMemcpyHostToDevice, st), "H2D")))
-        return rc;
-    rc = ntm_mpc_step_dual_device(ctx, phys, cfg, B, dx, drho, duo, dU, dxp, dxn, dfl, dit, dws, dl, drq, st);
-    if (rc) return rc;
-    struct { void* h; const void* d; size_t n; } outs[] = {
-        {rho, drho, (size_t)3 * N * B * 8}, {U_old, duo, (size_t)N * B * 8}, {U, dU, (size_t)N * B * 8},
-        {x_pred, dxp, (size_t)2 * (N + 1) * B * 8}, {x_next, dxn, (size_t)2 * B * 8}, {exitflag, dfl, (size_t)B * 4},
-        {inner_iters, dit, (size_t)B * 4}, {active_ws, dws, wsb}, {lambda, dl, (size_t)m * B * 8},
-        {rho_qp, drq, (size_t)3 * N * B * 8}};
-    for (auto& o : outs)
-        if (o.h && o.d && o.n && (rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H")))
-            return rc;
-    return check_hip(ctx, hipStreamSynchronize(st), "sync");
-}
-
-int ntm_mpc_step_obs_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_observer* obs,
-                            int64_t B, const double* x_k, double* rho, double* U_old, double* d_hat, double* U,
-                            double* x_pred, double* x_next, int32_t* exitflag, int32_t* inner_iters,
-                            int32_t* active_ws, void* stream) {
-    DeviceGuard dg(ctx);
-    int rc = validate(ctx, phys, cfg, B);
-    if (rc) return rc;
-    if ((rc = validate_obs(ctx, cfg, obs))) return rc;
-    if (!d_hat) return fail(ctx, NTM_E_INVALID, "null d_hat");
-    if (B == 0) return NTM_OK;
-    if (!x_k || !rho || !U_old || !U || !x_pred || !x_next || !exitflag || !inner_iters)
-        return fail(ctx, NTM_E_INVALID, "null array");
-    Prob pb = make_prob(phys, cfg);
-    pb.stats = ctx->stats;
-    if (ctx->gen_on) attach_gen(ctx->gen, phys, cfg, pb);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    // every horizon on the runtime-N kernels (the observer is compiled into those only)
-    const int P = lanes_for(cfg->N);
-#define CALL(P_) \
-    launch_step_obs<P_>(ctx, pb, B, x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters, active_ws, d_hat, obs, st)
-    return P == 16 ? CALL(16) : (P == 32 ? CALL(32) : CALL(64));
-#undef CALL
-}
-
-int ntm_mpc_step_obs(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_observer* obs, int64_t B,
-                     const double* x_k, double* rho, double* U_old, double* d_hat, double* U, double* x_pred,
-                     double* x_next, int32_t* exitflag, int32_t* inner_iters, int32_t* active_ws) {
-    DeviceGuard dg(ctx);
-    int rc = validate(ctx, phys, cfg, B);
-    if (rc) return rc;
-    if ((rc = validate_obs(ctx, cfg, obs))) return rc;
-    if (!d_hat) return fail(ctx, NTM_E_INVALID, "null d_hat");
-    if (B == 0) return NTM_OK;
-    if (!x_k || !rho || !U_old || !U || !x_pred || !x_next || !exitflag || !inner_iters)
-        return fail(ctx, NTM_E_INVALID, "null array");
-    const int N = cfg->N;
-    size_t bx = al(2 * B * 8), brho = al(3 * N * B * 8), bu = al(N * B * 8), bxp = al(2 * (N + 1) * B * 8),
-           bi = al(B * 4), bws = active_ws ? al(2 * (N + 1) * B * 4) : 0;
-    rc = ensure_buf(ctx, bx * 3 + brho + bu * 2 + bxp + bi * 2 + bws);
-    if (rc) return rc;
-    char* p = static_cast<char*>(ctx->dbuf);
-    double* dx = (double*)p; p += bx;
-    double* drho = (double*)p; p += brho;
-    double* duo = (double*)p; p += bu;
-    double* dU = (double*)p; p += bu;
-    double* dxp = (double*)p; p += bxp;
-    double* dxn = (double*)p; p += bx;
-    double* ddh = (double*)p; p += bx;
-    int32_t* dfl = (int32_t*)p; p += bi;
-    int32_t* dit = (int32_t*)p; p += bi;
-    int32_t* dws = active_ws ? (int32_t*)p : nullptr;
-    hipStream_t st = ctx->stream;
-    const size_t wsb = 2 * (size_t)(N + 1) * B * 4;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(dx, x_k, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(drho, rho, 3 * N * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(duo, U_old, N * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(ddh, d_hat, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    if (dws && (rc = check_hip(ctx, hipMemcpyAsync(dws, active_ws, wsb, hipMemcpyHostToDevice, st), "H2D")))
-        return rc;
-    rc = ntm_mpc_step_obs_device(ctx, phys, cfg, obs, B, dx, drho, duo, ddh, dU, dxp, dxn, dfl, dit, dws, st);
-    if (rc) return rc;
-    struct { void* h; const void* d; size_t n; } outs[] = {
-        {rho, drho, (size_t)3 * N * B * 8}, {U_old, duo, (size_t)N * B * 8}, {d_hat, ddh, (size_t)2 * B * 8},
-        {U, dU, (size_t)N * B * 8}, {x_pred, dxp, (size_t)2 * (N + 1) * B * 8}, {x_next, dxn, (size_t)2 * B * 8},
-        {exitflag, dfl, (size_t)B * 4}, {inner_iters, dit, (size_t)B * 4}, {active_ws, dws, wsb}};
-    for (auto& o : outs)
-        if (o.h && o.d && o.n && (rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H")))
-            return rc;
-    return check_hip(ctx, hipStreamSynchronize(st), "sync");
-}
-
-int ntm_mpc_run_obs_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_observer* obs,
-                           int64_t B, int32_t k_sim, const double* x0, const double* d0, double* xk, double* uk,
-                           double* Uk, double* wpred, double* dk, int32_t* exitflag, int32_t* inner_iters,
-                           void* stream) {
-    DeviceGuard dg(ctx);
-    int rc = validate(ctx, phys, cfg, B);
-    if (rc) return rc;
-    if ((rc = validate_obs(ctx, cfg, obs))) return rc;
-    if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
-    if (B == 0) return NTM_OK;
-    if (!x0) return fail(ctx, NTM_E_INVALID, "null x0");
-    Prob pb = make_prob(phys, cfg);
-    pb.stats = ctx->stats;
-    if (ctx->gen_on) attach_gen(ctx->gen, phys, cfg, pb);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int P = lanes_for(cfg->N);
-#define CALL(P_) \
-    launch_run_obs<P_>(ctx, pb, B, k_sim, x0, d0, xk, uk, Uk, wpred, dk, exitflag, inner_iters, obs, st)
-    return P == 16 ? CALL(16) : (P == 32 ? CALL(32) : CALL(64));
-#undef CALL
-}
-
-int ntm_mpc_run_obs(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_observer* obs, int64_t B,
-                    int32_t k_sim, const double* x0, const double* d0, double* xk, double* uk, double* Uk,
-                    double* wpred, double* dk, int32_t* exitflag, int32_t* inner_iters) {
-    DeviceGuard dg(ctx);
-    int rc = validate(ctx, phys, cfg, B);
-    if (rc) return rc;
-    if ((rc = validate_obs(ctx, cfg, obs))) return rc;
-    if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
-    if (B == 0) return NTM_OK;
-    if (!x0) return fail(ctx, NTM_E_INVALID, "null x0");
-    const int N = cfg->N;
-    size_t b0 = al(2 * B * 8), bxk = al(2 * (size_t)(k_sim + 1) * B * 8), buk = al((size_t)k_sim * B * 8),
-           bUk = al((size_t)N * k_sim * B * 8), bwp = al((size_t)(N + 1) * k_sim * B * 8),
-           bi = al((size_t)k_sim * B * 4);
-    rc = ensure_buf(ctx, 2 * b0 + 2 * bxk + buk + bUk + bwp + 2 * bi);
-    if (rc) return rc;
-    char* p = static_cast<char*>(ctx->dbuf);
-    double* dx0 = (double*)p; p += b0;
-    double* dd0 = (double*)p; p += b0;
-    double* dxk = (double*)p; p += bxk;
-    double* ddk = (double*)p; p += bxk;
-    double* duk = (double*)p; p += buk;
-    double* dUk = (double*)p; p += bUk;
-    double* dwp = (double*)p; p += bwp;
-    int32_t* dfl = (int32_t*)p; p += bi;
-    int32_t* dit = (int32_t*)p;
-    hipStream_t st = ctx->stream;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(dx0, x0, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    if (d0 && (rc = check_hip(ctx, hipMemcpyAsync(dd0, d0, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    rc = ntm_mpc_run_obs_device(ctx, phys, cfg, obs, B, k_sim, dx0, d0 ? dd0 : nullptr, xk ? dxk : nullptr,
-                                uk ? duk : nullptr, Uk ? dUk : nullptr, wpred ? dwp : nullptr, dk ? ddk : nullptr,
-                                exitflag ? dfl : nullptr, inner_iters ? dit : nullptr, st);
-    if (rc) return rc;
-    struct { void* h; void* d; size_t n; } outs[] = {
-        {xk, dxk, 2 * (size_t)(k_sim + 1) * B * 8}, {uk, duk, (size_t)k_sim * B * 8},
-        {Uk, dUk, (size_t)N * k_sim * B * 8},        {wpred, dwp, (size_t)(N + 1) * k_sim * B * 8},
-        {dk, ddk, 2 * (size_t)(k_sim + 1) * B * 8}, {exitflag, dfl, (size_t)k_sim * B * 4},
-        {inner_iters, dit, (size_t)k_sim * B * 4}};
-    for (auto& o : outs)
-        if (o.h && o.n && (rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H")))
-            return rc;
-    return check_hip(ctx, hipStreamSynchronize(st), "sync");
-}
-
-int ntm_mpc_step_est_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est,
-                            int64_t B, const double* x_k, double* rho, double* U_old, double* d_hat, double* x_hat,
-                            double* U, double* x_pred, double* x_next, double* y, int32_t* exitflag,
-                            int32_t* inner_iters, int32_t* active_ws, void* stream) {
-    DeviceGuard dg(ctx);
-    int rc = validate(ctx, phys, cfg, B);
-    if (rc) return rc;
-    if ((rc = validate_est(ctx, cfg, est))) return rc;
-    if (!d_hat) return fail(ctx, NTM_E_INVALID, "null d_hat");
-    if (!x_hat) return fail(ctx, NTM_E_INVALID, "null x_hat");
-    if (B == 0) return NTM_OK;
-    if (!x_k || !rho || !U_old || !U || !x_pred || !x_next || !exitflag || !inner_iters)
-        return fail(ctx, NTM_E_INVALID, "null array");
-    Prob pb = make_prob(phys, cfg);
-    pb.stats = ctx->stats;
-    if (ctx->gen_on) attach_gen(ctx->gen, phys, cfg, pb);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    // every horizon on the runtime-N kernels (the estimator is compiled into those only)
-    const int P = lanes_for(cfg->N);
-#define CALL(P_)                                                                                                  \
-    launch_step_est<P_>(ctx, pb, B, x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters, active_ws, d_hat, \
-                        x_hat, y, est, st)
-    return P == 16 ? CALL(16) : (P == 32 ? CALL(32) : CALL(64));
-#undef CALL
-}
-
-int ntm_mpc_step_est(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est, int64_t B,
-                     const double* x_k, double* rho, double* U_old, double* d_hat, double* x_hat, double* U,
-                     double* x_pred, double* x_next, double* y, int32_t* exitflag, int32_t* inner_iters,
-                     int32_t* active_ws) {
-    DeviceGuard dg(ctx);
-    int rc = validate(ctx, phys, cfg, B);
-    if (rc) return rc;
-    if ((rc = validate_est(ctx, cfg, est))) return rc;
-    if (!d_hat) return fail(ctx, NTM_E_INVALID, "null d_hat");
-    if (!x_hat) return fail(ctx, NTM_E_INVALID, "null x_hat");
-    if (B == 0) return NTM_OK;
-    if (!x_k || !rho || !U_old || !U || !x_pred || !x_next || !exitflag || !inner_iters)
-        return fail(ctx, NTM_E_INVALID, "null array");
-    const int N = cfg->N;
-    size_t bx = al(2 * B * 8), brho = al(3 * N * B * 8), bu = al(N * B * 8), bxp = al(2 * (N + 1) * B * 8),
-           bi = al(B * 4), bws = active_ws ? al(2 * (N + 1) * B * 4) : 0;
-    rc = ensure_buf(ctx, bx * 5 + brho + bu * 2 + bxp + bi * 2 + bws);
-    if (rc) return rc;
-    char* p = static_cast<char*>(ctx->dbuf);
-    double* dx = (double*)p; p += bx;
-    double* drho = (double*)p; p += brho;
-    double* duo = (double*)p; p += bu;
-    double* dU = (double*)p; p += bu;
-    double* dxp = (double*)p; p += bxp;
-    double* dxn = (double*)p; p += bx;
-    double* ddh = (double*)p; p += bx;
-    double* dxh = (double*)p; p += bx;
-    double* dy = (double*)p; p += bx;
-    int32_t* dfl = (int32_t*)p; p += bi;
-    int32_t* dit = (int32_t*)p; p += bi;
-    int32_t* dws = active_ws ? (int32_t*)p : nullptr;
-    hipStream_t st = ctx->stream;
-    const size_t wsb = 2 * (size_t)(N + 1) * B * 4;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(dx, x_k, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(drho, rho, 3 * N * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(duo, U_old, N * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(ddh, d_hat, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(dxh, x_hat, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    if (dws && (rc = check_hip(ctx, hipMemcpyAsync(dws, active_ws, wsb, hipMemcpyHostToDevice, st), "H2D")))
-        return rc;
-    rc = ntm_mpc_step_est_device(ctx, phys, cfg, est, B, dx, drho, duo, ddh, dxh, dU, dxp, dxn, y ? dy : nullptr, dfl,
-                                 dit, dws, st);
-    if (rc) return rc;
-    struct { void* h; const void* d; size_t n; } outs[] = {
-        {rho, drho, (size_t)3 * N * B * 8}, {U_old, duo, (size_t)N * B * 8}, {d_hat, ddh, (size_t)2 * B * 8},
-        {x_hat, dxh, (size_t)2 * B * 8}, {U, dU, (size_t)N * B * 8}, {x_pred, dxp, (size_t)2 * (N + 1) * B * 8},
-        {x_next, dxn, (size_t)2 * B * 8}, {y, dy, (size_t)2 * B * 8}, {exitflag, dfl, (size_t)B * 4},
-        {inner_iters, dit, (size_t)B * 4}, {active_ws, dws, wsb}};
-    for (auto& o : outs)
-        if (o.h && o.d && o.n && (rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H")))
-            return rc;
-    return check_hip(ctx, hipStreamSynchronize(st), "sync");
-}
-
-int ntm_mpc_run_est_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est,
-                           int64_t B, int32_t k_sim, const double* x0, const double* d0, const double* xhat0,
-                           double* xk, double* uk, double* Uk, double* wpred, double* dk, double* xhk, double* yk,
-                           int32_t* exitflag, int32_t* inner_iters, void* stream) {
-    DeviceGuard dg(ctx);
-    int rc = validate(ctx, phys, cfg, B);
-    if (rc) return rc;
-    if ((rc = validate_est(ctx, cfg, est))) return rc;
-    if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
-    if (B == 0) return NTM_OK;
-    if (!x0) return fail(ctx, NTM_E_INVALID, "null x0");
-    Prob pb = make_prob(phys, cfg);
-    pb.stats = ctx->stats;
-    if (ctx->gen_on) attach_gen(ctx->gen, phys, cfg, pb);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int P = lanes_for(cfg->N);
-#define CALL(P_)                                                                                              \
-    launch_run_est<P_>(ctx, pb, B, k_sim, x0, d0, xhat0, xk, uk, Uk, wpred, dk, xhk, yk, exitflag, inner_iters, \
-                       est, st)
-    return P == 16 ? CALL(16) : (P == 32 ? CALL(32) : CALL(64));
-#undef CALL
-}
-
-int ntm_mpc_run_est(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est, int64_t B,
-                    int32_t k_sim, const double* x0, const double* d0, const double* xhat0, double* xk, double* uk,
-                    double* Uk, double* wpred, double* dk, double* xhk, double* yk, int32_t* exitflag,
-                    int32_t* inner_iters) {
-    DeviceGuard dg(ctx);
-    int rc = validate(ctx, phys, cfg, B);
-    if (rc) return rc;
-    if ((rc = validate_est(ctx, cfg, est))) return rc;
-    if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
-    if (B == 0) return NTM_OK;
-    if (!x0) return fail(ctx, NTM_E_INVALID, "null x0");
-    const int N = cfg->N;
-    size_t b0 = al(2 * B * 8), bxk = al(2 * (size_t)(k_sim + 1) * B * 8), buk = al((size_t)k_sim * B * 8),
-           bUk = al((size_t)N * k_sim * B * 8), bwp = al((size_t)(N + 1) * k_sim * B * 8),
-           byk = al(2 * (size_t)k_sim * B * 8), bi = al((size_t)k_sim * B * 4);
-    rc = ensure_buf(ctx, 3 * b0 + 3 * bxk + buk + bUk + bwp + byk + 2 * bi);
-    if (rc) return rc;
-    char* p = static_cast<char*>(ctx->dbuf);
-    double* dx0 = (double*)p; p += b0;
-    double* dd0 = (double*)p; p += b0;
-    double* dh0 = (double*)p; p += b0;
-    double* dxk = (double*)p; p += bxk;
-    double* ddk = (double*)p; p += bxk;
-    double* dxhk = (double*)p; p += bxk;
-    double* duk = (double*)p; p += buk;
-    double* dUk = (double*)p; p += bUk;
-    double* dwp = (double*)p; p += bwp;
-    double* dyk = (double*)p; p += byk;
-    int32_t* dfl = (int32_t*)p; p += bi;
-    int32_t* dit = (int32_t*)p;
-    hipStream_t st = ctx->stream;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(dx0, x0, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    if (d0 && (rc = check_hip(ctx, hipMemcpyAsync(dd0, d0, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    if (xhat0 && (rc = check_hip(ctx, hipMemcpyAsync(dh0, xhat0, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D")))
-        return rc;
-    rc = ntm_mpc_run_est_device(ctx, phys, cfg, est, B, k_sim, dx0, d0 ? dd0 : nullptr, xhat0 ? dh0 : nullptr,
-                                xk ? dxk : nullptr, uk ? duk : nullptr, Uk ? dUk : nullptr, wpred ? dwp : nullptr,
-                                dk ? ddk : nullptr, xhk ? dxhk : nullptr, yk ? dyk : nullptr,
-                                exitflag ? dfl : nullptr, inner_iters ? dit : nullptr, st);
-    if (rc) return rc;
-    struct { void* h; void* d; size_t n; } outs[] = {
-        {xk, dxk, 2 * (size_t)(k_sim + 1) * B * 8},  {uk, duk, (size_t)k_sim * B * 8},
-        {Uk, dUk, (size_t)N * k_sim * B * 8},         {wpred, dwp, (size_t)(N + 1) * k_sim * B * 8},
-        {dk, ddk, 2 * (size_t)(k_sim + 1) * B * 8},  {xhk, dxhk, 2 * (size_t)(k_sim + 1) * B * 8},
-        {yk, dyk, 2 * (size_t)k_sim * B * 8},         {exitflag, dfl, (size_t)k_sim * B * 4},
-        {inner_iters, dit, (size_t)k_sim * B * 4}};
-    for (auto& o : outs)
-        if (o.h && o.n && (rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H")))
-            return rc;
-    return check_hip(ctx, hipStreamSynchronize(st), "sync");
+int ntm_mpc_step(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, int64_t B, const double* x_k,
+                 double* rho, double* U_old, double* U, double* x_pred, double* x_next, int32_t* exitflag,
+                 int32_t* inner_iters) {
+    return ntm_mpc_step_ws(ctx, phys, cfg, B, x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters, nullptr);
 }
 
 int ntm_step_launch_info(int32_t N, int32_t* lanes, int32_t* horizon_template) {
@@ -1517,10 +1062,24 @@ int ntm_step_launch_info(int32_t N, int32_t* lanes, int32_t* horizon_template) {
 #undef INFO
 }
 
-int ntm_mpc_step(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, int64_t B, const double* x_k,
-                 double* rho, double* U_old, double* U, double* x_pred, double* x_next, int32_t* exitflag,
-                 int32_t* inner_iters) {
-    return ntm_mpc_step_ws(ctx, phys, cfg, B, x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters, nullptr);
+// Each entry point twice: the _device form (device arrays, the caller's stream; returns
+// once the work is queued) and the host form, which makes the same checks, stages its
+// arrays (stage_in), calls the _device form on the context's stream and copies back.
+#define NTM_HOT(P, NN) launch_hot<P, NN>(ctx, pb, B, what, a, st)
+int ntm_mpc_step_ws_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, int64_t B,
+                           const double* x_k, double* rho, double* U_old, double* U, double* x_pred, double* x_next,
+                           int32_t* exitflag, int32_t* inner_iters, int32_t* active_ws, void* stream) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B);
+    if (rc || B == 0) return rc;
+    if (any_null({x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters})) return fail(ctx, NTM_E_INVALID, "null array");
+    const Prob pb = launch_prob(ctx, phys, cfg);
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const Hot what = Hot::step;
+    HotArgs a{};
+    a.x_in = x_k, a.rho = rho, a.U_old = U_old, a.U = U, a.x_pred = x_pred, a.x_next = x_next;
+    a.exitflag = exitflag, a.inner_iters = inner_iters, a.active_ws = active_ws;
+    return NTM_DISPATCH_P(cfg->N, use_generic(cfg), NTM_HOT);
 }
 
 int ntm_mpc_step_ws(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, int64_t B, const double* x_k,
@@ -1528,45 +1087,224 @@ int ntm_mpc_step_ws(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg
                     int32_t* inner_iters, int32_t* active_ws) {
     DeviceGuard dg(ctx);
     int rc = validate(ctx, phys, cfg, B);
-    if (rc) return rc;
-    if (B == 0) return NTM_OK;
-    if (!x_k || !rho || !U_old || !U || !x_pred || !x_next || !exitflag || !inner_iters)
+    if (rc || B == 0) return rc;
+    if (any_null({x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters})) return fail(ctx, NTM_E_INVALID, "null array");
+    const Bytes n(cfg->N, B);
+    double *dx, *drho, *duo, *dU, *dxp, *dxn;
+    int32_t *dfl, *dit, *dws;
+    Arr arrs[] = {{x_k, &dx, n.x, kIn}, {rho, &drho, n.rho, kInOut}, {U_old, &duo, n.u, kInOut}, {U, &dU, n.u, kOut},
+                  {x_pred, &dxp, n.xp, kOut}, {x_next, &dxn, n.x, kOut}, {exitflag, &dfl, n.i, kOut},
+                  {inner_iters, &dit, n.i, kOut}, {active_ws, &dws, n.ws, kInOut}};
+    if ((rc = stage_in(ctx, arrs))) return rc;
+    rc = ntm_mpc_step_ws_device(ctx, phys, cfg, B, dx, drho, duo, dU, dxp, dxn, dfl, dit, dws, ctx->stream);
+    return stage_out(ctx, rc, arrs);
+}
+
+int ntm_mpc_step_dual_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, int64_t B,
+                             const double* x_k, double* rho, double* U_old, double* U, double* x_pred,
+                             double* x_next, int32_t* exitflag, int32_t* inner_iters, int32_t* active_ws,
+                             double* lambda, double* rho_qp, void* stream) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B);
+    if (rc || B == 0) return rc;
+    if (any_null({x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters, rho_qp}) || (!lambda && rows_of(cfg) > 0))
         return fail(ctx, NTM_E_INVALID, "null array");
-    const int N = cfg->N;
-    size_t bx = al(2 * B * 8), brho = al(3 * N * B * 8), bu = al(N * B * 8), bxp = al(2 * (N + 1) * B * 8),
-           bi = al(B * 4), bws = active_ws ? al(2 * (N + 1) * B * 4) : 0;
-    rc = ensure_buf(ctx, bx * 2 + brho + bu * 2 + bxp + bi * 2 + bws);
+    const Prob pb = launch_prob(ctx, phys, cfg);
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // every horizon on the runtime-N kernels (the export is compiled into those only)
+#define CALL(P_)                                                                                                   \
+    launch_sibling<P_>(ctx, k_mpc_step_dual<P_>, "k_mpc_step_dual launch", pb, B, st, pb, B, x_k, rho, U_old, U, \
+                       x_pred, x_next, exitflag, inner_iters, active_ws, lambda, rho_qp)
+    return NTM_DISPATCH_LANES(cfg->N, CALL);
+#undef CALL
+}
+
+int ntm_mpc_step_dual(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, int64_t B, const double* x_k,
+                      double* rho, double* U_old, double* U, double* x_pred, double* x_next, int32_t* exitflag,
+                      int32_t* inner_iters, int32_t* active_ws, double* lambda, double* rho_qp) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B);
+    if (rc || B == 0) return rc;
+    if (any_null({x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters, rho_qp}) || (!lambda && rows_of(cfg) > 0))
+        return fail(ctx, NTM_E_INVALID, "null array");
+    const Bytes n(cfg->N, B);
+    double *dx, *drho, *duo, *dU, *dxp, *dxn, *dl, *drq;
+    int32_t *dfl, *dit, *dws;
+    Arr arrs[] = {{x_k, &dx, n.x, kIn}, {rho, &drho, n.rho, kInOut}, {U_old, &duo, n.u, kInOut}, {U, &dU, n.u, kOut},
+                  {x_pred, &dxp, n.xp, kOut}, {x_next, &dxn, n.x, kOut}, {exitflag, &dfl, n.i, kOut},
+                  {inner_iters, &dit, n.i, kOut}, {active_ws, &dws, n.ws, kInOut},
+                  {lambda, &dl, (size_t)rows_of(cfg) * B * 8, kOut}, {rho_qp, &drq, n.rho, kOut}};
+    if ((rc = stage_in(ctx, arrs))) return rc;
+    rc = ntm_mpc_step_dual_device(ctx, phys, cfg, B, dx, drho, duo, dU, dxp, dxn, dfl, dit, dws, dl, drq, ctx->stream);
+    return stage_out(ctx, rc, arrs);
+}
+
+int ntm_mpc_step_obs_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_observer* obs,
+                            int64_t B, const double* x_k, double* rho, double* U_old, double* d_hat, double* U,
+                            double* x_pred, double* x_next, int32_t* exitflag, int32_t* inner_iters,
+                            int32_t* active_ws, void* stream) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B, obs);
     if (rc) return rc;
-    char* p = static_cast<char*>(ctx->dbuf);
-    double* dx = (double*)p; p += bx;
-    double* drho = (double*)p; p += brho;
-    double* duo = (double*)p; p += bu;
-    double* dU = (double*)p; p += bu;
-    double* dxp = (double*)p; p += bxp;
-    double* dxn = (double*)p; p += bx;
-    int32_t* dfl = (int32_t*)p; p += bi;
-    int32_t* dit = (int32_t*)p; p += bi;
-    int32_t* dws = active_ws ? (int32_t*)p : nullptr;
-    hipStream_t st = ctx->stream;
-    const size_t wsb = 2 * (size_t)(N + 1) * B * 4;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(dx, x_k, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(drho, rho, 3 * N * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(duo, U_old, N * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    if (dws && (rc = check_hip(ctx, hipMemcpyAsync(dws, active_ws, wsb, hipMemcpyHostToDevice, st), "H2D")))
-        return rc;
-    rc = ntm_mpc_step_ws_device(ctx, phys, cfg, B, dx, drho, duo, dU, dxp, dxn, dfl, dit, dws, st);
+    if (!d_hat) return fail(ctx, NTM_E_INVALID, "null d_hat");
+    if (B == 0) return NTM_OK;
+    if (any_null({x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters})) return fail(ctx, NTM_E_INVALID, "null array");
+    const Prob pb = launch_prob(ctx, phys, cfg);
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // every horizon on the runtime-N kernels (the observer is compiled into those only)
+#define CALL(P_)                                                                                                 \
+    launch_sibling<P_>(ctx, k_mpc_step_obs<P_>, "k_mpc_step_obs launch", pb, B, st, pb, B, x_k, rho, U_old, U, \
+                       x_pred, x_next, exitflag, inner_iters, active_ws, d_hat, (int)(obs->nominal_model != 0), \
+                       obs->gain)
+    return NTM_DISPATCH_LANES(cfg->N, CALL);
+#undef CALL
+}
+
+int ntm_mpc_step_obs(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_observer* obs, int64_t B,
+                     const double* x_k, double* rho, double* U_old, double* d_hat, double* U, double* x_pred,
+                     double* x_next, int32_t* exitflag, int32_t* inner_iters, int32_t* active_ws) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B, obs);
     if (rc) return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(rho, drho, 3 * N * B * 8, hipMemcpyDeviceToHost, st), "D2H"))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(U_old, duo, N * B * 8, hipMemcpyDeviceToHost, st), "D2H"))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(U, dU, N * B * 8, hipMemcpyDeviceToHost, st), "D2H"))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(x_pred, dxp, 2 * (N + 1) * B * 8, hipMemcpyDeviceToHost, st), "D2H")))
-        return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(x_next, dxn, 2 * B * 8, hipMemcpyDeviceToHost, st), "D2H"))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(exitflag, dfl, B * 4, hipMemcpyDeviceToHost, st), "D2H"))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(inner_iters, dit, B * 4, hipMemcpyDeviceToHost, st), "D2H"))) return rc;
-    if (dws && (rc = check_hip(ctx, hipMemcpyAsync(active_ws, dws, wsb, hipMemcpyDeviceToHost, st), "D2H")))
-        return rc;
-    return check_hip(ctx, hipStreamSynchronize(st), "sync");
+    if (!d_hat) return fail(ctx, NTM_E_INVALID, "null d_hat");
+    if (B == 0) return NTM_OK;
+    if (any_null({x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters})) return fail(ctx, NTM_E_INVALID, "null array");
+    const Bytes n(cfg->N, B);
+    double *dx, *drho, *duo, *ddh, *dU, *dxp, *dxn;
+    int32_t *dfl, *dit, *dws;
+    Arr arrs[] = {{x_k, &dx, n.x, kIn}, {rho, &drho, n.rho, kInOut}, {U_old, &duo, n.u, kInOut},
+                  {d_hat, &ddh, n.x, kInOut}, {U, &dU, n.u, kOut}, {x_pred, &dxp, n.xp, kOut},
+                  {x_next, &dxn, n.x, kOut}, {exitflag, &dfl, n.i, kOut}, {inner_iters, &dit, n.i, kOut},
+                  {active_ws, &dws, n.ws, kInOut}};
+    if ((rc = stage_in(ctx, arrs))) return rc;
+    rc = ntm_mpc_step_obs_device(ctx, phys, cfg, obs, B, dx, drho, duo, ddh, dU, dxp, dxn, dfl, dit, dws, ctx->stream);
+    return stage_out(ctx, rc, arrs);
+}
+
+int ntm_mpc_run_obs_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_observer* obs,
+                           int64_t B, int32_t k_sim, const double* x0, const double* d0, double* xk, double* uk,
+                           double* Uk, double* wpred, double* dk, int32_t* exitflag, int32_t* inner_iters,
+                           void* stream) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B, obs);
+    if (rc) return rc;
+    if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
+    if (B == 0) return NTM_OK;
+    if (!x0) return fail(ctx, NTM_E_INVALID, "null x0");
+    const Prob pb = launch_prob(ctx, phys, cfg);
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define CALL(P_)                                                                                                  \
+    launch_sibling<P_>(ctx, k_mpc_run_obs<P_>, "k_mpc_run_obs launch", pb, B, st, pb, B, k_sim, x0, d0, xk, uk, Uk, \
+                       wpred, dk, exitflag, inner_iters, (int)(obs->nominal_model != 0), obs->gain)
+    return NTM_DISPATCH_LANES(cfg->N, CALL);
+#undef CALL
+}
+
+int ntm_mpc_run_obs(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_observer* obs, int64_t B,
+                    int32_t k_sim, const double* x0, const double* d0, double* xk, double* uk, double* Uk,
+                    double* wpred, double* dk, int32_t* exitflag, int32_t* inner_iters) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B, obs);
+    if (rc) return rc;
+    if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
+    if (B == 0) return NTM_OK;
+    if (!x0) return fail(ctx, NTM_E_INVALID, "null x0");
+    const Bytes n(cfg->N, B, k_sim);
+    double *dx0, *dd0, *dxk, *duk, *dUk, *dwp, *ddk;
+    int32_t *dfl, *dit;
+    Arr arrs[] = {{x0, &dx0, n.x, kIn}, {d0, &dd0, n.x, kIn}, {xk, &dxk, n.xk, kOut}, {uk, &duk, n.uk, kOut},
+                  {Uk, &dUk, n.Uk, kOut}, {wpred, &dwp, n.wp, kOut}, {dk, &ddk, n.xk, kOut},
+                  {exitflag, &dfl, n.ik, kOut}, {inner_iters, &dit, n.ik, kOut}};
+    if ((rc = stage_in(ctx, arrs))) return rc;
+    rc = ntm_mpc_run_obs_device(ctx, phys, cfg, obs, B, k_sim, dx0, dd0, dxk, duk, dUk, dwp, ddk, dfl, dit, ctx->stream);
+    return stage_out(ctx, rc, arrs);
+}
+
+int ntm_mpc_step_est_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est,
+                            int64_t B, const double* x_k, double* rho, double* U_old, double* d_hat, double* x_hat,
+                            double* U, double* x_pred, double* x_next, double* y, int32_t* exitflag,
+                            int32_t* inner_iters, int32_t* active_ws, void* stream) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B, est);
+    if (rc) return rc;
+    if (!d_hat) return fail(ctx, NTM_E_INVALID, "null d_hat");
+    if (!x_hat) return fail(ctx, NTM_E_INVALID, "null x_hat");
+    if (B == 0) return NTM_OK;
+    if (any_null({x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters})) return fail(ctx, NTM_E_INVALID, "null array");
+    const Prob pb = launch_prob(ctx, phys, cfg);
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // every horizon on the runtime-N kernels (the estimator is compiled into those only)
+#define CALL(P_)                                                                                                 \
+    launch_sibling<P_>(ctx, k_mpc_step_est<P_>, "k_mpc_step_est launch", pb, B, st, pb, B, x_k, rho, U_old, U, \
+                       x_pred, x_next, exitflag, inner_iters, active_ws, d_hat, x_hat, y, est_opt(est))
+    return NTM_DISPATCH_LANES(cfg->N, CALL);
+#undef CALL
+}
+
+int ntm_mpc_step_est(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est, int64_t B,
+                     const double* x_k, double* rho, double* U_old, double* d_hat, double* x_hat, double* U,
+                     double* x_pred, double* x_next, double* y, int32_t* exitflag, int32_t* inner_iters,
+                     int32_t* active_ws) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B, est);
+    if (rc) return rc;
+    if (!d_hat) return fail(ctx, NTM_E_INVALID, "null d_hat");
+    if (!x_hat) return fail(ctx, NTM_E_INVALID, "null x_hat");
+    if (B == 0) return NTM_OK;
+    if (any_null({x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters})) return fail(ctx, NTM_E_INVALID, "null array");
+    const Bytes n(cfg->N, B);
+    double *dx, *drho, *duo, *ddh, *dxh, *dU, *dxp, *dxn, *dy;
+    int32_t *dfl, *dit, *dws;
+    Arr arrs[] = {{x_k, &dx, n.x, kIn}, {rho, &drho, n.rho, kInOut}, {U_old, &duo, n.u, kInOut},
+                  {d_hat, &ddh, n.x, kInOut}, {x_hat, &dxh, n.x, kInOut}, {U, &dU, n.u, kOut},
+                  {x_pred, &dxp, n.xp, kOut}, {x_next, &dxn, n.x, kOut}, {y, &dy, n.x, kOut},
+                  {exitflag, &dfl, n.i, kOut}, {inner_iters, &dit, n.i, kOut}, {active_ws, &dws, n.ws, kInOut}};
+    if ((rc = stage_in(ctx, arrs))) return rc;
+    rc = ntm_mpc_step_est_device(ctx, phys, cfg, est, B, dx, drho, duo, ddh, dxh, dU, dxp, dxn, dy, dfl, dit, dws,
+                                 ctx->stream);
+    return stage_out(ctx, rc, arrs);
+}
+
+int ntm_mpc_run_est_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est,
+                           int64_t B, int32_t k_sim, const double* x0, const double* d0, const double* xhat0,
+                           double* xk, double* uk, double* Uk, double* wpred, double* dk, double* xhk, double* yk,
+                           int32_t* exitflag, int32_t* inner_iters, void* stream) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B, est);
+    if (rc) return rc;
+    if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
+    if (B == 0) return NTM_OK;
+    if (!x0) return fail(ctx, NTM_E_INVALID, "null x0");
+    const Prob pb = launch_prob(ctx, phys, cfg);
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define CALL(P_)                                                                                                   \
+    launch_sibling<P_>(ctx, k_mpc_run_est<P_>, "k_mpc_run_est launch", pb, B, st, pb, B, k_sim, x0, d0, xhat0, xk, \
+                       uk, Uk, wpred, dk, xhk, yk, exitflag, inner_iters, est_opt(est))
+    return NTM_DISPATCH_LANES(cfg->N, CALL);
+#undef CALL
+}
+
+int ntm_mpc_run_est(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est, int64_t B,
+                    int32_t k_sim, const double* x0, const double* d0, const double* xhat0, double* xk, double* uk,
+                    double* Uk, double* wpred, double* dk, double* xhk, double* yk, int32_t* exitflag,
+                    int32_t* inner_iters) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B, est);
+    if (rc) return rc;
+    if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
+    if (B == 0) return NTM_OK;
+    if (!x0) return fail(ctx, NTM_E_INVALID, "null x0");
+    const Bytes n(cfg->N, B, k_sim);
+    double *dx0, *dd0, *dh0, *dxk, *duk, *dUk, *dwp, *ddk, *dxhk, *dyk;
+    int32_t *dfl, *dit;
+    Arr arrs[] = {{x0, &dx0, n.x, kIn}, {d0, &dd0, n.x, kIn}, {xhat0, &dh0, n.x, kIn}, {xk, &dxk, n.xk, kOut},
+                  {uk, &duk, n.uk, kOut}, {Uk, &dUk, n.Uk, kOut}, {wpred, &dwp, n.wp, kOut}, {dk, &ddk, n.xk, kOut},
+                  {xhk, &dxhk, n.xk, kOut}, {yk, &dyk, n.yk, kOut}, {exitflag, &dfl, n.ik, kOut},
+                  {inner_iters, &dit, n.ik, kOut}};
+    if ((rc = stage_in(ctx, arrs))) return rc;
+    rc = ntm_mpc_run_est_device(ctx, phys, cfg, est, B, k_sim, dx0, dd0, dh0, dxk, duk, dUk, dwp, ddk, dxhk, dyk, dfl,
+                                dit, ctx->stream);
+    return stage_out(ctx, rc, arrs);
 }
 
 int ntm_mpc_run_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, int64_t B, int32_t k_sim,
@@ -1578,13 +1316,13 @@ int ntm_mpc_run_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* 
     if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
     if (B == 0) return NTM_OK;
     if (!x0) return fail(ctx, NTM_E_INVALID, "null x0");
-    Prob pb = make_prob(phys, cfg);
-    pb.stats = ctx->stats;
-    if (ctx->gen_on) attach_gen(ctx->gen, phys, cfg, pb);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define CALL(P, NN) launch_run<P, NN>(ctx, pb, B, k_sim, x0, xk, uk, Uk, wpred, exitflag, inner_iters, st)
-    return NTM_DISPATCH_P(cfg->N, use_generic(cfg), CALL);
-#undef CALL
+    const Prob pb = launch_prob(ctx, phys, cfg);
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const Hot what = Hot::run;
+    HotArgs a{};
+    a.k_sim = k_sim, a.x_in = x0, a.xk = xk, a.uk = uk, a.Uk = Uk, a.wpred = wpred;
+    a.exitflag = exitflag, a.inner_iters = inner_iters;
+    return NTM_DISPATCH_P(cfg->N, use_generic(cfg), NTM_HOT);
 }
 
 int ntm_mpc_run(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, int64_t B, int32_t k_sim,
@@ -1595,34 +1333,15 @@ int ntm_mpc_run(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, in
     if (rc) return rc;
     if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
     if (B == 0) return NTM_OK;
-    const int N = cfg->N;
-    size_t b0 = al(2 * B * 8), bxk = al(2 * (size_t)(k_sim + 1) * B * 8), buk = al((size_t)k_sim * B * 8),
-           bUk = al((size_t)N * k_sim * B * 8), bwp = al((size_t)(N + 1) * k_sim * B * 8),
-           bi = al((size_t)k_sim * B * 4);
-    rc = ensure_buf(ctx, b0 + bxk + buk + bUk + bwp + 2 * bi);
-    if (rc) return rc;
-    char* p = static_cast<char*>(ctx->dbuf);
-    double* d0 = (double*)p; p += b0;
-    double* dxk = (double*)p; p += bxk;
-    double* duk = (double*)p; p += buk;
-    double* dUk = (double*)p; p += bUk;
-    double* dwp = (double*)p; p += bwp;
-    int32_t* dfl = (int32_t*)p; p += bi;
-    int32_t* dit = (int32_t*)p;
-    hipStream_t st = ctx->stream;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(d0, x0, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    rc = ntm_mpc_run_device(ctx, phys, cfg, B, k_sim, d0, xk ? dxk : nullptr, uk ? duk : nullptr,
-                            Uk ? dUk : nullptr, wpred ? dwp : nullptr, exitflag ? dfl : nullptr,
-                            inner_iters ? dit : nullptr, st);
-    if (rc) return rc;
-    struct { void* h; void* d; size_t n; } outs[] = {
-        {xk, dxk, 2 * (size_t)(k_sim + 1) * B * 8}, {uk, duk, (size_t)k_sim * B * 8},
-        {Uk, dUk, (size_t)N * k_sim * B * 8},        {wpred, dwp, (size_t)(N + 1) * k_sim * B * 8},
-        {exitflag, dfl, (size_t)k_sim * B * 4},      {inner_iters, dit, (size_t)k_sim * B * 4}};
-    for (auto& o : outs)
-        if (o.h && (rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H")))
-            return rc;
-    return check_hip(ctx, hipStreamSynchronize(st), "sync");
+    const Bytes n(cfg->N, B, k_sim);
+    double *dx0, *dxk, *duk, *dUk, *dwp;
+    int32_t *dfl, *dit;
+    // x0 is not checked here, unlike in the other run forms: a null x0 fails in its copy (kReq)
+    Arr arrs[] = {{x0, &dx0, n.x, kIn | kReq}, {xk, &dxk, n.xk, kOut}, {uk, &duk, n.uk, kOut}, {Uk, &dUk, n.Uk, kOut},
+                  {wpred, &dwp, n.wp, kOut}, {exitflag, &dfl, n.ik, kOut}, {inner_iters, &dit, n.ik, kOut}};
+    if ((rc = stage_in(ctx, arrs))) return rc;
+    rc = ntm_mpc_run_device(ctx, phys, cfg, B, k_sim, dx0, dxk, duk, dUk, dwp, dfl, dit, ctx->stream);
+    return stage_out(ctx, rc, arrs);
 }
 
 int ntm_mpc_run_from_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, int64_t B, int32_t k_sim,
@@ -1632,20 +1351,17 @@ int ntm_mpc_run_from_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_con
     int rc = validate(ctx, phys, cfg, B);
     if (rc) return rc;
     if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
-    if (!x || !rho || !U_old || !active_ws) return fail(ctx, NTM_E_INVALID, "null state array");
+    if (any_null({x, rho, U_old, active_ws})) return fail(ctx, NTM_E_INVALID, "null state array");
     if (B == 0) return NTM_OK;
-    Prob pb = make_prob(phys, cfg);
-    pb.stats = ctx->stats;
-    if (ctx->gen_on) attach_gen(ctx->gen, phys, cfg, pb);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define CALL(P, NN) \
-    launch_run_from<P, NN>(ctx, pb, B, k_sim, x, rho, U_old, active_ws, xk, uk, Uk, wpred, exitflag, inner_iters, st)
-    return NTM_DISPATCH_P(cfg->N, use_generic(cfg), CALL);
-#undef CALL
+    const Prob pb = launch_prob(ctx, phys, cfg);
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const Hot what = Hot::run_from;
+    HotArgs a{};
+    a.k_sim = k_sim, a.x = x, a.rho = rho, a.U_old = U_old, a.active_ws = active_ws;
+    a.xk = xk, a.uk = uk, a.Uk = Uk, a.wpred = wpred, a.exitflag = exitflag, a.inner_iters = inner_iters;
+    return NTM_DISPATCH_P(cfg->N, use_generic(cfg), NTM_HOT);
 }
-
-// host staging of the carried state: {host, device, bytes} of each in/out array
-struct StateBuf { void* h; void* d; size_t n; };
+#undef NTM_HOT
 
 int ntm_mpc_run_from(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, int64_t B, int32_t k_sim,
                      double* x, double* rho, double* U_old, int32_t* active_ws, double* xk, double* uk, double* Uk,
@@ -1654,45 +1370,18 @@ int ntm_mpc_run_from(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cf
     int rc = validate(ctx, phys, cfg, B);
     if (rc) return rc;
     if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
-    if (!x || !rho || !U_old || !active_ws) return fail(ctx, NTM_E_INVALID, "null state array");
+    if (any_null({x, rho, U_old, active_ws})) return fail(ctx, NTM_E_INVALID, "null state array");
     if (B == 0) return NTM_OK;
-    const int N = cfg->N;
-    size_t b0 = al(2 * B * 8), brho = al((size_t)3 * N * B * 8), bu = al((size_t)N * B * 8),
-           bws = al(2 * (size_t)(N + 1) * B * 4), bxk = al(2 * (size_t)(k_sim + 1) * B * 8),
-           buk = al((size_t)k_sim * B * 8), bUk = al((size_t)N * k_sim * B * 8),
-           bwp = al((size_t)(N + 1) * k_sim * B * 8), bi = al((size_t)k_sim * B * 4);
-    rc = ensure_buf(ctx, b0 + brho + bu + bws + bxk + buk + bUk + bwp + 2 * bi);
-    if (rc) return rc;
-    char* p = static_cast<char*>(ctx->dbuf);
-    double* dx = (double*)p; p += b0;
-    double* drho = (double*)p; p += brho;
-    double* duo = (double*)p; p += bu;
-    int32_t* dws = (int32_t*)p; p += bws;
-    double* dxk = (double*)p; p += bxk;
-    double* duk = (double*)p; p += buk;
-    double* dUk = (double*)p; p += bUk;
-    double* dwp = (double*)p; p += bwp;
-    int32_t* dfl = (int32_t*)p; p += bi;
-    int32_t* dit = (int32_t*)p;
-    hipStream_t st = ctx->stream;
-    const StateBuf state[] = {{x, dx, 2 * (size_t)B * 8}, {rho, drho, (size_t)3 * N * B * 8},
-                              {U_old, duo, (size_t)N * B * 8}, {active_ws, dws, 2 * (size_t)(N + 1) * B * 4}};
-    for (auto& o : state)
-        if ((rc = check_hip(ctx, hipMemcpyAsync(o.d, o.h, o.n, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    rc = ntm_mpc_run_from_device(ctx, phys, cfg, B, k_sim, dx, drho, duo, dws, xk ? dxk : nullptr, uk ? duk : nullptr,
-                                 Uk ? dUk : nullptr, wpred ? dwp : nullptr, exitflag ? dfl : nullptr,
-                                 inner_iters ? dit : nullptr, st);
-    if (rc) return rc;
-    for (auto& o : state)
-        if ((rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H"))) return rc;
-    struct { void* h; void* d; size_t n; } outs[] = {
-        {xk, dxk, 2 * (size_t)(k_sim + 1) * B * 8}, {uk, duk, (size_t)k_sim * B * 8},
-        {Uk, dUk, (size_t)N * k_sim * B * 8},        {wpred, dwp, (size_t)(N + 1) * k_sim * B * 8},
-        {exitflag, dfl, (size_t)k_sim * B * 4},      {inner_iters, dit, (size_t)k_sim * B * 4}};
-    for (auto& o : outs)
-        if (o.h && o.n && (rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H")))
-            return rc;
-    return check_hip(ctx, hipStreamSynchronize(st), "sync");
+    const Bytes n(cfg->N, B, k_sim);
+    double *dx, *drho, *duo, *dxk, *duk, *dUk, *dwp;
+    int32_t *dws, *dfl, *dit;
+    Arr arrs[] = {{x, &dx, n.x, kInOut}, {rho, &drho, n.rho, kInOut}, {U_old, &duo, n.u, kInOut},
+                  {active_ws, &dws, n.ws, kInOut}, {xk, &dxk, n.xk, kOut}, {uk, &duk, n.uk, kOut},
+                  {Uk, &dUk, n.Uk, kOut}, {wpred, &dwp, n.wp, kOut}, {exitflag, &dfl, n.ik, kOut},
+                  {inner_iters, &dit, n.ik, kOut}};
+    if ((rc = stage_in(ctx, arrs))) return rc;
+    rc = ntm_mpc_run_from_device(ctx, phys, cfg, B, k_sim, dx, drho, duo, dws, dxk, duk, dUk, dwp, dfl, dit, ctx->stream);
+    return stage_out(ctx, rc, arrs);
 }
 
 int ntm_mpc_run_est_from_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est,
@@ -1701,21 +1390,18 @@ int ntm_mpc_run_est_from_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm
                                 double* dk, double* xhk, double* yk, int32_t* exitflag, int32_t* inner_iters,
                                 void* stream) {
     DeviceGuard dg(ctx);
-    int rc = validate(ctx, phys, cfg, B);
+    int rc = validate(ctx, phys, cfg, B, est);
     if (rc) return rc;
-    if ((rc = validate_est(ctx, cfg, est))) return rc;
     if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
-    if (!x || !rho || !U_old || !active_ws || !d_hat || !x_hat) return fail(ctx, NTM_E_INVALID, "null state array");
+    if (any_null({x, rho, U_old, active_ws, d_hat, x_hat})) return fail(ctx, NTM_E_INVALID, "null state array");
     if (B == 0) return NTM_OK;
-    Prob pb = make_prob(phys, cfg);
-    pb.stats = ctx->stats;
-    if (ctx->gen_on) attach_gen(ctx->gen, phys, cfg, pb);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int P = lanes_for(cfg->N);
-#define CALL(P_)                                                                                                  \
-    launch_run_est_from<P_>(ctx, pb, B, k_sim, x, rho, U_old, active_ws, d_hat, x_hat, xk, uk, Uk, wpred, dk, xhk, \
-                            yk, exitflag, inner_iters, est, st)
-    return P == 16 ? CALL(16) : (P == 32 ? CALL(32) : CALL(64));
+    const Prob pb = launch_prob(ctx, phys, cfg);
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define CALL(P_)                                                                                                    \
+    launch_sibling<P_>(ctx, k_mpc_run_est_from<P_>, "k_mpc_run_est_from launch", pb, B, st, pb, B, k_sim, x, rho, \
+                       U_old, active_ws, d_hat, x_hat, xk, uk, Uk, wpred, dk, xhk, yk, exitflag, inner_iters,     \
+                       est_opt(est))
+    return NTM_DISPATCH_LANES(cfg->N, CALL);
 #undef CALL
 }
 
@@ -1724,59 +1410,23 @@ int ntm_mpc_run_est_from(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config
                          double* d_hat, double* x_hat, double* xk, double* uk, double* Uk, double* wpred, double* dk,
                          double* xhk, double* yk, int32_t* exitflag, int32_t* inner_iters) {
     DeviceGuard dg(ctx);
-    int rc = validate(ctx, phys, cfg, B);
+    int rc = validate(ctx, phys, cfg, B, est);
     if (rc) return rc;
-    if ((rc = validate_est(ctx, cfg, est))) return rc;
     if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
-    if (!x || !rho || !U_old || !active_ws || !d_hat || !x_hat) return fail(ctx, NTM_E_INVALID, "null state array");
+    if (any_null({x, rho, U_old, active_ws, d_hat, x_hat})) return fail(ctx, NTM_E_INVALID, "null state array");
     if (B == 0) return NTM_OK;
-    const int N = cfg->N;
-    size_t b0 = al(2 * B * 8), brho = al((size_t)3 * N * B * 8), bu = al((size_t)N * B * 8),
-           bws = al(2 * (size_t)(N + 1) * B * 4), bxk = al(2 * (size_t)(k_sim + 1) * B * 8),
-           buk = al((size_t)k_sim * B * 8), bUk = al((size_t)N * k_sim * B * 8),
-           bwp = al((size_t)(N + 1) * k_sim * B * 8), byk = al(2 * (size_t)k_sim * B * 8),
-           bi = al((size_t)k_sim * B * 4);
-    rc = ensure_buf(ctx, 3 * b0 + brho + bu + bws + 3 * bxk + buk + bUk + bwp + byk + 2 * bi);
-    if (rc) return rc;
-    char* p = static_cast<char*>(ctx->dbuf);
-    double* dx = (double*)p; p += b0;
-    double* ddh = (double*)p; p += b0;
-    double* dxh = (double*)p; p += b0;
-    double* drho = (double*)p; p += brho;
-    double* duo = (double*)p; p += bu;
-    int32_t* dws = (int32_t*)p; p += bws;
-    double* dxk = (double*)p; p += bxk;
-    double* ddk = (double*)p; p += bxk;
-    double* dxhk = (double*)p; p += bxk;
-    double* duk = (double*)p; p += buk;
-    double* dUk = (double*)p; p += bUk;
-    double* dwp = (double*)p; p += bwp;
-    double* dyk = (double*)p; p += byk;
-    int32_t* dfl = (int32_t*)p; p += bi;
-    int32_t* dit = (int32_t*)p;
-    hipStream_t st = ctx->stream;
-    const StateBuf state[] = {{x, dx, 2 * (size_t)B * 8},     {d_hat, ddh, 2 * (size_t)B * 8},
-                              {x_hat, dxh, 2 * (size_t)B * 8}, {rho, drho, (size_t)3 * N * B * 8},
-                              {U_old, duo, (size_t)N * B * 8}, {active_ws, dws, 2 * (size_t)(N + 1) * B * 4}};
-    for (auto& o : state)
-        if ((rc = check_hip(ctx, hipMemcpyAsync(o.d, o.h, o.n, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    rc = ntm_mpc_run_est_from_device(ctx, phys, cfg, est, B, k_sim, dx, drho, duo, dws, ddh, dxh, xk ? dxk : nullptr,
-                                     uk ? duk : nullptr, Uk ? dUk : nullptr, wpred ? dwp : nullptr,
-                                     dk ? ddk : nullptr, xhk ? dxhk : nullptr, yk ? dyk : nullptr,
-                                     exitflag ? dfl : nullptr, inner_iters ? dit : nullptr, st);
-    if (rc) return rc;
-    for (auto& o : state)
-        if ((rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H"))) return rc;
-    struct { void* h; void* d; size_t n; } outs[] = {
-        {xk, dxk, 2 * (size_t)(k_sim + 1) * B * 8},  {uk, duk, (size_t)k_sim * B * 8},
-        {Uk, dUk, (size_t)N * k_sim * B * 8},         {wpred, dwp, (size_t)(N + 1) * k_sim * B * 8},
-        {dk, ddk, 2 * (size_t)(k_sim + 1) * B * 8},  {xhk, dxhk, 2 * (size_t)(k_sim + 1) * B * 8},
-        {yk, dyk, 2 * (size_t)k_sim * B * 8},         {exitflag, dfl, (size_t)k_sim * B * 4},
-        {inner_iters, dit, (size_t)k_sim * B * 4}};
-    for (auto& o : outs)
-        if (o.h && o.n && (rc = check_hip(ctx, hipMemcpyAsync(o.h, o.d, o.n, hipMemcpyDeviceToHost, st), "D2H")))
-            return rc;
-    return check_hip(ctx, hipStreamSynchronize(st), "sync");
+    const Bytes n(cfg->N, B, k_sim);
+    double *dx, *drho, *duo, *ddh, *dxh, *dxk, *duk, *dUk, *dwp, *ddk, *dxhk, *dyk;
+    int32_t *dws, *dfl, *dit;
+    Arr arrs[] = {{x, &dx, n.x, kInOut}, {rho, &drho, n.rho, kInOut}, {U_old, &duo, n.u, kInOut},
+                  {active_ws, &dws, n.ws, kInOut}, {d_hat, &ddh, n.x, kInOut}, {x_hat, &dxh, n.x, kInOut},
+                  {xk, &dxk, n.xk, kOut}, {uk, &duk, n.uk, kOut}, {Uk, &dUk, n.Uk, kOut}, {wpred, &dwp, n.wp, kOut},
+                  {dk, &ddk, n.xk, kOut}, {xhk, &dxhk, n.xk, kOut}, {yk, &dyk, n.yk, kOut},
+                  {exitflag, &dfl, n.ik, kOut}, {inner_iters, &dit, n.ik, kOut}};
+    if ((rc = stage_in(ctx, arrs))) return rc;
+    rc = ntm_mpc_run_est_from_device(ctx, phys, cfg, est, B, k_sim, dx, drho, duo, dws, ddh, dxh, dxk, duk, dUk, dwp, ddk,
+                                     dxhk, dyk, dfl, dit, ctx->stream);
+    return stage_out(ctx, rc, arrs);
 }
 
 int ntm_rho_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, int64_t B, const double* x,
@@ -1808,19 +1458,12 @@ int ntm_mpc_init(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, i
     int rc = validate(ctx, phys, cfg, B);
     if (rc || B == 0) return rc;
     if (!x0 || !rho || !U_old) return fail(ctx, NTM_E_INVALID, "null array");
-    const int N = cfg->N;
-    size_t bx = al(2 * B * 8), brho = al(3 * N * B * 8), bu = al(N * B * 8);
-    if ((rc = ensure_buf(ctx, bx + brho + bu))) return rc;
-    char* p = static_cast<char*>(ctx->dbuf);
-    double* dx = (double*)p; p += bx;
-    double* drho = (double*)p; p += brho;
-    double* duo = (double*)p;
-    hipStream_t st = ctx->stream;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(dx, x0, 2 * B * 8, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-    if ((rc = ntm_mpc_init_device(ctx, phys, cfg, B, dx, drho, duo, st))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(rho, drho, 3 * N * B * 8, hipMemcpyDeviceToHost, st), "D2H"))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(U_old, duo, N * B * 8, hipMemcpyDeviceToHost, st), "D2H"))) return rc;
-    return check_hip(ctx, hipStreamSynchronize(st), "sync");
+    const Bytes n(cfg->N, B);
+    double *dx, *drho, *duo;
+    Arr arrs[] = {{x0, &dx, n.x, kIn}, {rho, &drho, n.rho, kOut}, {U_old, &duo, n.u, kOut}};
+    if ((rc = stage_in(ctx, arrs))) return rc;
+    rc = ntm_mpc_init_device(ctx, phys, cfg, B, dx, drho, duo, ctx->stream);
+    return stage_out(ctx, rc, arrs);
 }
 
 int ntm_AB_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, int64_t B, const double* rho,

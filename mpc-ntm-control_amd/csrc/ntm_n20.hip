@@ -46,4 +46,4 @@
 #endif
 static_assert(!ntm::rate_rows<ntm::WS<20, false, ntm::ws_far(20)>>() && !ntm::rate_rows<ntm::WS<20, true, ntm::ws_far(20)>>(),
               "the kernels of this unit are built without rate rows; its launchers refuse mode 3 (ntm_mode_built)");
-NTM_DEFINE_LAYOUT_LAUNCHERS(n20, 20, ntm::ws_far(20))
+NTM_DEFINE_LAYOUT_LAUNCHER(n20, 20, ntm::ws_far(20))

@@ -11,4 +11,4 @@
 #define NTM_CH NTM_N20NEAR_CH
 #include "ntm_step.h"
 
-NTM_DEFINE_LAYOUT_LAUNCHERS(n20near, 20, false)
+NTM_DEFINE_LAYOUT_LAUNCHER(n20near, 20, false)

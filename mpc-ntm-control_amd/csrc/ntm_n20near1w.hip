@@ -15,4 +15,4 @@
 #define NTM_HOT_WAVES_PER_EU 1
 #include "ntm_step.h"
 
-NTM_DEFINE_LAYOUT_LAUNCHERS(n20near1w, 20, false)
+NTM_DEFINE_LAYOUT_LAUNCHER(n20near1w, 20, false)

@@ -24,4 +24,4 @@
 #endif
 #include "ntm_step.h"
 
-NTM_DEFINE_LAYOUT_LAUNCHERS(n50, 50, true)
+NTM_DEFINE_LAYOUT_LAUNCHER(n50, 50, true)

@@ -21,4 +21,4 @@
 #endif
 #include "ntm_step.h"
 
-NTM_DEFINE_LAYOUT_LAUNCHERS(n50m3, 50, true)
+NTM_DEFINE_LAYOUT_LAUNCHER(n50m3, 50, true)

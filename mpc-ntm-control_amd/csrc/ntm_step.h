@@ -186,33 +186,127 @@ __device__ __forceinline__ int mpc_step_dev(const Prob& pb, const W& w, double x
 template <int P, int NN>
 __host__ __device__ constexpr bool static_lds() { return NTM_STATIC_LDS && P == 64 && NN > 0; }
 
+// ---------------------------------------------------------------- the kernels' shared pieces
+// The ten kernels below are siblings, not flags of one another (their argument blocks
+// differ: DESIGN.md §4a); what they have in common is written once here.  How much can be
+// an inline function is decided by the register allocator, not by taste: a piece stays a
+// function only where every production instantiation of every kernel that uses it keeps its
+// spill counts, scratch and occupancy (tools/asm_digest.sh --per-kernel, profiles/fold/).
+// That holds for the prologue (all ten kernels) and for start_from_state (the three
+// sibling step kernels and the two _from kernels).  The closed loops and the Rho = rho(x0)
+// start change the allocation of their kernels even as functions holding the same
+// statements, so they are shared as text: macros on the kernel's own names, expanded to the
+// tokens each kernel had.  The step epilogues differ from kernel to kernel and stay there.
+
+// Block and lane to group g, lane l and scenario s of the launch (s >= B: none, the caller
+// returns).  The diagnostic builds' hooks sit here, so every kernel has them: the stamps
+// (make diag; each kernel ends with NTM_STAMPS_FLUSH) and the traced scenario (make trace).
+struct Lanes { int g, l; int64_t s; };
+template <int P>
+__device__ __forceinline__ Lanes scn_lanes() {
+    constexpr int G = 64 / P;
+    const int g = threadIdx.x / P, l = threadIdx.x % P;
+    const int64_t s = xcd_swizzle(blockIdx.x, gridDim.x) * G + g;
+    NTM_STAMPS_INIT();
+    NTM_TRACE_SET(s, g, l);
+    return {g, l, s};
+}
+// debug build (make poison): the workspace starts as NTM_POISON-valued doubles, so
+// a read of LDS this launch never wrote shows up as a run-to-run difference
+// (tools/determinism.py + compare_runs.py; this found the x_0-row read of rinfo[-1])
+template <int P>
+__device__ __forceinline__ void ws_poison(char* sbase, int bytes, int l) {
+#ifdef NTM_POISON
+    for (int e = l; e < bytes / 8; e += P) reinterpret_cast<double*>(sbase)[e] = NTM_POISON;
+    NTM_WSYNC();
+#endif
+}
+// Group g's workspace bytes: its slice of the launch's dynamic LDS, or the kernel's static
+// array (static_lds).  Carved by ws_carve<NN, GEN, FAR> or, for the observer kernels, ws_carve_obs.
+template <int P, int NN, bool FAR>
+__device__ __forceinline__ char* scn_lds(int N, int g, int l) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* sbase = smem + g * ws_bytes(N, FAR);
+    if constexpr (static_lds<P, NN>()) {
+        __shared__ __attribute__((aligned(16))) char smem_s[ws_bytes(NN > 0 ? NN : 1, FAR)];
+        sbase = smem_s;
+    }
+    ws_poison<P>(sbase, ws_bytes(N, FAR), l);
+    return sbase;
+}
+
+// A step from the caller's state: the candidate sets (null for a step kernel: none), rho, U_old
+template <int P, bool RUN, class W>
+__device__ __forceinline__ void start_from_state(const Prob& pb, const W& w, int64_t B, int64_t s, const double* rho,
+                                                 const double* U_old, const int32_t* active_ws, int l) {
+    if (RUN || active_ws) {
+        load_candidates<P, W, RUN>(pb, w, B, s, active_ws, l);
+    } else if (l < 2) {
+        w.cand()[l * (w.n() + 1) + w.n()] = -1;
+    }
+    load_state<P>(w, B, s, rho, U_old, l);
+}
+
+
+// Closed-loop start, k_mpc_run / _run_obs / _run_est: Rho = repmat(rho(A0, A1), 1, N) from the
+// model's coefficients K (NTM_MPC_Sim.m:63-65), Uold = +inf (D14).  Uses the kernel's w, N, l.
+#define NTM_START_FROM_X0(K, A0, A1)                                                                                  \
+    {   /* Rho = repmat(rho(x0), 1, N) (NTM_MPC_Sim.m:63-65); Uold = +inf (D14) */                                    \
+        double r1, r2, r3;                                                                                            \
+        rho_eval(K, A0, A1, r1, r2, r3);                                                                              \
+        if (l < N) {                                                                                                  \
+            w.rho()[3 * l] = r1;                                                                                      \
+            w.rho()[3 * l + 1] = r2;                                                                                  \
+            w.rho()[3 * l + 2] = r3;                                                                                  \
+            w.Uold()[l] = kInf;                                                                                       \
+        }                                                                                                             \
+        NTM_WSYNC();                                                                                                  \
+    }
+
+// k_mpc_run's loop and k_mpc_run_from's, on the kernel's pb, w, N, B, s, l, k_sim, the state
+// x0, x1 and the history arrays xk, uk, Uk, wpred, exitflag, inner_iters (each may be null).
+// It leaves the workspace as the next step reads it and x0, x1 as the plant's state.
+// s is int64_t, so every offset is formed in 64 bits.
+#define NTM_RUN_LOOP                                                                                                  \
+    if (xk && l == 0) { xk[s * 2 * (k_sim + 1)] = x0; xk[s * 2 * (k_sim + 1) + 1] = x1; }                             \
+    for (int kk = 0; kk < k_sim; ++kk) {                                                                              \
+        int its;                                                                                                      \
+        int flag = mpc_step_dev<P>(pb, w, x0, x1, l, &its, B, s);                                                     \
+        if (Uk && l < N) Uk[(s * k_sim + kk) * N + l] = w.U()[l];                                                     \
+        if (wpred) for (int i = l; i <= N; i += P) wpred[(s * k_sim + kk) * (N + 1) + i] = w.xp()[2 * i];             \
+        double n0, n1;                                                                                                \
+        plant_step<true>(pb, scn_coef(pb, w), x0, x1, w.U()[0], n0, n1, pb.g.first_id + s, pb.g.k0 + kk);             \
+        if (l == 0) {                                                                                                 \
+            if (uk) uk[s * k_sim + kk] = w.U()[0];                                                                    \
+            if (exitflag) exitflag[s * k_sim + kk] = flag;                                                            \
+            if (inner_iters) inner_iters[s * k_sim + kk] = its;                                                       \
+            if (xk) { xk[s * 2 * (k_sim + 1) + 2 * kk + 2] = n0; xk[s * 2 * (k_sim + 1) + 2 * kk + 3] = n1; }         \
+        }                                                                                                             \
+        x0 = n0;                                                                                                      \
+        x1 = n1;                                                                                                      \
+        NTM_WSYNC();                                                                                                  \
+    }
+
 template <int P, int NN, bool GEN, bool FAR = ws_far(NN)>
 __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, NN, FAR)) void k_mpc_step(Prob pb, int64_t B, const double* __restrict__ x_k,
                                                  double* __restrict__ rho, double* __restrict__ U_old,
                                                  double* __restrict__ U, double* __restrict__ x_pred,
                                                  double* __restrict__ x_next, int32_t* __restrict__ exitflag,
                                                  int32_t* __restrict__ inner_iters, int32_t* __restrict__ active_ws) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int G = 64 / P;
-    const int g = threadIdx.x / P, l = threadIdx.x % P;
-    const int64_t s = xcd_swizzle(blockIdx.x, gridDim.x) * G + g;
+    const auto [g, l, s] = scn_lanes<P>();
     const int N = NN > 0 ? NN : pb.N;
-    NTM_STAMPS_INIT();
-    NTM_TRACE_SET(s, g, l);
     if (s >= B) return;
+    // scn_lds' and start_from_state's text, kept here: this is the kernel the benchmark
+    // times; inlined from start_from_state the production units allocate its registers
+    // differently, and scn_lds changes what the single-TU builds inline into it
+    extern __shared__ __attribute__((aligned(16))) char smem[];
     char* sbase = smem + g * ws_bytes(N, FAR);
     if constexpr (static_lds<P, NN>()) {
         __shared__ __attribute__((aligned(16))) char smem_s[ws_bytes(NN > 0 ? NN : 1, FAR)];
         sbase = smem_s;
     }
+    ws_poison<P>(sbase, ws_bytes(N, FAR), l);
     auto w = ws_carve<NN, GEN, FAR>(sbase, N, &pb, s);
-#ifdef NTM_POISON
-    // debug build (make poison): the workspace starts as NTM_POISON-valued doubles, so
-    // a read of LDS this launch never wrote shows up as a run-to-run difference
-    // (tools/determinism.py + compare_runs.py; this found the x_0-row read of rinfo[-1])
-    for (int e = l; e < ws_bytes(N, FAR) / 8; e += P) w.base[e] = NTM_POISON;
-    NTM_WSYNC();
-#endif
     const double x0 = x_k[2 * s], x1 = x_k[2 * s + 1];
     if (active_ws) {
         load_candidates<P>(pb, w, B, s, active_ws, l);
@@ -224,7 +318,6 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, NN, FAR)) void k_mpc_step
     NTM_WSYNC();
     int its;
     int flag = mpc_step_dev<P>(pb, w, x0, x1, l, &its, B, s);
-    // scenario-major outputs: each wave writes its scenario's contiguous records
     store_record<P>(rho + s * (3 * N), w.rho(), 3 * N, l);
     store_record<P>(U_old + s * N, w.Uold(), N, l);
     store_record<P>(U + s * N, w.U(), N, l);
@@ -260,20 +353,12 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_ste
     double* __restrict__ U, double* __restrict__ x_pred, double* __restrict__ x_next, int32_t* __restrict__ exitflag,
     int32_t* __restrict__ inner_iters, int32_t* __restrict__ active_ws, double* __restrict__ lambda,
     double* __restrict__ rho_qp) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int G = 64 / P;
-    const int g = threadIdx.x / P, l = threadIdx.x % P;
-    const int64_t s = xcd_swizzle(blockIdx.x, gridDim.x) * G + g;
+    const auto [g, l, s] = scn_lanes<P>();
     const int N = pb.N;
     if (s >= B) return;
-    auto w = ws_carve<0, true, false>(smem + g * ws_bytes(N, false), N, &pb, s);
+    auto w = ws_carve<0, true, false>(scn_lds<P, 0, false>(N, g, l), N, &pb, s);
     const double x0 = x_k[2 * s], x1 = x_k[2 * s + 1];
-    if (active_ws) {
-        load_candidates<P>(pb, w, B, s, active_ws, l);
-    } else if (l < 2) {
-        w.cand()[l * (N + 1) + N] = -1;
-    }
-    load_state<P>(w, B, s, rho, U_old, l);
+    start_from_state<P, false>(pb, w, B, s, rho, U_old, active_ws, l);
     scn_store(pb, w, pb.g.first_id + s, l);
     NTM_WSYNC();
     int its, q = 0;
@@ -305,107 +390,48 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_ste
     }
     if (active_ws)
         for (int e = l; e < 2 * (N + 1); e += P) active_ws[s * (2 * (N + 1)) + e] = w.cand()[e];
+    NTM_STAMPS_FLUSH();
 }
 
 template <int P, int NN, bool FAR = ws_far(NN)>
 __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, NN, FAR)) void k_mpc_run(Prob pb, int64_t B, int k_sim, const double* __restrict__ x0v,
                                                 double* xk, double* uk, double* Uk, double* wpred,
                                                 int32_t* exitflag, int32_t* inner_iters) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int G = 64 / P;
-    const int g = threadIdx.x / P, l = threadIdx.x % P;
-    const int64_t s = xcd_swizzle(blockIdx.x, gridDim.x) * G + g;
+    const auto [g, l, s] = scn_lanes<P>();
     const int N = NN > 0 ? NN : pb.N;
     if (s >= B) return;
-    char* sbase = smem + g * ws_bytes(N, FAR);
-    if constexpr (static_lds<P, NN>()) {
-        __shared__ __attribute__((aligned(16))) char smem_s[ws_bytes(NN > 0 ? NN : 1, FAR)];
-        sbase = smem_s;
-    }
-    auto w = ws_carve<NN, true, FAR>(sbase, N, &pb, s);
+    auto w = ws_carve<NN, true, FAR>(scn_lds<P, NN, FAR>(N, g, l), N, &pb, s);
     double x0 = x0v[2 * s], x1 = x0v[2 * s + 1];
     if (l < 2) w.cand()[l * (N + 1) + N] = -1;
     scn_store(pb, w, pb.g.first_id + s, l);           // this scenario's plasma (generator)
     NTM_WSYNC();
-    {   // Rho = repmat(rho(x0), 1, N) (NTM_MPC_Sim.m:63-65); Uold = +inf (D14)
-        double r1, r2, r3;
-        rho_eval(scn_coef(pb, w), x0, x1, r1, r2, r3);
-        if (l < N) {
-            w.rho()[3 * l] = r1;
-            w.rho()[3 * l + 1] = r2;
-            w.rho()[3 * l + 2] = r3;
-            w.Uold()[l] = kInf;
-        }
-        NTM_WSYNC();
-    }
-    if (xk && l == 0) { xk[s * 2 * (k_sim + 1)] = x0; xk[s * 2 * (k_sim + 1) + 1] = x1; }
-    for (int kk = 0; kk < k_sim; ++kk) {
-        int its;
-        int flag = mpc_step_dev<P>(pb, w, x0, x1, l, &its, B, s);
-        if (Uk && l < N) Uk[(s * k_sim + kk) * N + l] = w.U()[l];
-        if (wpred) for (int i = l; i <= N; i += P) wpred[(s * k_sim + kk) * (N + 1) + i] = w.xp()[2 * i];
-        double n0, n1;
-        plant_step<true>(pb, scn_coef(pb, w), x0, x1, w.U()[0], n0, n1, pb.g.first_id + s, pb.g.k0 + kk);
-        if (l == 0) {
-            if (uk) uk[s * k_sim + kk] = w.U()[0];
-            if (exitflag) exitflag[s * k_sim + kk] = flag;
-            if (inner_iters) inner_iters[s * k_sim + kk] = its;
-            if (xk) { xk[s * 2 * (k_sim + 1) + 2 * kk + 2] = n0; xk[s * 2 * (k_sim + 1) + 2 * kk + 3] = n1; }
-        }
-        x0 = n0;
-        x1 = n1;
-        NTM_WSYNC();
-    }
+    NTM_START_FROM_X0(scn_coef(pb, w), x0, x1)
+    NTM_RUN_LOOP
+    NTM_STAMPS_FLUSH();
 }
 
 // k_mpc_run from a carried state and back to it (ntm_mpc_run_from): x[2], rho[3N],
 // U_old[N] and active_ws[2(N+1)] per scenario, in/out, in ntm_mpc_step_ws's layouts.
 // A sibling kernel and not a flag of k_mpc_run, for k_mpc_step_dual's reason: more
 // kernel arguments on the template would change every existing instantiation's
-// argument block.  The inline initialisation is replaced by load_candidates /
-// load_state as in k_mpc_step; the loop body is k_mpc_run's; what the next step would
-// read from the workspace (rho, U_old, the two candidate sets) and the plant state go
-// back to HBM after the last step.  k_sim = 0 stores nothing but xk's column 0.
+// argument block.  It is k_mpc_run with k_mpc_step's start (start_from_state) and a
+// write-back: what the next step would read from the workspace (rho, U_old, the two
+// candidate sets) and the plant state go back to HBM after the last step.  k_sim = 0
+// stores nothing but xk's column 0.
 template <int P, int NN, bool FAR = ws_far(NN)>
 __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, NN, FAR)) void k_mpc_run_from(
     Prob pb, int64_t B, int k_sim, double* __restrict__ x, double* __restrict__ rho, double* __restrict__ U_old,
     int32_t* __restrict__ active_ws, double* xk, double* uk, double* Uk, double* wpred, int32_t* exitflag,
     int32_t* inner_iters) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int G = 64 / P;
-    const int g = threadIdx.x / P, l = threadIdx.x % P;
-    const int64_t s = xcd_swizzle(blockIdx.x, gridDim.x) * G + g;
+    const auto [g, l, s] = scn_lanes<P>();
     const int N = NN > 0 ? NN : pb.N;
     if (s >= B) return;
-    char* sbase = smem + g * ws_bytes(N, FAR);
-    if constexpr (static_lds<P, NN>()) {
-        __shared__ __attribute__((aligned(16))) char smem_s[ws_bytes(NN > 0 ? NN : 1, FAR)];
-        sbase = smem_s;
-    }
-    auto w = ws_carve<NN, true, FAR>(sbase, N, &pb, s);
+    auto w = ws_carve<NN, true, FAR>(scn_lds<P, NN, FAR>(N, g, l), N, &pb, s);
     double x0 = x[2 * s], x1 = x[2 * s + 1];
-    load_candidates<P, decltype(w), true>(pb, w, B, s, active_ws, l);
-    load_state<P>(w, B, s, rho, U_old, l);
+    start_from_state<P, true>(pb, w, B, s, rho, U_old, active_ws, l);
     scn_store(pb, w, pb.g.first_id + s, l);           // this scenario's plasma (generator)
     NTM_WSYNC();
-    if (xk && l == 0) { xk[s * 2 * (k_sim + 1)] = x0; xk[s * 2 * (k_sim + 1) + 1] = x1; }
-    for (int kk = 0; kk < k_sim; ++kk) {
-        int its;
-        int flag = mpc_step_dev<P>(pb, w, x0, x1, l, &its, B, s);
-        if (Uk && l < N) Uk[(s * k_sim + kk) * N + l] = w.U()[l];
-        if (wpred) for (int i = l; i <= N; i += P) wpred[(s * k_sim + kk) * (N + 1) + i] = w.xp()[2 * i];
-        double n0, n1;
-        plant_step<true>(pb, scn_coef(pb, w), x0, x1, w.U()[0], n0, n1, pb.g.first_id + s, pb.g.k0 + kk);
-        if (l == 0) {
-            if (uk) uk[s * k_sim + kk] = w.U()[0];
-            if (exitflag) exitflag[s * k_sim + kk] = flag;
-            if (inner_iters) inner_iters[s * k_sim + kk] = its;
-            if (xk) { xk[s * 2 * (k_sim + 1) + 2 * kk + 2] = n0; xk[s * 2 * (k_sim + 1) + 2 * kk + 3] = n1; }
-        }
-        x0 = n0;
-        x1 = n1;
-        NTM_WSYNC();
-    }
+    NTM_RUN_LOOP
     if (k_sim > 0) {
         store_record<P>(rho + s * (3 * N), w.rho(), 3 * N, l);
         store_record<P>(U_old + s * N, w.Uold(), N, l);
@@ -416,6 +442,7 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, NN, FAR)) void k_mpc_run_
             x[2 * s + l] = l ? x1 : x0;
         }
     }
+    NTM_STAMPS_FLUSH();
 }
 
 // Plant-model mismatch and the offset-free disturbance estimate (ntm_mpc_step_obs /
@@ -457,47 +484,72 @@ __device__ __forceinline__ WSObs ws_carve_obs(char* base, int N) {
     return w;
 }
 
+// k_mpc_run_est's loop and k_mpc_run_est_from's, as NTM_RUN_LOOP: also on the kernel's gid, kp,
+// km, eo, the carried h0, h1 (x_hat), d0, d1 (d_hat) and the histories dk, xhk, yk
+#define NTM_RUN_EST_LOOP                                                                                              \
+    const int64_t xs = s * 2 * (int64_t)(k_sim + 1);                                                                  \
+    if (xk && l == 0) { xk[xs] = x0; xk[xs + 1] = x1; }                                                               \
+    if (dk && l == 0) { dk[xs] = d0; dk[xs + 1] = d1; }                                                               \
+    if (xhk && l == 0) { xhk[xs] = h0; xhk[xs + 1] = h1; }                                                            \
+    for (int kk = 0; kk < k_sim; ++kk) {                                                                              \
+        int its;                                                                                                      \
+        int flag = mpc_step_dev<P>(pb, w, h0, h1, l, &its, B, s);                                                     \
+        if (Uk && l < N) Uk[(s * k_sim + kk) * N + l] = w.U()[l];                                                     \
+        if (wpred) for (int i = l; i <= N; i += P) wpred[(s * k_sim + kk) * (N + 1) + i] = w.xp()[2 * i];             \
+        const double u0 = w.U()[0];                                                                                   \
+        double n0, n1, m0, m1;                                                                                        \
+        plant_step<true>(pb, kp, x0, x1, u0, n0, n1, gid, pb.g.k0 + kk);                                              \
+        model_step(pb, km, h0, h1, u0, m0, m1);                                                                       \
+        const double y0 = est_measure(pb, eo.sy[0], n0, gid, pb.g.k0 + kk, 2);                                        \
+        const double y1 = est_measure(pb, eo.sy[1], n1, gid, pb.g.k0 + kk, 3);                                        \
+        est_update(eo.gain[0], eo.kappa[0], y0, m0, d0, h0);                                                          \
+        est_update(eo.gain[1], eo.kappa[1], y1, m1, d1, h1);                                                          \
+        if (l == 0) {                                                                                                 \
+            if (uk) uk[s * k_sim + kk] = u0;                                                                          \
+            if (exitflag) exitflag[s * k_sim + kk] = flag;                                                            \
+            if (inner_iters) inner_iters[s * k_sim + kk] = its;                                                       \
+            if (xk) { xk[xs + 2 * kk + 2] = n0; xk[xs + 2 * kk + 3] = n1; }                                           \
+            if (dk) { dk[xs + 2 * kk + 2] = d0; dk[xs + 2 * kk + 3] = d1; }                                           \
+            if (xhk) { xhk[xs + 2 * kk + 2] = h0; xhk[xs + 2 * kk + 3] = h1; }                                        \
+            if (yk) { yk[(s * k_sim + kk) * 2] = y0; yk[(s * k_sim + kk) * 2 + 1] = y1; }                             \
+        }                                                                                                             \
+        x0 = n0;                                                                                                      \
+        x1 = n1;                                                                                                      \
+        NTM_WSYNC();                                                                                                  \
+        obs_model(w, km, d0, d1);                                                                                     \
+    }
+
 template <int P>
 __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_step_obs(
     Prob pb, int64_t B, const double* __restrict__ x_k, double* __restrict__ rho, double* __restrict__ U_old,
     double* __restrict__ U, double* __restrict__ x_pred, double* __restrict__ x_next, int32_t* __restrict__ exitflag,
     int32_t* __restrict__ inner_iters, int32_t* __restrict__ active_ws, double* __restrict__ d_hat, int nominal,
     double gain) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int G = 64 / P;
-    const int g = threadIdx.x / P, l = threadIdx.x % P;
-    const int64_t s = xcd_swizzle(blockIdx.x, gridDim.x) * G + g;
+    const auto [g, l, s] = scn_lanes<P>();
     const int N = pb.N;
     if (s >= B) return;
-    WSObs w = ws_carve_obs(smem + g * ws_bytes(N, false), N);
+    WSObs w = ws_carve_obs(scn_lds<P, 0, false>(N, g, l), N);
     const double x0 = x_k[2 * s], x1 = x_k[2 * s + 1];
     const double d0 = d_hat[2 * s], d1 = d_hat[2 * s + 1];
     const int64_t gid = pb.g.first_id + s;
     const Coef kp = plant_coef(pb, gid);
     const Coef km = nominal ? pb.k : kp;
     obs_model(w, km, d0, d1);
-    if (active_ws) {
-        load_candidates<P>(pb, w, B, s, active_ws, l);
-    } else if (l < 2) {
-        w.cand()[l * (N + 1) + N] = -1;
-    }
-    load_state<P>(w, B, s, rho, U_old, l);
+    start_from_state<P, false>(pb, w, B, s, rho, U_old, active_ws, l);
     int its;
     int flag = mpc_step_dev<P>(pb, w, x0, x1, l, &its, B, s);
     store_record<P>(rho + s * (3 * N), w.rho(), 3 * N, l);
     store_record<P>(U_old + s * N, w.Uold(), N, l);
     store_record<P>(U + s * N, w.U(), N, l);
     store_record<P>(x_pred + s * (2 * (N + 1)), w.xp(), 2 * (N + 1), l);
-    {
-        const double u0 = w.U()[0];
-        double n0, n1, m0, m1;
-        plant_step<true>(pb, kp, x0, x1, u0, n0, n1, gid, pb.g.k0);
-        model_step(pb, km, x0, x1, u0, m0, m1);
-        const double e0 = obs_update(gain, n0 - m0, d0), e1 = obs_update(gain, n1 - m1, d1);
-        if (l < 2) {
-            x_next[2 * s + l] = l ? n1 : n0;
-            d_hat[2 * s + l] = l ? e1 : e0;
-        }
+    const double u0 = w.U()[0];
+    double n0, n1, m0, m1;
+    plant_step<true>(pb, kp, x0, x1, u0, n0, n1, gid, pb.g.k0);
+    model_step(pb, km, x0, x1, u0, m0, m1);
+    const double e0 = obs_update(gain, n0 - m0, d0), e1 = obs_update(gain, n1 - m1, d1);
+    if (l < 2) {
+        x_next[2 * s + l] = l ? n1 : n0;
+        d_hat[2 * s + l] = l ? e1 : e0;
     }
     if (l == 0) {
         exitflag[s] = flag;
@@ -505,6 +557,7 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_ste
     }
     if (active_ws)
         for (int e = l; e < 2 * (N + 1); e += P) active_ws[s * (2 * (N + 1)) + e] = w.cand()[e];
+    NTM_STAMPS_FLUSH();
 }
 
 // k_mpc_run<P, 0> with the estimate carried on chip: d0v (2 per scenario, null: zeros),
@@ -515,13 +568,10 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_run
     Prob pb, int64_t B, int k_sim, const double* __restrict__ x0v, const double* __restrict__ d0v, double* xk,
     double* uk, double* Uk, double* wpred, double* dk, int32_t* exitflag, int32_t* inner_iters, int nominal,
     double gain) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int G = 64 / P;
-    const int g = threadIdx.x / P, l = threadIdx.x % P;
-    const int64_t s = xcd_swizzle(blockIdx.x, gridDim.x) * G + g;
+    const auto [g, l, s] = scn_lanes<P>();
     const int N = pb.N;
     if (s >= B) return;
-    WSObs w = ws_carve_obs(smem + g * ws_bytes(N, false), N);
+    WSObs w = ws_carve_obs(scn_lds<P, 0, false>(N, g, l), N);
     double x0 = x0v[2 * s], x1 = x0v[2 * s + 1];
     double d0 = d0v ? d0v[2 * s] : 0.0, d1 = d0v ? d0v[2 * s + 1] : 0.0;
     const int64_t gid = pb.g.first_id + s;
@@ -529,17 +579,7 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_run
     const Coef km = nominal ? pb.k : kp;
     obs_model(w, km, d0, d1);
     if (l < 2) w.cand()[l * (N + 1) + N] = -1;
-    {   // Rho = repmat(rho(x0), 1, N) (NTM_MPC_Sim.m:63-65); Uold = +inf (D14)
-        double r1, r2, r3;
-        rho_eval(km, x0, x1, r1, r2, r3);
-        if (l < N) {
-            w.rho()[3 * l] = r1;
-            w.rho()[3 * l + 1] = r2;
-            w.rho()[3 * l + 2] = r3;
-            w.Uold()[l] = kInf;
-        }
-        NTM_WSYNC();
-    }
+    NTM_START_FROM_X0(km, x0, x1)
     const int64_t xs = s * 2 * (int64_t)(k_sim + 1);
     if (xk && l == 0) { xk[xs] = x0; xk[xs + 1] = x1; }
     if (dk && l == 0) { dk[xs] = d0; dk[xs + 1] = d1; }
@@ -566,6 +606,7 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_run
         NTM_WSYNC();
         obs_model(w, km, d0, d1);
     }
+    NTM_STAMPS_FLUSH();
 }
 
 // Output feedback (ntm_mpc_step_est / ntm_mpc_run_est): the observer kernels with a
@@ -579,20 +620,17 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_run
 //   d_hat, x_hat <- est_update(gain, kappa, y, m, ...).
 // With sy = 0, kappa = 0, gain[0] == gain[1] and x_hat == x this is k_mpc_step_obs's
 // step bit for bit (x_hat = y = x_next): the plant step and the model's map are the same
-// calls on the same values, and model_step keeps them apart for the compiler.
+// calls on the same values (feedback_step), and model_step keeps them apart for the compiler.
 template <int P>
 __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_step_est(
     Prob pb, int64_t B, const double* __restrict__ x_k, double* __restrict__ rho, double* __restrict__ U_old,
     double* __restrict__ U, double* __restrict__ x_pred, double* __restrict__ x_next, int32_t* __restrict__ exitflag,
     int32_t* __restrict__ inner_iters, int32_t* __restrict__ active_ws, double* __restrict__ d_hat,
     double* __restrict__ x_hat, double* __restrict__ y, EstOpt eo) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int G = 64 / P;
-    const int g = threadIdx.x / P, l = threadIdx.x % P;
-    const int64_t s = xcd_swizzle(blockIdx.x, gridDim.x) * G + g;
+    const auto [g, l, s] = scn_lanes<P>();
     const int N = pb.N;
     if (s >= B) return;
-    WSObs w = ws_carve_obs(smem + g * ws_bytes(N, false), N);
+    WSObs w = ws_carve_obs(scn_lds<P, 0, false>(N, g, l), N);
     const double x0 = x_k[2 * s], x1 = x_k[2 * s + 1];
     const double h0 = x_hat[2 * s], h1 = x_hat[2 * s + 1];
     double d0 = d_hat[2 * s], d1 = d_hat[2 * s + 1];
@@ -600,33 +638,26 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_ste
     const Coef kp = plant_coef(pb, gid);
     const Coef km = eo.nominal ? pb.k : kp;
     obs_model(w, km, d0, d1);
-    if (active_ws) {
-        load_candidates<P>(pb, w, B, s, active_ws, l);
-    } else if (l < 2) {
-        w.cand()[l * (N + 1) + N] = -1;
-    }
-    load_state<P>(w, B, s, rho, U_old, l);
+    start_from_state<P, false>(pb, w, B, s, rho, U_old, active_ws, l);
     int its;
     int flag = mpc_step_dev<P>(pb, w, h0, h1, l, &its, B, s);
     store_record<P>(rho + s * (3 * N), w.rho(), 3 * N, l);
     store_record<P>(U_old + s * N, w.Uold(), N, l);
     store_record<P>(U + s * N, w.U(), N, l);
     store_record<P>(x_pred + s * (2 * (N + 1)), w.xp(), 2 * (N + 1), l);
-    {
-        const double u0 = w.U()[0];
-        double n0, n1, m0, m1, e0, e1;
-        plant_step<true>(pb, kp, x0, x1, u0, n0, n1, gid, pb.g.k0);
-        model_step(pb, km, h0, h1, u0, m0, m1);
-        const double y0 = est_measure(pb, eo.sy[0], n0, gid, pb.g.k0, 2);
-        const double y1 = est_measure(pb, eo.sy[1], n1, gid, pb.g.k0, 3);
-        est_update(eo.gain[0], eo.kappa[0], y0, m0, d0, e0);
-        est_update(eo.gain[1], eo.kappa[1], y1, m1, d1, e1);
-        if (l < 2) {
-            x_next[2 * s + l] = l ? n1 : n0;
-            d_hat[2 * s + l] = l ? d1 : d0;
-            x_hat[2 * s + l] = l ? e1 : e0;
-            if (y) y[2 * s + l] = l ? y1 : y0;
-        }
+    const double u0 = w.U()[0];
+    double n0, n1, m0, m1, e0, e1;
+    plant_step<true>(pb, kp, x0, x1, u0, n0, n1, gid, pb.g.k0);
+    model_step(pb, km, h0, h1, u0, m0, m1);
+    const double y0 = est_measure(pb, eo.sy[0], n0, gid, pb.g.k0, 2);
+    const double y1 = est_measure(pb, eo.sy[1], n1, gid, pb.g.k0, 3);
+    est_update(eo.gain[0], eo.kappa[0], y0, m0, d0, e0);
+    est_update(eo.gain[1], eo.kappa[1], y1, m1, d1, e1);
+    if (l < 2) {
+        x_next[2 * s + l] = l ? n1 : n0;
+        d_hat[2 * s + l] = l ? d1 : d0;
+        x_hat[2 * s + l] = l ? e1 : e0;
+        if (y) y[2 * s + l] = l ? y1 : y0;
     }
     if (l == 0) {
         exitflag[s] = flag;
@@ -634,6 +665,7 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_ste
     }
     if (active_ws)
         for (int e = l; e < 2 * (N + 1); e += P) active_ws[s * (2 * (N + 1)) + e] = w.cand()[e];
+    NTM_STAMPS_FLUSH();
 }
 
 // k_mpc_run_obs with the measurement and the filter, x, x_hat and d_hat carried on chip:
@@ -645,13 +677,10 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_run
     Prob pb, int64_t B, int k_sim, const double* __restrict__ x0v, const double* __restrict__ d0v,
     const double* __restrict__ h0v, double* xk, double* uk, double* Uk, double* wpred, double* dk, double* xhk,
     double* yk, int32_t* exitflag, int32_t* inner_iters, EstOpt eo) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int G = 64 / P;
-    const int g = threadIdx.x / P, l = threadIdx.x % P;
-    const int64_t s = xcd_swizzle(blockIdx.x, gridDim.x) * G + g;
+    const auto [g, l, s] = scn_lanes<P>();
     const int N = pb.N;
     if (s >= B) return;
-    WSObs w = ws_carve_obs(smem + g * ws_bytes(N, false), N);
+    WSObs w = ws_carve_obs(scn_lds<P, 0, false>(N, g, l), N);
     double x0 = x0v[2 * s], x1 = x0v[2 * s + 1];
     double h0 = h0v ? h0v[2 * s] : x0, h1 = h0v ? h0v[2 * s + 1] : x1;
     double d0 = d0v ? d0v[2 * s] : 0.0, d1 = d0v ? d0v[2 * s + 1] : 0.0;
@@ -660,67 +689,25 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_run
     const Coef km = eo.nominal ? pb.k : kp;
     obs_model(w, km, d0, d1);
     if (l < 2) w.cand()[l * (N + 1) + N] = -1;
-    {   // Rho = repmat(rho(x_hat0), 1, N) (NTM_MPC_Sim.m:63-65); Uold = +inf (D14)
-        double r1, r2, r3;
-        rho_eval(km, h0, h1, r1, r2, r3);
-        if (l < N) {
-            w.rho()[3 * l] = r1;
-            w.rho()[3 * l + 1] = r2;
-            w.rho()[3 * l + 2] = r3;
-            w.Uold()[l] = kInf;
-        }
-        NTM_WSYNC();
-    }
-    const int64_t xs = s * 2 * (int64_t)(k_sim + 1);
-    if (xk && l == 0) { xk[xs] = x0; xk[xs + 1] = x1; }
-    if (dk && l == 0) { dk[xs] = d0; dk[xs + 1] = d1; }
-    if (xhk && l == 0) { xhk[xs] = h0; xhk[xs + 1] = h1; }
-    for (int kk = 0; kk < k_sim; ++kk) {
-        int its;
-        int flag = mpc_step_dev<P>(pb, w, h0, h1, l, &its, B, s);
-        if (Uk && l < N) Uk[(s * k_sim + kk) * N + l] = w.U()[l];
-        if (wpred) for (int i = l; i <= N; i += P) wpred[(s * k_sim + kk) * (N + 1) + i] = w.xp()[2 * i];
-        const double u0 = w.U()[0];
-        double n0, n1, m0, m1;
-        plant_step<true>(pb, kp, x0, x1, u0, n0, n1, gid, pb.g.k0 + kk);
-        model_step(pb, km, h0, h1, u0, m0, m1);
-        const double y0 = est_measure(pb, eo.sy[0], n0, gid, pb.g.k0 + kk, 2);
-        const double y1 = est_measure(pb, eo.sy[1], n1, gid, pb.g.k0 + kk, 3);
-        est_update(eo.gain[0], eo.kappa[0], y0, m0, d0, h0);
-        est_update(eo.gain[1], eo.kappa[1], y1, m1, d1, h1);
-        if (l == 0) {
-            if (uk) uk[s * k_sim + kk] = u0;
-            if (exitflag) exitflag[s * k_sim + kk] = flag;
-            if (inner_iters) inner_iters[s * k_sim + kk] = its;
-            if (xk) { xk[xs + 2 * kk + 2] = n0; xk[xs + 2 * kk + 3] = n1; }
-            if (dk) { dk[xs + 2 * kk + 2] = d0; dk[xs + 2 * kk + 3] = d1; }
-            if (xhk) { xhk[xs + 2 * kk + 2] = h0; xhk[xs + 2 * kk + 3] = h1; }
-            if (yk) { yk[(s * k_sim + kk) * 2] = y0; yk[(s * k_sim + kk) * 2 + 1] = y1; }
-        }
-        x0 = n0;
-        x1 = n1;
-        NTM_WSYNC();
-        obs_model(w, km, d0, d1);
-    }
+    NTM_START_FROM_X0(km, h0, h1)
+    NTM_RUN_EST_LOOP
+    NTM_STAMPS_FLUSH();
 }
 
 // k_mpc_run_est from a carried state and back to it (ntm_mpc_run_est_from), the sibling
-// k_mpc_run_from is of k_mpc_run: x, rho, U_old, active_ws, d_hat[2] and x_hat[2] per
-// scenario, in/out.  The model is built from the loaded d_hat.  With sy = 0, kappa = 0,
-// equal gains and x_hat == x it continues k_mpc_run_obs.
+// k_mpc_run_from is of k_mpc_run, with the same two differences: x, rho, U_old,
+// active_ws, d_hat[2] and x_hat[2] per scenario, in/out.  The model is built from the
+// loaded d_hat.  With sy = 0, kappa = 0, equal gains and x_hat == x it continues k_mpc_run_obs.
 template <int P>
 __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_run_est_from(
     Prob pb, int64_t B, int k_sim, double* __restrict__ x, double* __restrict__ rho, double* __restrict__ U_old,
     int32_t* __restrict__ active_ws, double* __restrict__ d_hat, double* __restrict__ x_hat, double* xk, double* uk,
     double* Uk, double* wpred, double* dk, double* xhk, double* yk, int32_t* exitflag, int32_t* inner_iters,
     EstOpt eo) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int G = 64 / P;
-    const int g = threadIdx.x / P, l = threadIdx.x % P;
-    const int64_t s = xcd_swizzle(blockIdx.x, gridDim.x) * G + g;
+    const auto [g, l, s] = scn_lanes<P>();
     const int N = pb.N;
     if (s >= B) return;
-    WSObs w = ws_carve_obs(smem + g * ws_bytes(N, false), N);
+    WSObs w = ws_carve_obs(scn_lds<P, 0, false>(N, g, l), N);
     double x0 = x[2 * s], x1 = x[2 * s + 1];
     double h0 = x_hat[2 * s], h1 = x_hat[2 * s + 1];
     double d0 = d_hat[2 * s], d1 = d_hat[2 * s + 1];
@@ -728,39 +715,8 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_run
     const Coef kp = plant_coef(pb, gid);
     const Coef km = eo.nominal ? pb.k : kp;
     obs_model(w, km, d0, d1);
-    load_candidates<P, WSObs, true>(pb, w, B, s, active_ws, l);
-    load_state<P>(w, B, s, rho, U_old, l);
-    const int64_t xs = s * 2 * (int64_t)(k_sim + 1);
-    if (xk && l == 0) { xk[xs] = x0; xk[xs + 1] = x1; }
-    if (dk && l == 0) { dk[xs] = d0; dk[xs + 1] = d1; }
-    if (xhk && l == 0) { xhk[xs] = h0; xhk[xs + 1] = h1; }
-    for (int kk = 0; kk < k_sim; ++kk) {
-        int its;
-        int flag = mpc_step_dev<P>(pb, w, h0, h1, l, &its, B, s);
-        if (Uk && l < N) Uk[(s * k_sim + kk) * N + l] = w.U()[l];
-        if (wpred) for (int i = l; i <= N; i += P) wpred[(s * k_sim + kk) * (N + 1) + i] = w.xp()[2 * i];
-        const double u0 = w.U()[0];
-        double n0, n1, m0, m1;
-        plant_step<true>(pb, kp, x0, x1, u0, n0, n1, gid, pb.g.k0 + kk);
-        model_step(pb, km, h0, h1, u0, m0, m1);
-        const double y0 = est_measure(pb, eo.sy[0], n0, gid, pb.g.k0 + kk, 2);
-        const double y1 = est_measure(pb, eo.sy[1], n1, gid, pb.g.k0 + kk, 3);
-        est_update(eo.gain[0], eo.kappa[0], y0, m0, d0, h0);
-        est_update(eo.gain[1], eo.kappa[1], y1, m1, d1, h1);
-        if (l == 0) {
-            if (uk) uk[s * k_sim + kk] = u0;
-            if (exitflag) exitflag[s * k_sim + kk] = flag;
-            if (inner_iters) inner_iters[s * k_sim + kk] = its;
-            if (xk) { xk[xs + 2 * kk + 2] = n0; xk[xs + 2 * kk + 3] = n1; }
-            if (dk) { dk[xs + 2 * kk + 2] = d0; dk[xs + 2 * kk + 3] = d1; }
-            if (xhk) { xhk[xs + 2 * kk + 2] = h0; xhk[xs + 2 * kk + 3] = h1; }
-            if (yk) { yk[(s * k_sim + kk) * 2] = y0; yk[(s * k_sim + kk) * 2 + 1] = y1; }
-        }
-        x0 = n0;
-        x1 = n1;
-        NTM_WSYNC();
-        obs_model(w, km, d0, d1);
-    }
+    start_from_state<P, true>(pb, w, B, s, rho, U_old, active_ws, l);
+    NTM_RUN_EST_LOOP
     if (k_sim > 0) {
         store_record<P>(rho + s * (3 * N), w.rho(), 3 * N, l);
         store_record<P>(U_old + s * N, w.Uold(), N, l);
@@ -771,111 +727,82 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_run
             x_hat[2 * s + l] = l ? h1 : h0;
         }
     }
+    NTM_STAMPS_FLUSH();
 }
+
 
 }  // namespace
 
-// Launchers of one horizon's one-wave-per-scenario kernels (grid of one 64-lane
-// block per scenario, lds bytes each), instantiated by the translation unit that
-// owns that horizon (ntm_n20.hip, ntm_n50.hip: each sets its own LDS batch size).
+// The launchers of the hot kernels of one (lanes, horizon, layout): k_mpc_step (the
+// generator's build only when the generator is used), k_mpc_run and k_mpc_run_from.
+// The generic horizons instantiate them in ntm_kernels.hip; a specialised horizon's are
+// instantiated by the translation unit that owns it (ntm_n20.hip, ntm_n50.hip, ...: each
+// sets its own LDS batch size) and reached through that unit's ntm_launch_<name>.
 // Internal linkage: two translation units that build the same horizon with
 // different settings (ntm_n50.hip and ntm_n50m3.hip) instantiate these templates
 // with the same arguments, and external (COMDAT) instances would be folded into
 // one of the two builds at link time
+enum class Hot { step, run, run_from };
+// the kernel arguments after (pb, B) of whichever of the three is launched
+struct HotArgs {
+    int k_sim;                                               // run, run_from
+    const double* x_in;                                      // step: x_k; run: x0
+    double *x, *rho, *U_old;                                 // step, run_from (x: run_from)
+    double *U, *x_pred, *x_next;                             // step
+    double *xk, *uk, *Uk, *wpred;                            // run, run_from
+    int32_t *exitflag, *inner_iters, *active_ws;
+};
 namespace {
-template <typename K>
-hipError_t ntm_lds_opt_in(K kern, size_t lds) {
-    if (lds <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds);
-}
 // a build without rate rows (rate_rows in ntm_ws.h) must never see mode 3: the host's
 // dispatch sends it to the runtime-N kernels, and this keeps that explicit
 template <int NN, bool FAR>
 bool ntm_mode_built(const ntm::Prob& pb) {
     return ntm::rate_rows<ntm::WS<NN, false, FAR>>() || pb.mode != NTM_MODE_FULL_DU;
 }
-template <int NN, bool FAR>
-hipError_t ntm_launch_step_v(const ntm::Prob& pb, int64_t B, const double* x_k, double* rho, double* U_old, double* U,
-                             double* x_pred, double* x_next, int32_t* exitflag, int32_t* inner_iters,
-                             int32_t* active_ws, size_t lds, hipStream_t st) {
-    if (!ntm_mode_built<NN, FAR>(pb)) return hipErrorInvalidValue;
-    const bool gen = pb.g.phys_on || pb.g.dist_on;     // the generator's build only when it is used
-    if (static_lds<64, NN>()) lds = 0;                 // the workspace is the kernel's static LDS
-    hipError_t e = gen ? ntm_lds_opt_in(k_mpc_step<64, NN, true, FAR>, lds)
-                       : ntm_lds_opt_in(k_mpc_step<64, NN, false, FAR>, lds);
-    if (e != hipSuccess) return e;
-    if (B <= 0) return hipSuccess;
-    if (gen)
-        hipLaunchKernelGGL((k_mpc_step<64, NN, true, FAR>), dim3((unsigned)B), dim3(64), lds, st, pb, B, x_k, rho,
-                           U_old, U, x_pred, x_next, exitflag, inner_iters, active_ws);
-    else
-        hipLaunchKernelGGL((k_mpc_step<64, NN, false, FAR>), dim3((unsigned)B), dim3(64), lds, st, pb, B, x_k, rho,
-                           U_old, U, x_pred, x_next, exitflag, inner_iters, active_ws);
+// the > 64 KiB opt-in, an empty batch, the launch: blocks of 64 / P scenarios
+template <int P, int NN, typename K, typename... A>
+hipError_t ntm_launch_k(K kern, int64_t B, size_t lds, hipStream_t st, A... args) {
+    constexpr int G = 64 / P;
+    if (static_lds<P, NN>()) lds = 0;                  // the workspace is the kernel's static LDS
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    const int64_t blocks = (B + G - 1) / G;
+    if (blocks <= 0) return hipSuccess;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64), lds, st, args...);
     return hipGetLastError();
 }
-template <int NN, bool FAR>
-hipError_t ntm_launch_run_v(const ntm::Prob& pb, int64_t B, int k_sim, const double* x0, double* xk, double* uk,
-                            double* Uk, double* wpred, int32_t* exitflag, int32_t* inner_iters, size_t lds,
-                            hipStream_t st) {
+template <int P, int NN, bool FAR>
+hipError_t ntm_launch_hot(Hot what, const ntm::Prob& pb, int64_t B, const HotArgs& a, size_t lds, hipStream_t st) {
     if (!ntm_mode_built<NN, FAR>(pb)) return hipErrorInvalidValue;
-    if (static_lds<64, NN>()) lds = 0;                 // the workspace is the kernel's static LDS
-    hipError_t e = ntm_lds_opt_in(k_mpc_run<64, NN, FAR>, lds);
-    if (e != hipSuccess) return e;
-    if (B <= 0) return hipSuccess;
-    hipLaunchKernelGGL((k_mpc_run<64, NN, FAR>), dim3((unsigned)B), dim3(64), lds, st, pb, B, k_sim, x0, xk, uk, Uk,
-                       wpred, exitflag, inner_iters);
-    return hipGetLastError();
-}
-template <int NN, bool FAR>
-hipError_t ntm_launch_run_from_v(const ntm::Prob& pb, int64_t B, int k_sim, double* x, double* rho, double* U_old,
-                                 int32_t* active_ws, double* xk, double* uk, double* Uk, double* wpred,
-                                 int32_t* exitflag, int32_t* inner_iters, size_t lds, hipStream_t st) {
-    if (!ntm_mode_built<NN, FAR>(pb)) return hipErrorInvalidValue;
-    if (static_lds<64, NN>()) lds = 0;                 // the workspace is the kernel's static LDS
-    hipError_t e = ntm_lds_opt_in(k_mpc_run_from<64, NN, FAR>, lds);
-    if (e != hipSuccess) return e;
-    if (B <= 0) return hipSuccess;
-    hipLaunchKernelGGL((k_mpc_run_from<64, NN, FAR>), dim3((unsigned)B), dim3(64), lds, st, pb, B, k_sim, x, rho,
-                       U_old, active_ws, xk, uk, Uk, wpred, exitflag, inner_iters);
-    return hipGetLastError();
+    switch (what) {
+    case Hot::step:
+        if (pb.g.phys_on || pb.g.dist_on)
+            return ntm_launch_k<P, NN>(k_mpc_step<P, NN, true, FAR>, B, lds, st, pb, B, a.x_in, a.rho, a.U_old, a.U,
+                                       a.x_pred, a.x_next, a.exitflag, a.inner_iters, a.active_ws);
+        return ntm_launch_k<P, NN>(k_mpc_step<P, NN, false, FAR>, B, lds, st, pb, B, a.x_in, a.rho, a.U_old, a.U,
+                                   a.x_pred, a.x_next, a.exitflag, a.inner_iters, a.active_ws);
+    case Hot::run:
+        return ntm_launch_k<P, NN>(k_mpc_run<P, NN, FAR>, B, lds, st, pb, B, a.k_sim, a.x_in, a.xk, a.uk, a.Uk,
+                                   a.wpred, a.exitflag, a.inner_iters);
+    case Hot::run_from:
+        return ntm_launch_k<P, NN>(k_mpc_run_from<P, NN, FAR>, B, lds, st, pb, B, a.k_sim, a.x, a.rho, a.U_old,
+                                   a.active_ws, a.xk, a.uk, a.Uk, a.wpred, a.exitflag, a.inner_iters);
+    }
+    return hipErrorInvalidValue;
 }
 }  // namespace
 // One translation unit per (horizon, layout): ntm_n20.hip (far), ntm_n20near.hip (the
-// all-LDS N = 20 build for small batches, its own batch settings), ntm_n50.hip (far,
-// modes 0-2) and ntm_n50m3.hip (far, input-rate rows: mode 3)
-#define NTM_DECLARE_LAYOUT_LAUNCHERS(NAME)                                                                         \
-    hipError_t ntm_launch_step_##NAME(const ntm::Prob& pb, int64_t B, const double* x_k, double* rho,             \
-                                      double* U_old, double* U, double* x_pred, double* x_next, int32_t* exitflag, \
-                                      int32_t* inner_iters, int32_t* active_ws, size_t lds, hipStream_t st);       \
-    hipError_t ntm_launch_run_##NAME(const ntm::Prob& pb, int64_t B, int k_sim, const double* x0, double* xk,     \
-                                     double* uk, double* Uk, double* wpred, int32_t* exitflag,                     \
-                                     int32_t* inner_iters, size_t lds, hipStream_t st);                            \
-    hipError_t ntm_launch_run_from_##NAME(const ntm::Prob& pb, int64_t B, int k_sim, double* x, double* rho,      \
-                                          double* U_old, int32_t* active_ws, double* xk, double* uk, double* Uk,   \
-                                          double* wpred, int32_t* exitflag, int32_t* inner_iters, size_t lds,      \
-                                          hipStream_t st);
-#define NTM_DEFINE_LAYOUT_LAUNCHERS(NAME, NNV, FARV)                                                               \
-    hipError_t ntm_launch_step_##NAME(const ntm::Prob& pb, int64_t B, const double* x_k, double* rho,             \
-                                      double* U_old, double* U, double* x_pred, double* x_next, int32_t* exitflag, \
-                                      int32_t* inner_iters, int32_t* active_ws, size_t lds, hipStream_t st) {      \
-        return ntm_launch_step_v<NNV, FARV>(pb, B, x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters,     \
-                                            active_ws, lds, st);                                                   \
-    }                                                                                                              \
-    hipError_t ntm_launch_run_##NAME(const ntm::Prob& pb, int64_t B, int k_sim, const double* x0, double* xk,     \
-                                     double* uk, double* Uk, double* wpred, int32_t* exitflag,                     \
-                                     int32_t* inner_iters, size_t lds, hipStream_t st) {                           \
-        return ntm_launch_run_v<NNV, FARV>(pb, B, k_sim, x0, xk, uk, Uk, wpred, exitflag, inner_iters, lds, st);  \
-    }                                                                                                              \
-    hipError_t ntm_launch_run_from_##NAME(const ntm::Prob& pb, int64_t B, int k_sim, double* x, double* rho,      \
-                                          double* U_old, int32_t* active_ws, double* xk, double* uk, double* Uk,   \
-                                          double* wpred, int32_t* exitflag, int32_t* inner_iters, size_t lds,      \
-                                          hipStream_t st) {                                                        \
-        return ntm_launch_run_from_v<NNV, FARV>(pb, B, k_sim, x, rho, U_old, active_ws, xk, uk, Uk, wpred,        \
-                                                exitflag, inner_iters, lds, st);                                   \
+// all-LDS N = 20 build for small batches, its own batch settings), ntm_n20near1w.hip (the
+// same with a one-wave register budget), ntm_n50.hip (far, modes 0-2) and ntm_n50m3.hip
+// (far, input-rate rows: mode 3).  One wave per scenario: lds bytes per block
+typedef hipError_t ntm_layout_launcher(Hot what, const ntm::Prob& pb, int64_t B, const HotArgs& a, size_t lds,
+                                       hipStream_t st);
+#define NTM_DEFINE_LAYOUT_LAUNCHER(NAME, NNV, FARV)                                                         \
+    hipError_t ntm_launch_##NAME(Hot what, const ntm::Prob& pb, int64_t B, const HotArgs& a, size_t lds,    \
+                                 hipStream_t st) {                                                          \
+        return ntm_launch_hot<64, NNV, FARV>(what, pb, B, a, lds, st);                                      \
     }
-NTM_DECLARE_LAYOUT_LAUNCHERS(n20)
-NTM_DECLARE_LAYOUT_LAUNCHERS(n20near)
-NTM_DECLARE_LAYOUT_LAUNCHERS(n20near1w)
-NTM_DECLARE_LAYOUT_LAUNCHERS(n50)
-NTM_DECLARE_LAYOUT_LAUNCHERS(n50m3)
+ntm_layout_launcher ntm_launch_n20, ntm_launch_n20near, ntm_launch_n20near1w, ntm_launch_n50, ntm_launch_n50m3;
