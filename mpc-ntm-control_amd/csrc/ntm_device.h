@@ -235,7 +235,7 @@ struct StructRows {
         };
         if (l < N) {
             double lo, hi;
-            if constexpr (W::kSlim) {                         // (diag_scale_phase's expressions)
+            if constexpr (W::kSlim && !W::kBox) {             // (diag_scale_phase's expressions)
                 const double Dl = w.D()[l];
                 lo = -((-umin) / Dl);
                 hi = umax / Dl;

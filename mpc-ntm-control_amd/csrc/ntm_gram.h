@@ -419,8 +419,10 @@ __device__ __forceinline__ int diag_scale_phase(const Prob& pb, const W& w, int 
         double f = (2 * fs) * Dl;
         bad |= !isfinite(f) || !isfinite(Dl);
         w.F()[l] = f;
-        // V-space box of u_l (bc of the two u rows; same expressions as the oracle's b/rn)
-        if constexpr (!W::kSlim) {
+        // V-space box of u_l (bc of the two u rows; same expressions as the oracle's b/rn).
+        // kBox: into a11 / a21, which the lift has finished with (WS::kBox); once per QP, where
+        // StructRows::check divided twice per call
+        if constexpr (!W::kSlim || W::kBox) {
             w.vlo()[l] = -((-pb.umin) / Dl);
             w.vhi()[l] = pb.umax / Dl;
         }

@@ -132,10 +132,17 @@ __device__ __forceinline__ void ld5(const double* v, double (&x)[5]) {
 // +0.0, never a product with 0): a column's masked terms come first, onto the
 // +0.0 the sum starts from, so no accumulator is -0.0 where a term is masked
 // and the two forms are identical, whatever the data.
-//   One block per chunk of five terms, the masks s_lshl_b64 / s_lshr_b64 of -1 by
-// compile-time shifts (rule 1).  The blocks hold no memory instruction (rule 5);
-// the scaling pass's v_cmp_class writes an SGPR pair that only an s_or_b64 reads
-// (rule 4).
+//   One block per chunk of five terms.  A term's mask costs one scalar instruction
+// (round 16; it was s_lshl_b64 / s_lshr_b64 of -1 into an SGPR pair, then the AND):
+// the saved EXEC ANDed with a 32-bit literal (lanes <= i, i <= 19) or and-not one (the
+// lanes below 2j, 2j <= 32), straight into EXEC (rule 1); the row passes' terms 17..19
+// keep the shift and the pair, their term 0 writes no EXEC at all.  The wait states
+// are what they were: a SALU write of EXEC needs none before the VALU behind it
+// (rule 2), whether it is an s_and_b64 of two SGPR pairs or of a pair and a literal,
+// and nothing else of a block changed: the same VALU instructions in the same order,
+// the restoring s_mov_b64 and the s_nop 0 at the end (rule 3).  The blocks hold no
+// memory instruction (rule 5); the scaling pass's v_cmp_class writes an SGPR pair
+// that only an s_or_b64 reads (rule 4).
 //   Measured on the far N = 20 kernel at B = 1e5 (A/B on one box, three runs
 // each): the row dots 6.057 -> 5.962 ms per step-batch, the certificate's
 // gradient and the scaling pass's column pass on top 5.949 -> 5.772 ms; the
@@ -151,49 +158,109 @@ __device__ __forceinline__ constexpr bool lane_masked_ok() {
     // scaling pass split over idle lanes
     return P == 64 && CH == 5 && W::kNN == 20 && W::kFar;
 }
-// EXEC = entry EXEC & (lanes >= s<k>) / (lanes <= 63 - s<k>), s<k> a compile-time shift
-#define NTM_LANES_FROM(k) "s_lshl_b64 %[m], -1, %[s" #k "]\n\ts_and_b64 exec, %[sv], %[m]\n\t"
-#define NTM_LANES_UPTO(k) "s_lshr_b64 %[m], -1, %[s" #k "]\n\ts_and_b64 exec, %[sv], %[m]\n\t"
-#define NTM_SHIFTS_FROM(J0) \
-    [s0] "n"(2 * (J0)), [s1] "n"(2 * (J0) + 2), [s2] "n"(2 * (J0) + 4), [s3] "n"(2 * (J0) + 6), [s4] "n"(2 * (J0) + 8)
-#define NTM_SHIFTS_UPTO(I0) \
-    [s0] "n"(63 - (I0)), [s1] "n"(62 - (I0)), [s2] "n"(61 - (I0)), [s3] "n"(60 - (I0)), [s4] "n"(59 - (I0))
+// The masks.  Lanes >= 2j of a row pass: the entry EXEC and-not the lanes below 2j, one
+// s_andn2_b64 with a 32-bit literal for 2j <= 32 (a literal of a 64-bit scalar operand is
+// zero-extended, so its complement keeps the lanes 32..63); the terms j = 17..19 shift -1 and
+// AND, two instructions; term j = 0 belongs to every lane and leaves EXEC as it is (it is
+// the first term of its block: EXEC is still the entry EXEC).  Lanes <= i of a column pass,
+// i <= 19: one s_and_b64 with the literal (2 << i) - 1.
+constexpr unsigned long long lanes_below(int s) { return (1ull << s) - 1ull; }        // lanes 0..s-1
+// the literal of a term equals the shift form's mask (s_lshl_b64 / s_lshr_b64 of -1), and fits 32 bits
+constexpr bool from_lit_ok(int j) {
+    return ~lanes_below(2 * j) == (~0ull << (2 * j)) && lanes_below(2 * j) <= 0xFFFFFFFFull;
+}
+constexpr bool upto_lit_ok(int i) {
+    return lanes_below(i + 1) == (~0ull >> (63 - i)) && lanes_below(i + 1) <= 0xFFFFFFFFull;
+}
+template <int J0>
+constexpr bool from_chunk_ok() {                          // terms J0..J0+4: 2j <= 32 by literal, shifts above
+    static_assert(J0 == 0 || J0 == 5 || J0 == 10 || J0 == 15, "chunks of five terms of the N = 20 passes");
+    for (int k = 0; k < 5; ++k)
+        if (2 * (J0 + k) <= 32 && !from_lit_ok(J0 + k)) return false;
+    return true;
+}
+template <int I0>
+constexpr bool upto_chunk_ok() {
+    static_assert(I0 >= 0 && I0 + 5 <= 20, "columns 0..19");
+    for (int k = 0; k < 5; ++k)
+        if (!upto_lit_ok(I0 + k)) return false;
+    return true;
+}
+#define NTM_FROM_ALL(k)                                                                   // every lane: no EXEC write
+#define NTM_FROM_LIT(k) "s_andn2_b64 exec, %[sv], %[s" #k "]\n\t"                         // s<k>: the lanes below 2j
+#define NTM_FROM_SHL(k) "s_lshl_b64 %[m], -1, %[s" #k "]\n\ts_and_b64 exec, %[sv], %[m]\n\t"   // s<k>: the shift 2j
+#define NTM_UPTO_LIT(k) "s_and_b64 exec, %[sv], %[s" #k "]\n\t"                           // s<k>: the lanes <= i
+// a chunk's five "n" operands: literals (unsigned long long, so bit 31 prints unsigned); the last
+// chunk of a row pass holds the two literals of j = 15, 16 and the three shifts of j = 17..19
+#define NTM_LITS_FROM(J0)                                                                                  \
+    [s0] "n"(lanes_below(2 * (J0))), [s1] "n"(lanes_below(2 * (J0) + 2)), [s2] "n"(lanes_below(2 * (J0) + 4)), \
+        [s3] "n"(lanes_below(2 * (J0) + 6)), [s4] "n"(lanes_below(2 * (J0) + 8))
+#define NTM_LITS_FROM_LAST \
+    [s0] "n"(lanes_below(30)), [s1] "n"(lanes_below(32)), [s2] "n"(34), [s3] "n"(36), [s4] "n"(38)
+#define NTM_LITS_UPTO(I0)                                                                                  \
+    [s0] "n"(lanes_below((I0) + 1)), [s1] "n"(lanes_below((I0) + 2)), [s2] "n"(lanes_below((I0) + 3)),     \
+        [s3] "n"(lanes_below((I0) + 4)), [s4] "n"(lanes_below((I0) + 5))
 #define NTM_V5(n, a) [n##0] "v"(a[0]), [n##1] "v"(a[1]), [n##2] "v"(a[2]), [n##3] "v"(a[3]), [n##4] "v"(a[4])
+#define NTM_M_NONE
+#define NTM_M_PAIR , [m] "=&s"(m)
 // y += g[u] x[u] on lanes >= 2 (J0 + u), u = 0..4 in order, one v_fmac_f64 each
 template <int J0>
 __device__ __forceinline__ void fmac5_lanes_from(double& y, const double (&g)[5], const double (&x)[5]) {
-    unsigned long long sv, m;
-#define NTM_TERM(k) NTM_LANES_FROM(k) "v_fmac_f64_e32 %[y], %[g" #k "], %[x" #k "]\n\t"
-    asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_TERM(0) NTM_TERM(1) NTM_TERM(2) NTM_TERM(3) NTM_TERM(4)
-                 "s_mov_b64 exec, %[sv]\n\ts_nop 0"
-                 : [y] "+v"(y), [sv] "=&s"(sv), [m] "=&s"(m)
-                 : NTM_V5(g, g), NTM_V5(x, x), NTM_SHIFTS_FROM(J0)
-                 : "scc");
+    static_assert(from_chunk_ok<J0>(), "a term's literal is not its shift form's mask");
+    unsigned long long sv;
+#define NTM_TERM(M, k) M(k) "v_fmac_f64_e32 %[y], %[g" #k "], %[x" #k "]\n\t"
+#define NTM_BLOCK(M0, M1, M2, M3, M4, MOUT, LITS)                                                                    \
+    asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_TERM(M0, 0) NTM_TERM(M1, 1) NTM_TERM(M2, 2) NTM_TERM(M3, 3)          \
+                 NTM_TERM(M4, 4) "s_mov_b64 exec, %[sv]\n\ts_nop 0"                                                  \
+                 : [y] "+v"(y), [sv] "=&s"(sv) MOUT                                                                  \
+                 : NTM_V5(g, g), NTM_V5(x, x), LITS                                                                  \
+                 : "scc")
+    if constexpr (J0 == 0) {
+        NTM_BLOCK(NTM_FROM_ALL, NTM_FROM_LIT, NTM_FROM_LIT, NTM_FROM_LIT, NTM_FROM_LIT, NTM_M_NONE, NTM_LITS_FROM(J0));
+    } else if constexpr (J0 == 15) {
+        unsigned long long m;
+        NTM_BLOCK(NTM_FROM_LIT, NTM_FROM_LIT, NTM_FROM_SHL, NTM_FROM_SHL, NTM_FROM_SHL, NTM_M_PAIR, NTM_LITS_FROM_LAST);
+    } else {
+        NTM_BLOCK(NTM_FROM_LIT, NTM_FROM_LIT, NTM_FROM_LIT, NTM_FROM_LIT, NTM_FROM_LIT, NTM_M_NONE, NTM_LITS_FROM(J0));
+    }
+#undef NTM_BLOCK
 #undef NTM_TERM
 }
 // the same for two accumulators that share g and the masks: y1 += g x1, then y2 += g x2, per term
 template <int J0>
 __device__ __forceinline__ void fmac5x2_lanes_from(double& y1, double& y2, const double (&g)[5],
                                                    const double (&x1)[5], const double (&x2)[5]) {
-    unsigned long long sv, m;
-#define NTM_TERM(k) \
-    NTM_LANES_FROM(k) "v_fmac_f64_e32 %[y1], %[g" #k "], %[a" #k "]\n\tv_fmac_f64_e32 %[y2], %[g" #k "], %[b" #k "]\n\t"
-    asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_TERM(0) NTM_TERM(1) NTM_TERM(2) NTM_TERM(3) NTM_TERM(4)
-                 "s_mov_b64 exec, %[sv]\n\ts_nop 0"
-                 : [y1] "+v"(y1), [y2] "+v"(y2), [sv] "=&s"(sv), [m] "=&s"(m)
-                 : NTM_V5(g, g), NTM_V5(a, x1), NTM_V5(b, x2), NTM_SHIFTS_FROM(J0)
-                 : "scc");
+    static_assert(from_chunk_ok<J0>(), "a term's literal is not its shift form's mask");
+    unsigned long long sv;
+#define NTM_TERM(M, k) \
+    M(k) "v_fmac_f64_e32 %[y1], %[g" #k "], %[a" #k "]\n\tv_fmac_f64_e32 %[y2], %[g" #k "], %[b" #k "]\n\t"
+#define NTM_BLOCK(M0, M1, M2, M3, M4, MOUT, LITS)                                                                    \
+    asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_TERM(M0, 0) NTM_TERM(M1, 1) NTM_TERM(M2, 2) NTM_TERM(M3, 3)          \
+                 NTM_TERM(M4, 4) "s_mov_b64 exec, %[sv]\n\ts_nop 0"                                                  \
+                 : [y1] "+v"(y1), [y2] "+v"(y2), [sv] "=&s"(sv) MOUT                                                 \
+                 : NTM_V5(g, g), NTM_V5(a, x1), NTM_V5(b, x2), LITS                                                  \
+                 : "scc")
+    if constexpr (J0 == 0) {
+        NTM_BLOCK(NTM_FROM_ALL, NTM_FROM_LIT, NTM_FROM_LIT, NTM_FROM_LIT, NTM_FROM_LIT, NTM_M_NONE, NTM_LITS_FROM(J0));
+    } else if constexpr (J0 == 15) {
+        unsigned long long m;
+        NTM_BLOCK(NTM_FROM_LIT, NTM_FROM_LIT, NTM_FROM_SHL, NTM_FROM_SHL, NTM_FROM_SHL, NTM_M_PAIR, NTM_LITS_FROM_LAST);
+    } else {
+        NTM_BLOCK(NTM_FROM_LIT, NTM_FROM_LIT, NTM_FROM_LIT, NTM_FROM_LIT, NTM_FROM_LIT, NTM_M_NONE, NTM_LITS_FROM(J0));
+    }
+#undef NTM_BLOCK
 #undef NTM_TERM
 }
 // s += t[u] on lanes <= I0 + u (column pass), one v_add_f64 each
 template <int I0>
 __device__ __forceinline__ void fadd5_lanes_upto(double& s, const double (&t)[5]) {
-    unsigned long long sv, m;
-#define NTM_TERM(k) NTM_LANES_UPTO(k) "v_add_f64 %[y], %[y], %[t" #k "]\n\t"
+    static_assert(upto_chunk_ok<I0>(), "a term's literal is not its shift form's mask");
+    unsigned long long sv;
+#define NTM_TERM(k) NTM_UPTO_LIT(k) "v_add_f64 %[y], %[y], %[t" #k "]\n\t"
     asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_TERM(0) NTM_TERM(1) NTM_TERM(2) NTM_TERM(3) NTM_TERM(4)
                  "s_mov_b64 exec, %[sv]\n\ts_nop 0"
-                 : [y] "+v"(s), [sv] "=&s"(sv), [m] "=&s"(m)
-                 : NTM_V5(t, t), NTM_SHIFTS_UPTO(I0)
+                 : [y] "+v"(s), [sv] "=&s"(sv)
+                 : NTM_V5(t, t), NTM_LITS_UPTO(I0)
                  : "scc");
 #undef NTM_TERM
 }
@@ -204,23 +271,29 @@ template <int I0>
 __device__ __forceinline__ void fadd5x2_class_lanes_upto(double& s, double& fs, unsigned long long& nf,
                                                          const double (&t)[5], const double (&tf)[5],
                                                          const double (&g0)[5], const double (&g1)[5]) {
-    unsigned long long sv, m, c;
+    static_assert(upto_chunk_ok<I0>(), "a term's literal is not its shift form's mask");
+    unsigned long long sv, c;
     const int cls = 0x207;                                // signalling / quiet NaN, -inf, +inf
-#define NTM_TERM(k)                                                                                       \
-    NTM_LANES_UPTO(k) "v_cmp_class_f64_e64 %[c], %[p" #k "], %[cls]\n\ts_or_b64 %[nf], %[nf], %[c]\n\t" \
-                      "v_cmp_class_f64_e64 %[c], %[q" #k "], %[cls]\n\ts_or_b64 %[nf], %[nf], %[c]\n\t" \
-                      "v_add_f64 %[y], %[y], %[t" #k "]\n\tv_add_f64 %[z], %[z], %[u" #k "]\n\t"
+#define NTM_TERM(k)                                                                                      \
+    NTM_UPTO_LIT(k) "v_cmp_class_f64_e64 %[c], %[p" #k "], %[cls]\n\ts_or_b64 %[nf], %[nf], %[c]\n\t"  \
+                    "v_cmp_class_f64_e64 %[c], %[q" #k "], %[cls]\n\ts_or_b64 %[nf], %[nf], %[c]\n\t"  \
+                    "v_add_f64 %[y], %[y], %[t" #k "]\n\tv_add_f64 %[z], %[z], %[u" #k "]\n\t"
     asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_TERM(0) NTM_TERM(1) NTM_TERM(2) NTM_TERM(3) NTM_TERM(4)
                  "s_mov_b64 exec, %[sv]\n\ts_nop 0"
-                 : [y] "+v"(s), [z] "+v"(fs), [nf] "+s"(nf), [sv] "=&s"(sv), [m] "=&s"(m), [c] "=&s"(c)
-                 : NTM_V5(t, t), NTM_V5(u, tf), NTM_V5(p, g0), NTM_V5(q, g1), [cls] "s"(cls), NTM_SHIFTS_UPTO(I0)
+                 : [y] "+v"(s), [z] "+v"(fs), [nf] "+s"(nf), [sv] "=&s"(sv), [c] "=&s"(c)
+                 : NTM_V5(t, t), NTM_V5(u, tf), NTM_V5(p, g0), NTM_V5(q, g1), [cls] "s"(cls), NTM_LITS_UPTO(I0)
                  : "scc");
 #undef NTM_TERM
 }
-#undef NTM_LANES_FROM
-#undef NTM_LANES_UPTO
-#undef NTM_SHIFTS_FROM
-#undef NTM_SHIFTS_UPTO
+#undef NTM_FROM_ALL
+#undef NTM_FROM_LIT
+#undef NTM_FROM_SHL
+#undef NTM_UPTO_LIT
+#undef NTM_LITS_FROM
+#undef NTM_LITS_FROM_LAST
+#undef NTM_LITS_UPTO
+#undef NTM_M_NONE
+#undef NTM_M_PAIR
 #undef NTM_V5
 
 // ---------------------------------------------------------------------------
@@ -556,8 +629,12 @@ __device__ __forceinline__ void bsub_lanes(int n, double& acc, double& mu, doubl
 //   One block per chunk.  Its ten loads are issued first, under the chunk's widest
 // mask (lanes >= 2 J0 below 2N: gt(r, j) of such a lane lies inside the packed
 // Gamma for any j), and term k waits for its own pair (LDS loads return in order:
-// lgkmcnt(8 - 2k)); loads and waits are one statement (rule 5).  The masks are
-// s_bfm_b64 (40 - 2j ones from bit 2j) ANDed with the saved EXEC.  VCC written by
+// lgkmcnt(8 - 2k)); loads and waits are one statement (rule 5).  A chunk's first
+// mask is s_bfm_b64 (40 - 2j ones from bit 2j) ANDed with the saved EXEC.  The masks
+// of a chunk are nested (term j + 1's lanes are term j's without the lanes 2j and
+// 2j + 1), so a later term narrows the EXEC it finds by one s_andn2_b64 with the
+// literal of the lanes below its 2j (2j <= 32: a 32-bit literal, zero-extended; round
+// 16); the terms 17..19 build theirs by s_bfm_b64 as before.  VCC written by
 // v_cmp is read as a mask by v_cndmask and as a carry by v_addc: two wait states
 // (rule 4), which the two v_mul_f64 between them are, in the order the compiler
 // itself schedules this pair (v_cmp, two VALU, v_cndmask).  v_addc's carry-out
@@ -572,33 +649,43 @@ __device__ __forceinline__ void bsub_lanes(int n, double& acc, double& mu, doubl
 #define NTM_RN_LD(k) \
     "ds_read_b64 %[g" #k "], %[at] offset:%[o" #k "]\n\tds_read_b64 %[d" #k "], %[ad] offset:%[q" #k "]\n\t"
 #define NTM_RN_MASK(k) "s_bfm_b64 %[m], %[w" #k "], %[b" #k "]\n\ts_and_b64 exec, %[sv], %[m]\n\t"
+#define NTM_RN_NARROW(k) "s_andn2_b64 exec, exec, %[n" #k "]\n\t"    // n<k>: the lanes below 2j, a 32-bit literal
 #define NTM_RN_TERM(k, cntk)                                                                          \
     "s_waitcnt lgkmcnt(" #cntk ")\n\tv_cmp_neq_f64_e32 vcc, 0, %[g" #k "]\n\tv_mul_f64 %[v], %[g" #k "], %[d" #k "]\n\t"                \
     "v_mul_f64 %[v], %[v], %[v]\n\tv_cndmask_b32_e64 %[last], %[last], %[j" #k "], vcc\n\t"          \
     "v_addc_co_u32_e32 %[cnt], vcc, 0, %[cnt], vcc\n\tv_add_f64 %[s], %[s], %[v]\n\t"
 #define NTM_RN_N(k, J0)                                                                               \
     [w##k] "n"(40 - 2 * ((J0) + k)), [b##k] "n"(2 * ((J0) + k)), [j##k] "n"((J0) + k),                \
+        [n##k] "n"(lanes_below(2 * ((J0) + k) <= 32 ? 2 * ((J0) + k) : 0)),                           \
         [o##k] "n"(8 * ((J0) + k) * (39 - ((J0) + k))), [q##k] "n"(8 * ((J0) + k))
 // terms J0 .. J0 + 4 of row `lane`: at / ad the LDS byte addresses of Gt[lane] and of D[0]
 template <int J0>
 __device__ __forceinline__ void rownorm5_lanes_from(double& s, int& last, int& cnt, unsigned at, unsigned ad) {
-    static_assert(J0 >= 0 && J0 + 5 <= 20, "terms 0..19 of the N = 20 row pass");
+    static_assert(from_chunk_ok<J0>(), "a term's literal is not the mask of the lanes below 2j");
     unsigned long long sv, m;
     double g0, g1, g2, g3, g4, d0, d1, d2, d3, d4, v;
-    asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_RN_MASK(0)
-                 NTM_RN_LD(0) NTM_RN_LD(1) NTM_RN_LD(2) NTM_RN_LD(3) NTM_RN_LD(4) NTM_RN_TERM(0, 8)
-                 NTM_RN_MASK(1) NTM_RN_TERM(1, 6) NTM_RN_MASK(2) NTM_RN_TERM(2, 4)
-                 NTM_RN_MASK(3) NTM_RN_TERM(3, 2) NTM_RN_MASK(4) NTM_RN_TERM(4, 0)
-                 "s_mov_b64 exec, %[sv]\n\ts_nop 0"
-                 : [s] "+v"(s), [last] "+v"(last), [cnt] "+v"(cnt), [v] "=&v"(v), [sv] "=&s"(sv), [m] "=&s"(m),
-                   [g0] "=&v"(g0), [g1] "=&v"(g1), [g2] "=&v"(g2), [g3] "=&v"(g3), [g4] "=&v"(g4),
-                   [d0] "=&v"(d0), [d1] "=&v"(d1), [d2] "=&v"(d2), [d3] "=&v"(d3), [d4] "=&v"(d4)
-                 : [at] "v"(at), [ad] "v"(ad), NTM_RN_N(0, J0), NTM_RN_N(1, J0), NTM_RN_N(2, J0), NTM_RN_N(3, J0),
-                   NTM_RN_N(4, J0)
-                 : "scc", "vcc", "memory");
+    // M1..M4: how terms 1..4 come by their lanes: NTM_RN_NARROW from the term before, or NTM_RN_MASK
+#define NTM_RN_BLOCK(M1, M2, M3, M4)                                                                                \
+    asm volatile("s_mov_b64 %[sv], exec\n\t" NTM_RN_MASK(0)                                                         \
+                 NTM_RN_LD(0) NTM_RN_LD(1) NTM_RN_LD(2) NTM_RN_LD(3) NTM_RN_LD(4) NTM_RN_TERM(0, 8)                  \
+                 M1(1) NTM_RN_TERM(1, 6) M2(2) NTM_RN_TERM(2, 4) M3(3) NTM_RN_TERM(3, 2) M4(4) NTM_RN_TERM(4, 0)     \
+                 "s_mov_b64 exec, %[sv]\n\ts_nop 0"                                                                 \
+                 : [s] "+v"(s), [last] "+v"(last), [cnt] "+v"(cnt), [v] "=&v"(v), [sv] "=&s"(sv), [m] "=&s"(m),     \
+                   [g0] "=&v"(g0), [g1] "=&v"(g1), [g2] "=&v"(g2), [g3] "=&v"(g3), [g4] "=&v"(g4),                  \
+                   [d0] "=&v"(d0), [d1] "=&v"(d1), [d2] "=&v"(d2), [d3] "=&v"(d3), [d4] "=&v"(d4)                   \
+                 : [at] "v"(at), [ad] "v"(ad), NTM_RN_N(0, J0), NTM_RN_N(1, J0), NTM_RN_N(2, J0), NTM_RN_N(3, J0),  \
+                   NTM_RN_N(4, J0)                                                                                  \
+                 : "scc", "vcc", "memory")
+    if constexpr (J0 == 15) {                             // j = 16 by literal, j = 17..19 (bits 34..39) by s_bfm_b64
+        NTM_RN_BLOCK(NTM_RN_NARROW, NTM_RN_MASK, NTM_RN_MASK, NTM_RN_MASK);
+    } else {
+        NTM_RN_BLOCK(NTM_RN_NARROW, NTM_RN_NARROW, NTM_RN_NARROW, NTM_RN_NARROW);
+    }
+#undef NTM_RN_BLOCK
 }
 #undef NTM_RN_LD
 #undef NTM_RN_MASK
+#undef NTM_RN_NARROW
 #undef NTM_RN_TERM
 #undef NTM_RN_N
 

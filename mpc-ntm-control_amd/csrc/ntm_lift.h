@@ -138,6 +138,8 @@ __device__ __forceinline__ void lift_phase(const Prob& pb, const W& w, int l, do
             ra = coef_a11(k, w.rho()[3 * l]);
             rc = coef_a21(k, w.rho()[3 * l + 1]);
             rbb = coef_b(k, w.rho()[3 * l + 2]);
+            // (WS::kBox: these 2N doubles held the last QP's vlo / vhi until here; they are the
+            // lift's to the end of its recursion below, then the scaling pass's again)
             if constexpr (W::kAB) { w.a11()[l] = ra; w.a21()[l] = rc; }
         }
         if constexpr (W::kAB) NTM_WSYNC();

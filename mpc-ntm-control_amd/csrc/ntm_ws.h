@@ -52,6 +52,10 @@ __device__ __forceinline__ double coef_b(const Coef& k, double r3) { return k.bc
 #define NTM_FAR_N20 1
 #endif
 __host__ __device__ constexpr bool ws_far(int NN) { return NN > 32 || (NTM_FAR_N20 && NN == 20); }
+// the slim far N = 20 kernels keep the V-space box in LDS, in the lift's a11 / a21 (WS::kBox)
+#ifndef NTM_N20_BOX_LDS
+#define NTM_N20_BOX_LDS 1
+#endif
 // The slim far layout (N = 20 far, round 5): 16 scenarios per CU (4 waves per SIMD,
 // <= 10,240 B of LDS each) instead of 12.  What leaves LDS: the A/B coefficient
 // arrays (each lane keeps its stage's in registers, broadcast by readlane in the
@@ -119,6 +123,16 @@ struct WS {
     // front of rinfo; nothing is padded and nothing else moves.
     static constexpr bool kPair = kSlim && NN == 20;
     static constexpr int kUu = kPair ? 1 : 0;               // uu's n() + 1 doubles lead the block
+    // kBox (the slim far N = 20 layout, round 16): the V-space box vlo / vhi is back in LDS, in
+    // the 2N doubles of a11 / a21, at no cost in bytes.  Who owns those 2N doubles, and when:
+    // the lift, from its coefficient pass (lift_phase writes a11 / a21 first thing) to the end
+    // of its recursion, the only reader (the slim rollout recomputes its coefficients from
+    // rho); the box from the scaling pass (diag_scale_phase writes vlo / vhi where D_l is
+    // final) through the candidates, the dual path and GI, until the next QP's lift.  Nothing
+    // carries them over a step boundary or a state hand-over: every QP writes both before it
+    // reads either.  NTM_N20_BOX_LDS=0 builds the parent's form (bounds divided out of D on
+    // every call of StructRows::check), for the A/B.
+    static constexpr bool kBox = kPair && NTM_N20_BOX_LDS != 0;
     static constexpr int oPhin(int n) { return (kSlim ? kRL + kAB : 6) * n; }
     static constexpr int oEn(int n) { return (kSlim ? kRL + 2 + kAB : 12) * n; }
     static constexpr int oGtn(int n) { return (kSlim ? kRL + 4 + kAB : 14) * n; }
@@ -132,7 +146,8 @@ struct WS {
         if constexpr (kSF) return far + n() * ldj() + (n() + 1) * ldj() + 3 * n();
         else return base;
     }
-    // (kSlim: no a11 / a21 / bb / Lam, Phi is 2N of scratch; never called there)
+    // (kSlim: no a11 / a21 / bb / Lam, Phi is 2N of scratch; never called there.  kBox: a11 /
+    // a21 are the lift's from its coefficient pass to the end of its recursion, vlo / vhi's after)
     __device__ __forceinline__ double* a11() const { return base + 3 * n(); }         // n()
     __device__ __forceinline__ double* a21() const { return base + 4 * n(); }         // n()
     __device__ __forceinline__ double* bb() const { return base + 5 * n(); }          // n()
@@ -239,9 +254,16 @@ struct WS {
     __device__ __forceinline__ double* dr() const { return base + (kPair ? oDrn(n()) : oV() + (kRi + 12 + kUo) * n() + 3); }    // N: d masked to b < q (GI)
     __device__ __forceinline__ double* irn() const { return base + (kPair ? oIrnn(n()) : oV() + (kRi + 13 + kUo) * n() + 3); }   // 2N: 1/rn_r (0: const row)
     __device__ __forceinline__ double* ssg() const { return base + oV() + (kRi + 15 + kUo) * n() + 3; }   // N: sign of general row s
-    // per-QP constants hoisted out of the solver loops (not kSlim: recomputed from D)
-    __device__ __forceinline__ double* vlo() const { return base + oV() + (kRi + 17) * n() + 3; }   // N: umin/D_j
-    __device__ __forceinline__ double* vhi() const { return base + oV() + (kRi + 18) * n() + 3; }   // N: umax/D_j
+    // per-QP constants hoisted out of the solver loops (kSlim without kBox: recomputed from D;
+    // kBox: in a11 / a21's 2N doubles, which are dead once the lift's recursion has run)
+    __device__ __forceinline__ double* vlo() const {                                                 // N: umin/D_j
+        if constexpr (kBox) return a11();
+        else return base + oV() + (kRi + 17) * n() + 3;
+    }
+    __device__ __forceinline__ double* vhi() const {                                                 // N: umax/D_j
+        if constexpr (kBox) return a21();
+        else return base + oV() + (kRi + 18) * n() + 3;
+    }
     // 1/L(k,k) (Cholesky), 1/K(k,k) (Schur), contiguous; 1/|D (e_i - e_{i-1})|: in the far block when kSlim
     __device__ __forceinline__ double* ldi() const {
         if constexpr (kSlim) return far + n() * ldj() + (n() + 1) * ldj();
@@ -333,6 +355,10 @@ constexpr bool ws_pair_aligned() {
     // the lift's a11 / a21 (at 3N and 4N doubles, WS::a11 / a21)
     static_assert(W::oUn(20) % 2 == 0 && W::oDrn(20) % 2 == 0 && W::oVecn(20, 3) % 2 == 0, "U, dr, d on 16-byte offsets");
     static_assert(W::kAB == 2 && (3 * 20) % 2 == 0 && (4 * 20) % 2 == 0, "a11, a21 on 16-byte offsets");
+    // kBox: vlo / vhi are N doubles each, as a11 / a21 are (a21 starts N doubles behind a11, Phi
+    // N doubles behind a21), and they cost no LDS: one more 512-byte granule would cost the 16th wave
+    static_assert(W::oPhin(20) == 5 * 20 && W::kAB * 20 == 2 * 20, "a11 / a21 hold vlo / vhi: N doubles each, in front of Phi");
+    static_assert(ws_bytes(20, true) == 10224, "slim N = 20: the workspace's size is unchanged");
     return true;
 }
 static_assert(ws_pair_aligned<WS<20, false, true>>() && ws_pair_aligned<WS<20, true, true>>(), "slim N = 20: aligned pairs");

@@ -4,7 +4,9 @@ read-add-write of ntm_lds_stamps[i]; the code between two s_memtime is charged
 to the stamp the second one updates.  Static counts (loops counted once), so a
 guide to what a phase is made of, not a timing.  Per phase also the LDS read
 forms (tools/lds_forms.py): ds_read2_b64 and how many of them address adjacent
-elements, ds_read_b128, ds_read_b64, and the forms' LDS cycles by that tool's table.
+elements, ds_read_b128, ds_read_b64, and the forms' LDS cycles by that tool's table; and
+the fp64 divisions: v_rcp_f64 and the v_div_* family (v_div_scale, v_div_fmas, v_div_fixup:
+one v_div_fixup_f64 per division the compiler expanded).
 
     python tools/isa_phases.py /tmp/diag20.s [kernel-substring]
 """
@@ -80,10 +82,15 @@ def main():
                     seg[op[3:]] += 1
                 if op == "ds_read2_b64" and is_adjacent(ln):
                     seg["adj"] += 1
+            if op.startswith("v_rcp_f64"):
+                seg["rcp_f64"] += 1
+            elif op.startswith("v_div_"):
+                seg["div_*"] += 1
+                seg["divisions"] += op.startswith("v_div_fixup_f64")
         i += 1
     total["(tail)"].update(seg)
     keys = ("f64", "valu", "mask", "dpp", "lane", "salu", "lds", "scratch", "vmem", "other")
-    lkeys = ("read2_b64", "adj", "read_b128", "read_b64", "ldscyc")
+    lkeys = ("read2_b64", "adj", "read_b128", "read_b64", "ldscyc", "rcp_f64", "div_*", "divisions")
     print(f"{'phase':12s} " + " ".join(f"{k:>7s}" for k in keys) + "   total | " + " ".join(f"{k:>9s}" for k in lkeys))
     for name, c in sorted(total.items(), key=lambda kv: -sum(kv[1][k] for k in keys)):
         print(f"{name:12s} " + " ".join(f"{c[k]:7d}" for k in keys) + f"   {sum(c[k] for k in keys):5d} | " +
