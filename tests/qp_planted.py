@@ -27,13 +27,35 @@ Families (``FAMILIES``; ``make(family, N, rng)``):
     infeas2     plain + r.U <= -1 and -r.U <= -1                  -> flag -2
     infeas3     plain + U_0 <= 0, U_1 <= 0, -U_0 - U_1 <= -1      -> flag -2 (N >= 2)
 
+Families that make Goldfarb-Idnani take rows back (``DROP_FAMILIES``;
+``make_drop(family, N, draw)``, N >= 2; none of the twelve above ever drops a row
+or meets a dependent one on its way to flag 1):
+
+    drop        plain with lam in [20, 40] (the unconstrained minimiser lies far
+                from U*) + 2N+3 near rows with slack 1 or 2 at U*: many are
+                violated on the way, added and dropped again.  Kept only if the
+                counting copy of the oracle's loop (``gi_counted``) ends with
+                flag 1 after >= 2 drops
+    dropdep     drop + three pairs L_A[j] + c, -c with slack 1 each, whose sum is
+                an active row: with both in the set that row is dependent (a
+                dual-only step and a drop).  Kept only if flag 1 after >= 1
+                dependent event and >= 1 drop
+
+Both criteria are asked of two paths: the problem as stated (the NumPy oracle's)
+and its Jacobi-scaled form (``jacobi_scaled``: the units in which the C oracle
+and the device pick the most violated row).
+
 This is a plain helper module (no fixtures, no tests).
 """
 from __future__ import annotations
 
+import functools
+import math
 from dataclasses import dataclass, field
 
 import numpy as np
+
+from oracle import ntm_oracle as O
 
 U_TOL = 1e-10           # the project's QP bound (tests/test_gpu_parity.py)
 FLAG_OK, FLAG_INFEASIBLE, FLAG_NONFINITE = 1, -2, -7
@@ -41,14 +63,21 @@ FLAG_OK, FLAG_INFEASIBLE, FLAG_NONFINITE = 1, -2, -7
 FEASIBLE = ("plain", "dup", "weak", "eq", "dep", "vertex", "vertex_dup", "rowscale", "gscale", "bigm")
 INFEASIBLE = ("infeas2", "infeas3")
 FAMILIES = FEASIBLE + INFEASIBLE
+# Feasible too, but kept out of FAMILIES: batch(), family_batch() and every seed of
+# the twelve above (seed_of's family index) stay what they were.
+DROP_FAMILIES = ("drop", "dropdep")
+_SEED_ORDER = FAMILIES + DROP_FAMILIES
 
 HORIZONS_CPU = (1, 2, 3, 8, 16, 17, 32, 33, 64)
 HORIZONS_GPU = (1, 2, 3, 8, 15, 16, 17, 20, 32, 33, 50, 64)
 
 
-def families_for(N: int):
-    """Every family that exists at horizon N (infeas3 needs two variables)."""
-    return tuple(f for f in FAMILIES if not (f == "infeas3" and N < 2))
+def families_for(N: int, drops: bool = False):
+    """Every family that exists at horizon N (infeas3 needs two variables);
+    ``drops``: the drop families as well (N >= 2: at N = 1 the most violated row is
+    the final one, nothing is ever dropped)."""
+    fams = tuple(f for f in FAMILIES if not (f == "infeas3" and N < 2))
+    return fams + (DROP_FAMILIES if drops and N >= 2 else ())
 
 
 @dataclass
@@ -66,6 +95,7 @@ class Planted:
     LA: np.ndarray = field(default=None, repr=False)   # the rows with lam > 0 as drawn (unscaled)
     Lt: np.ndarray = field(default=None, repr=False)   # every row planted tight at U*, in the final units
     lam: np.ndarray = field(default=None, repr=False)  # their multipliers (>= 0)
+    path: dict = field(default=None, repr=False)       # drop families: gi_counted's adds, drops, deps
 
     @property
     def N(self):
@@ -202,7 +232,7 @@ def make(family: str, N: int, rng, m: int | None = None, nzero: int = 0, k: int 
 
 
 def seed_of(family: str, N: int, draw: int) -> int:
-    return 1000003 * FAMILIES.index(family) + 1009 * N + draw
+    return 1000003 * _SEED_ORDER.index(family) + 1009 * N + draw
 
 
 def batch(N: int, draws: int = 1, nzero: int = 2, families=None, m: int | None = None, first_draw: int = 0):
@@ -250,6 +280,202 @@ def check_kkt(p: Planted):
     for row in p.Lt:                                   # each planted row is among the tight ones
         assert np.any(np.all(tight == row[None, :], axis=1))
     return int(np.sum(r == 0.0))
+
+
+# ---- problems on which Goldfarb-Idnani drops rows and meets dependent ones
+
+def gi_counted(G, F, Lin, b):
+    """O.qp_dual_active_set's loop, statement for statement, with three counters.
+    Returns (U, flag, active rows, multipliers, iterations, counts) with counts =
+    {"adds", "drops", "deps", "deep"}: full steps that add the picked row, rows taken
+    out (after a partial step or a dual-only one), dual-only steps (the picked row
+    depends on the active ones: t2 = inf), and drops from position l of q active
+    rows with q - l >= 3 (two or more Givens rotations: only then does a rotated
+    column other than the discarded last one stay behind, which needs N >= 3 and
+    at N = 3 a full set).  iterations = adds + drops and
+    adds - drops = len(active) whenever it returns; make_drop holds it to the
+    oracle's own result on every problem it accepts."""
+    n, m = G.shape[0], Lin.shape[0]
+    max_iter = 10 * (n + m) + 50
+    cnt = {"adds": 0, "drops": 0, "deps": 0, "deep": 0}
+    assert np.all(np.isfinite(G)) and np.all(np.isfinite(F)) and np.all(np.isfinite(Lin)) and np.all(np.isfinite(b))
+    Nc, bc = -Lin, -b
+    nonzero = np.any(Nc != 0.0, axis=1)
+    if np.any((~nonzero) & (bc > O.CONST_ROW_TOL)):
+        return np.zeros(n), O.EXIT_INFEASIBLE, [], np.zeros(0), 0, cnt
+    nrm = np.linalg.norm(Nc, axis=1)
+    J = np.linalg.inv(np.linalg.cholesky(G)).T
+    U = -(J @ (J.T @ F))
+    R = np.zeros((n, n))
+    act: list[int] = []
+    u = np.zeros(0)
+    it = 0
+    while True:
+        s = Nc @ U - bc
+        viol = np.where(nonzero, s / np.where(nrm > 0, nrm, 1.0), np.inf)
+        if act:
+            viol[act] = np.inf
+        p = int(np.argmin(viol))
+        if viol[p] == np.inf or s[p] >= -1e-12 * max(nrm[p] * np.max(np.abs(U), initial=1.0), abs(bc[p])):
+            return U, O.EXIT_OK, act, u, it, cnt
+        up = np.append(u, 0.0)
+        while True:
+            it += 1
+            if it > max_iter:
+                return U, O.EXIT_MAXIT, act, up[:len(act)], it, cnt
+            q = len(act)
+            d = J.T @ Nc[p]
+            z = J[:, q:] @ d[q:]
+            r = np.linalg.solve(np.triu(R[:q, :q]), d[:q]) if q else np.zeros(0)
+            t1, l = math.inf, -1
+            for j in range(q):
+                if r[j] > 0.0:
+                    tj = up[j] / r[j]
+                    if tj < t1:
+                        t1, l = tj, j
+            zn = float(d[q:] @ d[q:])
+            sp = float(Nc[p] @ U - bc[p])
+            t2 = math.inf if zn <= 1e-300 or math.sqrt(zn) <= O.GI_DEP_TOL * np.linalg.norm(d) else -sp / zn
+            t = min(t1, t2)
+            if t == math.inf:
+                return np.zeros(n), O.EXIT_INFEASIBLE, act, up[:q], it, cnt
+            if t2 == math.inf:
+                cnt["deps"] += 1
+                cnt["drops"] += 1
+                cnt["deep"] += q - l >= 3
+                up[:q] = np.maximum(0.0, up[:q] - t * r)
+                up[q] += t
+                J, R = O._drop(J, R, q, l)
+                act.pop(l)
+                up = np.delete(up, l)
+                continue
+            U = U + t * z
+            up[:q] = np.maximum(0.0, up[:q] - t * r)
+            up[q] += t
+            if t == t2:
+                cnt["adds"] += 1
+                J, R = O._add(J, R, q, d)
+                act.append(p)
+                u = up
+                break
+            cnt["drops"] += 1
+            cnt["deep"] += q - l >= 3
+            J, R = O._drop(J, R, q, l)
+            act.pop(l)
+            up = np.delete(up, l)
+
+
+N_NEAR_PAIRS = 3
+DROP_SEARCH_CAP = 400
+
+
+def drop_rows(N: int) -> int:
+    """The most core rows a drop-family problem has: N/2 active, 2N+3 near, the pairs."""
+    return max(1, N // 2) + 2 * N + 3 + 2 * N_NEAR_PAIRS
+
+
+def _drop_candidate(family, N, rng, m, nzero):
+    """One draw of a drop-family problem, as yet unchecked.  min_iters = k holds on
+    any path; k + 2 drops is the NumPy oracle's count alone (the C oracle and the
+    device pick rows in Jacobi-scaled units and solve some of these in k)."""
+    A = _ints(rng, -2, 2, (N + 2, N))
+    G = A.T @ A + np.eye(N)
+    Us = _ints(rng, -3, 3, N)
+    LA = _independent_rows(rng, int(rng.integers(1, max(1, N // 2) + 1)), N)
+    k = LA.shape[0]
+    lam = _ints(rng, 20, 40, k)
+    F = -G @ Us - LA.T @ lam
+    near = _nonzero_rows(rng, 2 * N + 3, N)
+    L = np.vstack([LA, near])
+    bt = np.concatenate([LA @ Us, near @ Us + _ints(rng, 1, 2, near.shape[0])])
+    if family == "dropdep":
+        for _ in range(N_NEAR_PAIRS):
+            j = int(rng.integers(0, k))
+            while True:
+                c = _nonzero_rows(rng, 1, N)[0]
+                if (LA[j] + c).any():
+                    break
+            pair = np.vstack([LA[j] + c, -c])
+            L, bt = np.vstack([L, pair]), np.concatenate([bt, pair @ Us + 1.0])
+    n_core = L.shape[0]
+    n_in = m - n_core - nzero
+    if n_in < 0:
+        raise ValueError(f"{family}, N = {N}: m = {m} < {n_core} core rows + {nzero} zero rows")
+    Li = _ints(rng, -3, 3, (n_in, N))
+    Lin = np.vstack([L, Li, np.zeros((nzero, N))])
+    b = np.concatenate([bt, Li @ Us + _ints(rng, 1, 3, n_in), np.ones(nzero)])
+    perm = rng.permutation(m)
+    return Planted(family, G, F, Lin[perm], b[perm], Us, FLAG_OK, np.ones(N), n_core, k, LA, LA.copy(), lam)
+
+
+def jacobi_scaled(p: Planted):
+    """(G, F, Lin, b) of p in the units the device and the C oracle pick rows in:
+    V = U/d with d_j = 1/sqrt(G_jj), every ordinary row divided by |Lin_i o d|_2.
+    The same problem, but rounded, and Goldfarb-Idnani's most violated row is
+    another one: its path differs from the unscaled statement's."""
+    d = 1.0 / np.sqrt(np.diag(p.G))
+    Ls = p.Lin * d[None, :]
+    rn = np.linalg.norm(Ls, axis=1)
+    rn = np.where(rn > 0.0, rn, 1.0)
+    return p.G * d[:, None] * d[None, :], p.F * d, Ls / rn[:, None], p.b / rn
+
+
+def make_drop(family: str, N: int, draw: int, m: int | None = None, nzero: int = 0, min_drops: int | None = None):
+    """The first candidate of (family, N, draw) that gi_counted solves with flag 1
+    on the path the family is about: ``min_drops`` drops (default 2 for drop, 1 for
+    dropdep) and, for dropdep, one dependent event; both as stated (the NumPy
+    oracle's path, exact data) and Jacobi-scaled (the path of the device's
+    units: at N = 2 the two have little in common).  Candidate c is drawn from the
+    seed (seed_of(family, N, draw), c), c < DROP_SEARCH_CAP; the whole problem,
+    filler rows and permutation included, is what is tried, since the filler rows
+    have small slack too and steer the path.  Running out of candidates raises."""
+    if family not in DROP_FAMILIES:
+        raise ValueError(family)
+    if N < 2:
+        raise ValueError("the drop families need N >= 2")
+    if m is None:
+        m = drop_rows(N) + 3 + nzero
+    if min_drops is None:
+        min_drops = 2 if family == "drop" else 1
+    def meets(flag, cnt):
+        return flag == FLAG_OK and cnt["drops"] >= min_drops and (family != "dropdep" or cnt["deps"] >= 1)
+
+    for c in range(DROP_SEARCH_CAP):
+        p = _drop_candidate(family, N, np.random.default_rng([seed_of(family, N, draw), c]), m, nzero)
+        U, flag, act, u, it, cnt = gi_counted(p.G, p.F, p.Lin, p.b)
+        if not meets(flag, cnt):
+            continue
+        _, flags, _, _, _, cnts = gi_counted(*jacobi_scaled(p))
+        if not meets(flags, cnts):
+            continue
+        Uo, fo, acto, uo, ito = O.qp_dual_active_set(p.G, p.F, p.Lin, p.b)
+        assert fo == flag and ito == it and list(acto) == list(act), (family, N, draw, c)
+        assert np.array_equal(Uo, U) and np.array_equal(uo, u), (family, N, draw, c)
+        assert it == cnt["adds"] + cnt["drops"] and cnt["adds"] - cnt["drops"] == len(act), (family, N, draw, c, cnt)
+        p.path = dict(cnt, candidate=c, iterations=it, scaled_drops=cnts["drops"], scaled_deps=cnts["deps"],
+                      scaled_deep=cnts["deep"])
+        return p
+    raise RuntimeError(f"{family}, N = {N}, draw {draw}: no accepted problem in {DROP_SEARCH_CAP} candidates")
+
+
+@functools.lru_cache(maxsize=None)
+def _drop_batch(N: int):
+    m = drop_rows(N) + 3 + 2
+    ps = []
+    for d in range(4):
+        ps += [make_drop("drop", N, d, m=m, nzero=2), make_drop("dropdep", N, d, m=m, nzero=2)]
+    ps.insert(4, make("plain", N, np.random.default_rng(seed_of("plain", N, 3)), m=m, nzero=2))
+    assert len(ps) % 4 != 0 and {p.m for p in ps} == {m} and m <= 8 * N + 4
+    return tuple(ps)
+
+
+def drop_batch(N: int):
+    """Four drop and four dropdep problems, alternating, with one plain neighbour in
+    the middle: B = 9 (not a multiple of the four scenarios a wave of k_qp holds at
+    N <= 16, and every wave mixes long and short add/drop sequences), common
+    m = drop_rows(N) + 5, two all-zero rows with b = 1 in every scenario.  Built
+    once per horizon; the problems are shared, leave them unchanged."""
+    return list(_drop_batch(N))
 
 
 # ---- inputs with no optimum: the non-finite contract (flag -7, U = 0)
