@@ -39,11 +39,17 @@ extern "C" {
 
 #define NTM_MPC_ABI_VERSION 7   /* v7: ntm_estimator, ntm_mpc_step_est / run_est, ntm_meas_sample (additive);
                                    still 7: ntm_mpc_run_from / run_est_from (additive, NTM_MPC_HAS_RUN_FROM);
+                                   still 7: ntm_delay, ntm_mpc_step_dly / run_dly / run_dly_from (additive,
+                                   NTM_MPC_HAS_INPUT_DELAY);
                                    v6: ntm_observer, ntm_mpc_step_obs / run_obs (additive);
                                    v5: ntm_config.Ru (input weight); v4: ntm_scenario_gen */
 #define NTM_MAX_N 64
 /* ntm_mpc_run_from* / ntm_mpc_run_est_from* exist (added without an ABI bump) */
 #define NTM_MPC_HAS_RUN_FROM 1
+/* ntm_delay and ntm_mpc_step_dly* / ntm_mpc_run_dly* / ntm_mpc_run_dly_from* exist (added
+ * without an ABI bump) */
+#define NTM_MPC_HAS_INPUT_DELAY 1
+#define NTM_MAX_DELAY 8         /* longest actuator dead time, in sampling periods */
 
 /* Physics constants, NTM_MPC_Sim.m:5-22 (same names and units). */
 typedef struct {
@@ -526,6 +532,90 @@ int ntm_mpc_run_est_from_device(ntm_ctx* ctx, const ntm_physics* phys,
                                 double* uk, double* Uk, double* wpred, double* dk,
                                 double* xhk, double* yk, int32_t* exitflag,
                                 int32_t* inner_iters, void* stream);
+/* ---- actuator dead time: delayed inputs and a delay-compensating plan (still ABI v7) ---- */
+/* The estimator entry points above apply the input planned at step k at step k.  Here the
+ * plant applies the input commanded d = steps sampling periods ago, and one more value is
+ * carried per scenario: u_queue[d], the inputs still under way, oldest first (u_queue[0]
+ * reaches the plant now, u_queue[d-1] is last step's command).  One step, per scenario:
+ *   plan state z = x_hat.  With predict = 1, for j = 0 .. d-1: z <- k_m's one-step map
+ *          WITH d_hat (C + d_hat, the model the controller lifts) and without disturbance
+ *          at (z, u_queue[j]) from rho(z).  predict = 0 keeps z = x_hat: a controller that
+ *          does not know about the delay, for comparison studies;
+ *   controller: ntm_mpc_step_est's MPC step FROM z instead of x_hat: U, x_pred, rho, U_old,
+ *          the flag, the iteration count and the active sets; u_cmd = U[0];
+ *   u_app  = d > 0 ? u_queue[0] : u_cmd;
+ *   plant, y, m, d_hat, x_hat: exactly ntm_mpc_step_est's with u_app where it uses U[0]
+ *          (x_next = k_p's step at (x, u_app) + disturbance; m = k_m's map without d_hat at
+ *          (x_hat, u_app));
+ *   queue  u_queue[j] <- u_queue[j+1] for j < d-1, u_queue[d-1] <- u_cmd.
+ * With steps = 0 the step is ntm_mpc_step_est's bit for bit, whatever predict is.  The
+ * generator's time indices are unchanged, and the initial rho of a loop stays
+ * repmat(rho(xhat0)) of the model, so ntm_mpc_init* serves hand-stepped loops as before.
+ * A non-finite queue entry makes z non-finite (under predict); that scenario then behaves
+ * as one with a non-finite x_hat: flag -7, U = 0, its neighbours untouched.  Every horizon
+ * runs on the runtime-N kernels; the queue lives in registers for a whole run.
+ * Validation is the estimator entry points' plus NTM_E_INVALID for a NULL delay, steps
+ * outside [0, NTM_MAX_DELAY], predict outside {0, 1}, a NULL queue with steps > 0 (uq0 of
+ * ntm_mpc_run_dly excepted: NULL = zeros) and a queue that overlaps another argument. */
+typedef struct {
+    int32_t steps;          /* dead time d in sampling periods, 0 .. NTM_MAX_DELAY          */
+    int32_t predict;        /* 1: plan from the state predicted for the command's arrival;
+                               0: plan from x_hat                                            */
+} ntm_delay;
+/* ntm_mpc_step_est with the dead time.  u_queue[steps] per scenario, in/out (may be NULL
+ * when steps == 0); x_plan[2] per scenario (output, may be NULL): the z the plan was made
+ * from; u_applied[1] per scenario (output, may be NULL): u_app. */
+int ntm_mpc_step_dly(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg,
+                     const ntm_estimator* est, const ntm_delay* delay, int64_t B,
+                     const double* x_k, double* rho, double* U_old, double* d_hat,
+                     double* x_hat, double* u_queue, double* U, double* x_pred,
+                     double* x_next, double* y, double* x_plan, double* u_applied,
+                     int32_t* exitflag, int32_t* inner_iters, int32_t* active_ws);
+int ntm_mpc_step_dly_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg,
+                            const ntm_estimator* est, const ntm_delay* delay, int64_t B,
+                            const double* x_k, double* rho, double* U_old, double* d_hat,
+                            double* x_hat, double* u_queue, double* U, double* x_pred,
+                            double* x_next, double* y, double* x_plan, double* u_applied,
+                            int32_t* exitflag, int32_t* inner_iters, int32_t* active_ws,
+                            void* stream);
+/* ntm_mpc_run_est with the dead time; the queue stays on chip across the k_sim steps.
+ * uq0[steps] per scenario is the initial queue (NULL: zeros, power off until the first
+ * command arrives).  uak[k_sim] per scenario (may be NULL): the applied input of step k;
+ * uk stays the commanded U[0], so uak[k + steps] == uk[k].  xpk[2 k_sim] per scenario (may
+ * be NULL): the plan state z of step k. */
+int ntm_mpc_run_dly(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg,
+                    const ntm_estimator* est, const ntm_delay* delay, int64_t B,
+                    int32_t k_sim, const double* x0, const double* d0, const double* xhat0,
+                    const double* uq0, double* xk, double* uk, double* Uk, double* wpred,
+                    double* dk, double* xhk, double* yk, double* uak, double* xpk,
+                    int32_t* exitflag, int32_t* inner_iters);
+int ntm_mpc_run_dly_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg,
+                           const ntm_estimator* est, const ntm_delay* delay, int64_t B,
+                           int32_t k_sim, const double* x0, const double* d0,
+                           const double* xhat0, const double* uq0, double* xk, double* uk,
+                           double* Uk, double* wpred, double* dk, double* xhk, double* yk,
+                           double* uak, double* xpk, int32_t* exitflag,
+                           int32_t* inner_iters, void* stream);
+/* ntm_mpc_run_est_from with the dead time (ntm_mpc_run_from's rules hold): u_queue[steps]
+ * per scenario is carried in and out with the rest of the state, required when steps > 0.
+ * The same bits come out whether k steps run in one call or split over several.  steps
+ * must not change between the chunks of one loop (the queue's length is the delay);
+ * predict and est may. */
+int ntm_mpc_run_dly_from(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg,
+                         const ntm_estimator* est, const ntm_delay* delay, int64_t B,
+                         int32_t k_sim, double* x, double* rho, double* U_old,
+                         int32_t* active_ws, double* d_hat, double* x_hat, double* u_queue,
+                         double* xk, double* uk, double* Uk, double* wpred, double* dk,
+                         double* xhk, double* yk, double* uak, double* xpk,
+                         int32_t* exitflag, int32_t* inner_iters);
+int ntm_mpc_run_dly_from_device(ntm_ctx* ctx, const ntm_physics* phys,
+                                const ntm_config* cfg, const ntm_estimator* est,
+                                const ntm_delay* delay, int64_t B, int32_t k_sim, double* x,
+                                double* rho, double* U_old, int32_t* active_ws,
+                                double* d_hat, double* x_hat, double* u_queue, double* xk,
+                                double* uk, double* Uk, double* wpred, double* dk,
+                                double* xhk, double* yk, double* uak, double* xpk,
+                                int32_t* exitflag, int32_t* inner_iters, void* stream);
 /* Host-side unit samples of the measurement noise for scenarios first_id .. first_id + B
  * - 1 at time index k (out2: 2 per scenario: n(id, k, 2), n(id, k, 3)); the sibling of
  * ntm_scenario_sample, the same code the kernels run. */

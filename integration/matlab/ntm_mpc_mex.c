@@ -69,6 +69,23 @@
  *       ntm_mpc_mex('run_est_from', x, rho, Uold, ws, d_hat, x_hat, k_sim, est[, cfg])
  *       'run_est' from a carried state (ntm_mpc_run_est_from): d_hat and x_hat 2-by-B
  *       are carried too; the state comes back as outputs 10 to 15.
+ *   [U, x_pred, x_next, exitflag, iters, rho, Uold, ws, d_hat, x_hat, y, u_queue, x_plan, u_app] = ...
+ *       ntm_mpc_mex('step_dly', x_k, rho, Uold, d_hat, x_hat, u_queue, est, dly[, cfg[, ws]])
+ *       'step_est' with an actuator dead time (ntm_mpc_step_dly, NTM_MPC_HAS_INPUT_DELAY):
+ *       dly is a struct with steps (0 .. 8) and predict (missing: 1); u_queue steps-by-B
+ *       holds the inputs under way, oldest first ([] when steps is 0), and comes back
+ *       shifted with the new command at its end as output 12; x_plan 2-by-B is the state
+ *       the plan was made from, u_app 1-by-B the input the plant received.
+ *   [xk, uk, Uk, wpred, exitflag, iters, dk, xhk, yk, uak, xpk] = ...
+ *       ntm_mpc_mex('run_dly', x0, k_sim, est, dly[, cfg[, d0[, xhat0[, uq0]]]])
+ *       'run_est' with the dead time (ntm_mpc_run_dly): uq0 steps-by-B the initial queue
+ *       (omitted or []: zeros); uak k_sim-by-B the applied inputs (uk stays the commanded
+ *       ones), xpk 2 k_sim-by-B the plan states.
+ *   [xk, uk, Uk, wpred, exitflag, iters, dk, xhk, yk, uak, xpk, x, rho, Uold, ws, d_hat, x_hat, u_queue] = ...
+ *       ntm_mpc_mex('run_dly_from', x, rho, Uold, ws, d_hat, x_hat, u_queue, k_sim, est, dly[, cfg])
+ *       'run_dly' from a carried state (ntm_mpc_run_dly_from): the queue is carried too;
+ *       the state comes back as outputs 12 to 18.  dly.steps must not change between the
+ *       chunks of one loop.
  *   ntm_mpc_mex('scenarios', gen)                               
  *       gen struct with any of seed, first_id, k0, sigma_w, sigma_omega,
  *       jbs_spread, wdep_spread (ntm_scenario_gen): per-scenario plasma and
@@ -526,6 +543,164 @@ static void do_run_est_from(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     }
 }
 
+/* dly struct with steps (0 .. NTM_MAX_DELAY) and predict (missing: 1) (ntm_delay) */
+static ntm_delay read_dly(const mxArray* s) {
+    ntm_delay d;
+    if (!s || !mxIsStruct(s)) mexErrMsgIdAndTxt("ntm:arg", "dly must be a struct with steps and predict");
+    d.steps = (int32_t)scalar_field(s, "steps", 0.0);
+    d.predict = (int32_t)scalar_field(s, "predict", 1.0);
+    if (d.steps < 0 || d.steps > NTM_MAX_DELAY)
+        mexErrMsgIdAndTxt("ntm:arg", "dly.steps must be in 0 .. %d", (int)NTM_MAX_DELAY);
+    return d;
+}
+
+/* the queue of pending inputs, steps-by-B; with steps == 0 any empty array will do */
+static void in_queue(const mxArray* a, size_t steps, size_t B, const char* name) {
+    if (steps == 0 && mxIsDouble(a) && mxGetNumberOfElements(a) == 0) return;
+    in_matrix(a, steps, B, name);
+}
+
+static void put_outs(int nlhs, mxArray* plhs[], mxArray** outs, int n) {
+    for (int i = 0; i < n; ++i) {
+        if (i < (nlhs > 0 ? nlhs : 1)) plhs[i] = outs[i];
+        else mxDestroyArray(outs[i]);
+    }
+}
+
+/* 'step_est' with the dead time (ntm_mpc_step_dly): u_queue goes in after x_hat, dly after
+ * est; the shifted queue, the plan state and the applied input are outputs 12 to 14 */
+static void do_step_dly(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    if (nrhs < 9)
+        mexErrMsgIdAndTxt("ntm:arg",
+                          "usage: ntm_mpc_mex('step_dly', x_k, rho, Uold, d_hat, x_hat, u_queue, est, dly[, cfg[, ws]])");
+    const ntm_estimator e = read_est(prhs[7]);
+    const ntm_delay d = read_dly(prhs[8]);
+    const ntm_config c = read_cfg(nrhs > 9 ? prhs[9] : NULL);
+    ntm_physics p;
+    ntm_physics_default(&p);
+    const size_t B = mxGetN(prhs[1]), N = (size_t)c.N;
+    const double* x = in_matrix(prhs[1], 2, B, "x_k");
+    in_matrix(prhs[2], 3 * N, B, "rho");
+    in_matrix(prhs[3], N, B, "Uold");
+    in_matrix(prhs[4], 2, B, "d_hat");
+    in_matrix(prhs[5], 2, B, "x_hat");
+    in_queue(prhs[6], (size_t)d.steps, B, "u_queue");
+    mxArray* rho = mxDuplicateArray(prhs[2]);
+    mxArray* uold = mxDuplicateArray(prhs[3]);
+    mxArray* dh = mxDuplicateArray(prhs[4]);
+    mxArray* xh = mxDuplicateArray(prhs[5]);
+    mxArray* uq = d.steps ? mxDuplicateArray(prhs[6]) : mxCreateDoubleMatrix(0, B, mxREAL);
+    mxArray* U = mxCreateDoubleMatrix(N, B, mxREAL);
+    mxArray* xp = mxCreateDoubleMatrix(2 * (N + 1), B, mxREAL);
+    mxArray* xn = mxCreateDoubleMatrix(2, B, mxREAL);
+    mxArray* y = mxCreateDoubleMatrix(2, B, mxREAL);
+    mxArray* z = mxCreateDoubleMatrix(2, B, mxREAL);
+    mxArray* ua = mxCreateDoubleMatrix(1, B, mxREAL);
+    mxArray* fl = mxCreateNumericMatrix(1, B, mxINT32_CLASS, mxREAL);
+    mxArray* it = mxCreateNumericMatrix(1, B, mxINT32_CLASS, mxREAL);
+    mxArray* ws = NULL;
+    if (nrhs > 10) {
+        in_ws(prhs[10], N, B);
+        ws = mxDuplicateArray(prhs[10]);
+    } else {
+        ws = mxCreateNumericMatrix(2 * (N + 1), B, mxINT32_CLASS, mxREAL);
+        int32_t* wp = mxGetInt32s(ws);
+        for (size_t i = 0; i < B * 2 * (N + 1); ++i) wp[i] = -1;
+    }
+    check(ntm_mpc_step_dly(ctx(), &p, &c, &e, &d, (int64_t)B, x, mxGetDoubles(rho), mxGetDoubles(uold), mxGetDoubles(dh),
+                           mxGetDoubles(xh), d.steps ? mxGetDoubles(uq) : NULL, mxGetDoubles(U), mxGetDoubles(xp),
+                           mxGetDoubles(xn), mxGetDoubles(y), mxGetDoubles(z), mxGetDoubles(ua), mxGetInt32s(fl),
+                           mxGetInt32s(it), mxGetInt32s(ws)),
+          "ntm_mpc_step_dly");
+    mxArray* outs[14] = {U, xp, xn, fl, it, rho, uold, ws, dh, xh, y, uq, z, ua};
+    put_outs(nlhs, plhs, outs, 14);
+}
+
+/* 'run_est' with the dead time (ntm_mpc_run_dly): uak and xpk are outputs 10 and 11 */
+static void do_run_dly(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    if (nrhs < 5)
+        mexErrMsgIdAndTxt("ntm:arg", "usage: ntm_mpc_mex('run_dly', x0, k_sim, est, dly[, cfg[, d0[, xhat0[, uq0]]]])");
+    const ntm_estimator e = read_est(prhs[3]);
+    const ntm_delay d = read_dly(prhs[4]);
+    const ntm_config c = read_cfg(nrhs > 5 ? prhs[5] : NULL);
+    ntm_physics p;
+    ntm_physics_default(&p);
+    const size_t B = mxGetN(prhs[1]), N = (size_t)c.N;
+    const double* x0 = in_matrix(prhs[1], 2, B, "x0");
+    const double* d0 = opt_matrix(nrhs, prhs, 6, B, "d0");
+    const double* h0 = opt_matrix(nrhs, prhs, 7, B, "xhat0");
+    const double* q0 = NULL;
+    if (nrhs > 8 && !(mxIsDouble(prhs[8]) && mxGetNumberOfElements(prhs[8]) == 0))
+        q0 = in_matrix(prhs[8], (size_t)d.steps, B, "uq0");
+    const int k = (int)mxGetScalar(prhs[2]);
+    if (k < 1) mexErrMsgIdAndTxt("ntm:arg", "k_sim must be >= 1");
+    mxArray* xk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
+    mxArray* uk = mxCreateDoubleMatrix((size_t)k, B, mxREAL);
+    mxArray* Uk = mxCreateDoubleMatrix(N * (size_t)k, B, mxREAL);
+    mxArray* wp = mxCreateDoubleMatrix((N + 1) * (size_t)k, B, mxREAL);
+    mxArray* fl = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
+    mxArray* it = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
+    mxArray* dk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
+    mxArray* xhk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
+    mxArray* yk = mxCreateDoubleMatrix(2 * (size_t)k, B, mxREAL);
+    mxArray* uak = mxCreateDoubleMatrix((size_t)k, B, mxREAL);
+    mxArray* xpk = mxCreateDoubleMatrix(2 * (size_t)k, B, mxREAL);
+    check(ntm_mpc_run_dly(ctx(), &p, &c, &e, &d, (int64_t)B, k, x0, d0, h0, q0, mxGetDoubles(xk), mxGetDoubles(uk),
+                          mxGetDoubles(Uk), mxGetDoubles(wp), mxGetDoubles(dk), mxGetDoubles(xhk), mxGetDoubles(yk),
+                          mxGetDoubles(uak), mxGetDoubles(xpk), mxGetInt32s(fl), mxGetInt32s(it)),
+          "ntm_mpc_run_dly");
+    mxArray* outs[11] = {xk, uk, Uk, wp, fl, it, dk, xhk, yk, uak, xpk};
+    put_outs(nlhs, plhs, outs, 11);
+}
+
+/* 'run_dly' from a carried state (ntm_mpc_run_dly_from): the state is outputs 12 to 18 */
+static void do_run_dly_from(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    if (nrhs < 11)
+        mexErrMsgIdAndTxt(
+            "ntm:arg",
+            "usage: ntm_mpc_mex('run_dly_from', x, rho, Uold, ws, d_hat, x_hat, u_queue, k_sim, est, dly[, cfg])");
+    const ntm_estimator e = read_est(prhs[9]);
+    const ntm_delay d = read_dly(prhs[10]);
+    const ntm_config c = read_cfg(nrhs > 11 ? prhs[11] : NULL);
+    ntm_physics p;
+    ntm_physics_default(&p);
+    const size_t B = mxGetN(prhs[1]), N = (size_t)c.N;
+    in_matrix(prhs[1], 2, B, "x");
+    in_matrix(prhs[2], 3 * N, B, "rho");
+    in_matrix(prhs[3], N, B, "Uold");
+    in_ws(prhs[4], N, B);
+    in_matrix(prhs[5], 2, B, "d_hat");
+    in_matrix(prhs[6], 2, B, "x_hat");
+    in_queue(prhs[7], (size_t)d.steps, B, "u_queue");
+    const int k = in_ksim(prhs[8]);
+    mxArray* x = mxDuplicateArray(prhs[1]);
+    mxArray* rho = mxDuplicateArray(prhs[2]);
+    mxArray* uold = mxDuplicateArray(prhs[3]);
+    mxArray* ws = mxDuplicateArray(prhs[4]);
+    mxArray* dh = mxDuplicateArray(prhs[5]);
+    mxArray* xh = mxDuplicateArray(prhs[6]);
+    mxArray* uq = d.steps ? mxDuplicateArray(prhs[7]) : mxCreateDoubleMatrix(0, B, mxREAL);
+    mxArray* xk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
+    mxArray* uk = mxCreateDoubleMatrix((size_t)k, B, mxREAL);
+    mxArray* Uk = mxCreateDoubleMatrix(N * (size_t)k, B, mxREAL);
+    mxArray* wp = mxCreateDoubleMatrix((N + 1) * (size_t)k, B, mxREAL);
+    mxArray* fl = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
+    mxArray* it = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
+    mxArray* dk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
+    mxArray* xhk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
+    mxArray* yk = mxCreateDoubleMatrix(2 * (size_t)k, B, mxREAL);
+    mxArray* uak = mxCreateDoubleMatrix((size_t)k, B, mxREAL);
+    mxArray* xpk = mxCreateDoubleMatrix(2 * (size_t)k, B, mxREAL);
+    check(ntm_mpc_run_dly_from(ctx(), &p, &c, &e, &d, (int64_t)B, k, mxGetDoubles(x), mxGetDoubles(rho),
+                               mxGetDoubles(uold), mxGetInt32s(ws), mxGetDoubles(dh), mxGetDoubles(xh),
+                               d.steps ? mxGetDoubles(uq) : NULL, mxGetDoubles(xk), mxGetDoubles(uk), mxGetDoubles(Uk),
+                               mxGetDoubles(wp), mxGetDoubles(dk), mxGetDoubles(xhk), mxGetDoubles(yk),
+                               mxGetDoubles(uak), mxGetDoubles(xpk), mxGetInt32s(fl), mxGetInt32s(it)),
+          "ntm_mpc_run_dly_from");
+    mxArray* outs[18] = {xk, uk, Uk, wp, fl, it, dk, xhk, yk, uak, xpk, x, rho, uold, ws, dh, xh, uq};
+    put_outs(nlhs, plhs, outs, 18);
+}
+
 static void do_scenarios(int nrhs, const mxArray* prhs[]) {
     if (nrhs < 2 || (mxIsDouble(prhs[1]) && mxGetNumberOfElements(prhs[1]) == 0)) {
         check(ntm_ctx_set_scenarios(ctx(), NULL), "ntm_ctx_set_scenarios");
@@ -559,6 +734,9 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     else if (!strcmp(cmd, "run_est")) do_run_est(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "run_from")) do_run_from(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "run_est_from")) do_run_est_from(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "step_dly")) do_step_dly(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "run_dly")) do_run_dly(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "run_dly_from")) do_run_dly_from(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "scenarios")) do_scenarios(nrhs, prhs);
     else if (!strcmp(cmd, "close")) release();
     else mexErrMsgIdAndTxt("ntm:arg", "unknown command '%s'", cmd);

@@ -821,6 +821,32 @@ int validate_est(ntm_ctx* ctx, const ntm_config* c, const ntm_estimator* est) {
         return fail(ctx, NTM_E_UNSUPPORTED, "estimator: the literal D4 / D6 / D13 switches are not supported");
     return NTM_OK;
 }
+DlyOpt dly_opt(const ntm_delay* delay) { return DlyOpt{delay->steps, delay->predict}; }
+// call only after validate_dly accepted the delay
+size_t queue_bytes(const ntm_delay* delay, int64_t B) { return (size_t)delay->steps * (size_t)B * sizeof(double); }
+// the dead-time entry points' own checks (after the estimator's): the options, the queue
+// (steps per scenario; null_ok: ntm_mpc_run_dly's uq0, where null means zeros), and that it
+// shares no byte with another array of the call (others: pointer and bytes, null skipped)
+struct Span {
+    const void* p;
+    size_t bytes;
+};
+int validate_dly(ntm_ctx* ctx, const ntm_delay* delay, const void* queue, int64_t B, bool null_ok,
+                 std::initializer_list<Span> others) {
+    if (!delay) return fail(ctx, NTM_E_INVALID, "null delay");
+    if (delay->steps < 0 || delay->steps > NTM_MAX_DELAY)
+        return fail(ctx, NTM_E_INVALID, "delay: steps out of range [0, 8]");
+    if (delay->predict != 0 && delay->predict != 1) return fail(ctx, NTM_E_INVALID, "delay: predict must be 0 or 1");
+    if (delay->steps == 0) return NTM_OK;
+    if (!queue) return null_ok ? NTM_OK : fail(ctx, NTM_E_INVALID, "delay: null queue with steps > 0");
+    const uintptr_t q0 = reinterpret_cast<uintptr_t>(queue), q1 = q0 + queue_bytes(delay, B);
+    for (const Span& o : others) {
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(o.p), a1 = a0 + o.bytes;
+        if (o.p && o.bytes && q0 < q1 && a0 < q1 && q0 < a1)
+            return fail(ctx, NTM_E_INVALID, "delay: the queue overlaps another argument");
+    }
+    return NTM_OK;
+}
 // validate, then the feedback options' own checks
 int validate(ntm_ctx* ctx, const ntm_physics* p, const ntm_config* c, int64_t B, const ntm_observer* obs) {
     const int rc = validate(ctx, p, c, B);
@@ -1426,6 +1452,183 @@ int ntm_mpc_run_est_from(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config
     if ((rc = stage_in(ctx, arrs))) return rc;
     rc = ntm_mpc_run_est_from_device(ctx, phys, cfg, est, B, k_sim, dx, drho, duo, dws, ddh, dxh, dxk, duk, dUk, dwp, ddk,
                                      dxhk, dyk, dfl, dit, ctx->stream);
+    return stage_out(ctx, rc, arrs);
+}
+
+// ---- actuator dead time: every horizon on the runtime-N kernels, as the estimator's
+int ntm_mpc_step_dly_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est,
+                            const ntm_delay* delay, int64_t B, const double* x_k, double* rho, double* U_old,
+                            double* d_hat, double* x_hat, double* u_queue, double* U, double* x_pred, double* x_next,
+                            double* y, double* x_plan, double* u_applied, int32_t* exitflag, int32_t* inner_iters,
+                            int32_t* active_ws, void* stream) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B, est);
+    if (rc) return rc;
+    const Bytes n(cfg->N, B);
+    if ((rc = validate_dly(ctx, delay, u_queue, B, false,
+                           {{x_k, n.x}, {rho, n.rho}, {U_old, n.u}, {d_hat, n.x}, {x_hat, n.x}, {U, n.u},
+                            {x_pred, n.xp}, {x_next, n.x}, {y, n.x}, {x_plan, n.x}, {u_applied, n.x / 2},
+                            {exitflag, n.i}, {inner_iters, n.i}, {active_ws, n.ws}})))
+        return rc;
+    if (!d_hat) return fail(ctx, NTM_E_INVALID, "null d_hat");
+    if (!x_hat) return fail(ctx, NTM_E_INVALID, "null x_hat");
+    if (B == 0) return NTM_OK;
+    if (any_null({x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters})) return fail(ctx, NTM_E_INVALID, "null array");
+    const Prob pb = launch_prob(ctx, phys, cfg);
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define CALL(P_)                                                                                                 \
+    launch_sibling<P_>(ctx, k_mpc_step_dly<P_>, "k_mpc_step_dly launch", pb, B, st, pb, B, x_k, rho, U_old, U, \
+                       x_pred, x_next, exitflag, inner_iters, active_ws, d_hat, x_hat, y, est_opt(est),         \
+                       dly_opt(delay), u_queue, x_plan, u_applied)
+    return NTM_DISPATCH_LANES(cfg->N, CALL);
+#undef CALL
+}
+
+int ntm_mpc_step_dly(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est,
+                     const ntm_delay* delay, int64_t B, const double* x_k, double* rho, double* U_old, double* d_hat,
+                     double* x_hat, double* u_queue, double* U, double* x_pred, double* x_next, double* y,
+                     double* x_plan, double* u_applied, int32_t* exitflag, int32_t* inner_iters, int32_t* active_ws) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B, est);
+    if (rc) return rc;
+    const Bytes n(cfg->N, B);
+    if ((rc = validate_dly(ctx, delay, u_queue, B, false,
+                           {{x_k, n.x}, {rho, n.rho}, {U_old, n.u}, {d_hat, n.x}, {x_hat, n.x}, {U, n.u},
+                            {x_pred, n.xp}, {x_next, n.x}, {y, n.x}, {x_plan, n.x}, {u_applied, n.x / 2},
+                            {exitflag, n.i}, {inner_iters, n.i}, {active_ws, n.ws}})))
+        return rc;
+    if (!d_hat) return fail(ctx, NTM_E_INVALID, "null d_hat");
+    if (!x_hat) return fail(ctx, NTM_E_INVALID, "null x_hat");
+    if (B == 0) return NTM_OK;
+    if (any_null({x_k, rho, U_old, U, x_pred, x_next, exitflag, inner_iters})) return fail(ctx, NTM_E_INVALID, "null array");
+    const size_t nq = queue_bytes(delay, B);
+    double *dx, *drho, *duo, *ddh, *dxh, *dq, *dU, *dxp, *dxn, *dy, *dz, *dua;
+    int32_t *dfl, *dit, *dws;
+    Arr arrs[] = {{x_k, &dx, n.x, kIn}, {rho, &drho, n.rho, kInOut}, {U_old, &duo, n.u, kInOut},
+                  {d_hat, &ddh, n.x, kInOut}, {x_hat, &dxh, n.x, kInOut}, {nq ? u_queue : nullptr, &dq, nq, kInOut},
+                  {U, &dU, n.u, kOut}, {x_pred, &dxp, n.xp, kOut}, {x_next, &dxn, n.x, kOut}, {y, &dy, n.x, kOut},
+                  {x_plan, &dz, n.x, kOut}, {u_applied, &dua, n.x / 2, kOut}, {exitflag, &dfl, n.i, kOut},
+                  {inner_iters, &dit, n.i, kOut}, {active_ws, &dws, n.ws, kInOut}};
+    if ((rc = stage_in(ctx, arrs))) return rc;
+    rc = ntm_mpc_step_dly_device(ctx, phys, cfg, est, delay, B, dx, drho, duo, ddh, dxh, dq, dU, dxp, dxn, dy, dz, dua,
+                                 dfl, dit, dws, ctx->stream);
+    return stage_out(ctx, rc, arrs);
+}
+
+int ntm_mpc_run_dly_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est,
+                           const ntm_delay* delay, int64_t B, int32_t k_sim, const double* x0, const double* d0,
+                           const double* xhat0, const double* uq0, double* xk, double* uk, double* Uk, double* wpred,
+                           double* dk, double* xhk, double* yk, double* uak, double* xpk, int32_t* exitflag,
+                           int32_t* inner_iters, void* stream) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B, est);
+    if (rc) return rc;
+    if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
+    const Bytes n(cfg->N, B, k_sim);
+    if ((rc = validate_dly(ctx, delay, uq0, B, true,
+                           {{x0, n.x}, {d0, n.x}, {xhat0, n.x}, {xk, n.xk}, {uk, n.uk}, {Uk, n.Uk}, {wpred, n.wp},
+                            {dk, n.xk}, {xhk, n.xk}, {yk, n.yk}, {uak, n.uk}, {xpk, n.yk}, {exitflag, n.ik},
+                            {inner_iters, n.ik}})))
+        return rc;
+    if (B == 0) return NTM_OK;
+    if (!x0) return fail(ctx, NTM_E_INVALID, "null x0");
+    const Prob pb = launch_prob(ctx, phys, cfg);
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define CALL(P_)                                                                                                   \
+    launch_sibling<P_>(ctx, k_mpc_run_dly<P_>, "k_mpc_run_dly launch", pb, B, st, pb, B, k_sim, x0, d0, xhat0,    \
+                       uq0, xk, uk, Uk, wpred, dk, xhk, yk, uak, xpk, exitflag, inner_iters, est_opt(est),         \
+                       dly_opt(delay))
+    return NTM_DISPATCH_LANES(cfg->N, CALL);
+#undef CALL
+}
+
+int ntm_mpc_run_dly(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est,
+                    const ntm_delay* delay, int64_t B, int32_t k_sim, const double* x0, const double* d0,
+                    const double* xhat0, const double* uq0, double* xk, double* uk, double* Uk, double* wpred,
+                    double* dk, double* xhk, double* yk, double* uak, double* xpk, int32_t* exitflag,
+                    int32_t* inner_iters) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B, est);
+    if (rc) return rc;
+    if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
+    const Bytes n(cfg->N, B, k_sim);
+    if ((rc = validate_dly(ctx, delay, uq0, B, true,
+                           {{x0, n.x}, {d0, n.x}, {xhat0, n.x}, {xk, n.xk}, {uk, n.uk}, {Uk, n.Uk}, {wpred, n.wp},
+                            {dk, n.xk}, {xhk, n.xk}, {yk, n.yk}, {uak, n.uk}, {xpk, n.yk}, {exitflag, n.ik},
+                            {inner_iters, n.ik}})))
+        return rc;
+    if (B == 0) return NTM_OK;
+    if (!x0) return fail(ctx, NTM_E_INVALID, "null x0");
+    const size_t nq = queue_bytes(delay, B);
+    double *dx0, *dd0, *dh0, *dq0, *dxk, *duk, *dUk, *dwp, *ddk, *dxhk, *dyk, *duak, *dxpk;
+    int32_t *dfl, *dit;
+    Arr arrs[] = {{x0, &dx0, n.x, kIn}, {d0, &dd0, n.x, kIn}, {xhat0, &dh0, n.x, kIn},
+                  {nq ? uq0 : nullptr, &dq0, nq, kIn}, {xk, &dxk, n.xk, kOut}, {uk, &duk, n.uk, kOut},
+                  {Uk, &dUk, n.Uk, kOut}, {wpred, &dwp, n.wp, kOut}, {dk, &ddk, n.xk, kOut}, {xhk, &dxhk, n.xk, kOut},
+                  {yk, &dyk, n.yk, kOut}, {uak, &duak, n.uk, kOut}, {xpk, &dxpk, n.yk, kOut},
+                  {exitflag, &dfl, n.ik, kOut}, {inner_iters, &dit, n.ik, kOut}};
+    if ((rc = stage_in(ctx, arrs))) return rc;
+    rc = ntm_mpc_run_dly_device(ctx, phys, cfg, est, delay, B, k_sim, dx0, dd0, dh0, dq0, dxk, duk, dUk, dwp, ddk, dxhk,
+                                dyk, duak, dxpk, dfl, dit, ctx->stream);
+    return stage_out(ctx, rc, arrs);
+}
+
+int ntm_mpc_run_dly_from_device(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est,
+                                const ntm_delay* delay, int64_t B, int32_t k_sim, double* x, double* rho,
+                                double* U_old, int32_t* active_ws, double* d_hat, double* x_hat, double* u_queue,
+                                double* xk, double* uk, double* Uk, double* wpred, double* dk, double* xhk, double* yk,
+                                double* uak, double* xpk, int32_t* exitflag, int32_t* inner_iters, void* stream) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B, est);
+    if (rc) return rc;
+    if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
+    const Bytes n(cfg->N, B, k_sim);
+    if ((rc = validate_dly(ctx, delay, u_queue, B, false,
+                           {{x, n.x}, {rho, n.rho}, {U_old, n.u}, {active_ws, n.ws}, {d_hat, n.x}, {x_hat, n.x},
+                            {xk, n.xk}, {uk, n.uk}, {Uk, n.Uk}, {wpred, n.wp}, {dk, n.xk}, {xhk, n.xk}, {yk, n.yk},
+                            {uak, n.uk}, {xpk, n.yk}, {exitflag, n.ik}, {inner_iters, n.ik}})))
+        return rc;
+    if (any_null({x, rho, U_old, active_ws, d_hat, x_hat})) return fail(ctx, NTM_E_INVALID, "null state array");
+    if (B == 0) return NTM_OK;
+    const Prob pb = launch_prob(ctx, phys, cfg);
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define CALL(P_)                                                                                                    \
+    launch_sibling<P_>(ctx, k_mpc_run_dly_from<P_>, "k_mpc_run_dly_from launch", pb, B, st, pb, B, k_sim, x, rho, \
+                       U_old, active_ws, d_hat, x_hat, u_queue, xk, uk, Uk, wpred, dk, xhk, yk, uak, xpk,          \
+                       exitflag, inner_iters, est_opt(est), dly_opt(delay))
+    return NTM_DISPATCH_LANES(cfg->N, CALL);
+#undef CALL
+}
+
+int ntm_mpc_run_dly_from(ntm_ctx* ctx, const ntm_physics* phys, const ntm_config* cfg, const ntm_estimator* est,
+                         const ntm_delay* delay, int64_t B, int32_t k_sim, double* x, double* rho, double* U_old,
+                         int32_t* active_ws, double* d_hat, double* x_hat, double* u_queue, double* xk, double* uk,
+                         double* Uk, double* wpred, double* dk, double* xhk, double* yk, double* uak, double* xpk,
+                         int32_t* exitflag, int32_t* inner_iters) {
+    DeviceGuard dg(ctx);
+    int rc = validate(ctx, phys, cfg, B, est);
+    if (rc) return rc;
+    if (k_sim < 0) return fail(ctx, NTM_E_INVALID, "negative k_sim");
+    const Bytes n(cfg->N, B, k_sim);
+    if ((rc = validate_dly(ctx, delay, u_queue, B, false,
+                           {{x, n.x}, {rho, n.rho}, {U_old, n.u}, {active_ws, n.ws}, {d_hat, n.x}, {x_hat, n.x},
+                            {xk, n.xk}, {uk, n.uk}, {Uk, n.Uk}, {wpred, n.wp}, {dk, n.xk}, {xhk, n.xk}, {yk, n.yk},
+                            {uak, n.uk}, {xpk, n.yk}, {exitflag, n.ik}, {inner_iters, n.ik}})))
+        return rc;
+    if (any_null({x, rho, U_old, active_ws, d_hat, x_hat})) return fail(ctx, NTM_E_INVALID, "null state array");
+    if (B == 0) return NTM_OK;
+    const size_t nq = queue_bytes(delay, B);
+    double *dx, *drho, *duo, *ddh, *dxh, *dq, *dxk, *duk, *dUk, *dwp, *ddk, *dxhk, *dyk, *duak, *dxpk;
+    int32_t *dws, *dfl, *dit;
+    Arr arrs[] = {{x, &dx, n.x, kInOut}, {rho, &drho, n.rho, kInOut}, {U_old, &duo, n.u, kInOut},
+                  {active_ws, &dws, n.ws, kInOut}, {d_hat, &ddh, n.x, kInOut}, {x_hat, &dxh, n.x, kInOut},
+                  {nq ? u_queue : nullptr, &dq, nq, kInOut}, {xk, &dxk, n.xk, kOut}, {uk, &duk, n.uk, kOut},
+                  {Uk, &dUk, n.Uk, kOut}, {wpred, &dwp, n.wp, kOut}, {dk, &ddk, n.xk, kOut}, {xhk, &dxhk, n.xk, kOut},
+                  {yk, &dyk, n.yk, kOut}, {uak, &duak, n.uk, kOut}, {xpk, &dxpk, n.yk, kOut},
+                  {exitflag, &dfl, n.ik, kOut}, {inner_iters, &dit, n.ik, kOut}};
+    if ((rc = stage_in(ctx, arrs))) return rc;
+    rc = ntm_mpc_run_dly_from_device(ctx, phys, cfg, est, delay, B, k_sim, dx, drho, duo, dws, ddh, dxh, dq, dxk, duk,
+                                     dUk, dwp, ddk, dxhk, dyk, duak, dxpk, dfl, dit, ctx->stream);
     return stage_out(ctx, rc, arrs);
 }
 

@@ -730,6 +730,219 @@ __global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_run
     NTM_STAMPS_FLUSH();
 }
 
+// Actuator dead time (ntm_mpc_step_dly / ntm_mpc_run_dly / ntm_mpc_run_dly_from): the
+// estimator kernels with the input commanded d = dl.steps steps ago reaching the plant,
+// d in [0, NTM_MAX_DELAY].  One more carried value per scenario, the queue of pending
+// inputs u_queue[d], oldest first; lane j < d of the scenario's own group holds entry j
+// (d <= 8 <= P, so it never leaves the group's first DPP row; lanes >= d hold 0).
+//   plan state z = x_hat; with dl.predict, z <- k_m's one-step map WITH d_hat (scn_coef of
+//          the workspace: C + d_hat) at (z, u_queue[j]) from rho(z), j = 0 .. d-1;
+//   controller: k_mpc_step_est's, from z; u_cmd = U[0];
+//   u_app  = d > 0 ? u_queue[0] : u_cmd; plant, measurement and estimator are
+//          k_mpc_step_est's with u_app in the place of U[0];
+//   queue  u_queue[j] <- u_queue[j+1], u_queue[d-1] <- u_cmd.
+// With d = 0 no lane holds an entry, z is x_hat and u_app is U[0]: the estimator kernels'
+// steps, bit for bit.
+struct DlyOpt {
+    int steps, predict;
+};
+// scenario s's queue into its lanes (qv null: zeros, power off until the first command arrives)
+__device__ __forceinline__ double dly_load(const double* qv, int64_t s, int d, int l) {
+    return (qv && l < d) ? qv[s * d + l] : 0.0;
+}
+// One prediction step.  Its inputs pass through model_step's empty asm, for model_step's
+// reason: sub-expressions shared with the plant step or the model's map would change how
+// those are fused, and d = 0 would no longer be the estimator kernels' step bit for bit
+__device__ __forceinline__ void dly_predict(const Prob& pb, const Coef& kd, double& z0, double& z1, double u) {
+    double a0 = z0, a1 = z1;
+    asm volatile("" : "+v"(a0), "+v"(a1), "+v"(u));
+    plant_step<false>(pb, kd, a0, a1, u, z0, z1);
+}
+// the plan state: x_hat carried over the d inputs already under way
+template <int P>
+__device__ __forceinline__ void dly_plan(const Prob& pb, const WSObs& w, const DlyOpt& dl, double q, double& z0,
+                                         double& z1) {
+    if (!dl.predict) return;
+    const Coef kd = scn_coef(pb, w);
+    for (int j = 0; j < dl.steps; ++j) dly_predict(pb, kd, z0, z1, gbcast<P>(q, j));
+}
+// the input that reaches the plant now
+template <int P>
+__device__ __forceinline__ double dly_applied(const DlyOpt& dl, double q, double u_cmd) {
+    const double head = gbcast<P>(q, 0);
+    return dl.steps > 0 ? head : u_cmd;
+}
+// Entry j takes entry j + 1's value, the last one the new command.  row_shl:1 moves every
+// lane's value one lane down inside its row of 16; groups start at multiples of 16 and
+// d <= 8, so what lanes 0 .. d-2 receive comes from their own group
+__device__ __forceinline__ double dly_shift(const DlyOpt& dl, double q, double u_cmd, int l) {
+    static_assert(NTM_MAX_DELAY < 16, "the queue must fit one DPP row");
+    const double up = dpp_d<0x101>(q);
+    return l + 1 < dl.steps ? up : (l + 1 == dl.steps ? u_cmd : 0.0);
+}
+
+// NTM_RUN_EST_LOOP with the dead time: also on the kernel's dl, the queue q and the
+// histories uak (applied input) and xpk (plan state); uk stays the commanded U[0]
+#define NTM_RUN_DLY_LOOP                                                                                              \
+    const int64_t xs = s * 2 * (int64_t)(k_sim + 1);                                                                  \
+    if (xk && l == 0) { xk[xs] = x0; xk[xs + 1] = x1; }                                                               \
+    if (dk && l == 0) { dk[xs] = d0; dk[xs + 1] = d1; }                                                               \
+    if (xhk && l == 0) { xhk[xs] = h0; xhk[xs + 1] = h1; }                                                            \
+    for (int kk = 0; kk < k_sim; ++kk) {                                                                              \
+        int its;                                                                                                      \
+        double z0 = h0, z1 = h1;                                                                                      \
+        dly_plan<P>(pb, w, dl, q, z0, z1);                                                                            \
+        int flag = mpc_step_dev<P>(pb, w, z0, z1, l, &its, B, s);                                                     \
+        if (Uk && l < N) Uk[(s * k_sim + kk) * N + l] = w.U()[l];                                                     \
+        if (wpred) for (int i = l; i <= N; i += P) wpred[(s * k_sim + kk) * (N + 1) + i] = w.xp()[2 * i];             \
+        const double u0 = w.U()[0];                                                                                   \
+        const double ua = dly_applied<P>(dl, q, u0);                                                                  \
+        double n0, n1, m0, m1;                                                                                        \
+        plant_step<true>(pb, kp, x0, x1, ua, n0, n1, gid, pb.g.k0 + kk);                                              \
+        model_step(pb, km, h0, h1, ua, m0, m1);                                                                       \
+        const double y0 = est_measure(pb, eo.sy[0], n0, gid, pb.g.k0 + kk, 2);                                        \
+        const double y1 = est_measure(pb, eo.sy[1], n1, gid, pb.g.k0 + kk, 3);                                        \
+        est_update(eo.gain[0], eo.kappa[0], y0, m0, d0, h0);                                                          \
+        est_update(eo.gain[1], eo.kappa[1], y1, m1, d1, h1);                                                          \
+        q = dly_shift(dl, q, u0, l);                                                                                  \
+        if (l == 0) {                                                                                                 \
+            if (uk) uk[s * k_sim + kk] = u0;                                                                          \
+            if (uak) uak[s * k_sim + kk] = ua;                                                                        \
+            if (xpk) { xpk[(s * k_sim + kk) * 2] = z0; xpk[(s * k_sim + kk) * 2 + 1] = z1; }                          \
+            if (exitflag) exitflag[s * k_sim + kk] = flag;                                                            \
+            if (inner_iters) inner_iters[s * k_sim + kk] = its;                                                       \
+            if (xk) { xk[xs + 2 * kk + 2] = n0; xk[xs + 2 * kk + 3] = n1; }                                           \
+            if (dk) { dk[xs + 2 * kk + 2] = d0; dk[xs + 2 * kk + 3] = d1; }                                           \
+            if (xhk) { xhk[xs + 2 * kk + 2] = h0; xhk[xs + 2 * kk + 3] = h1; }                                        \
+            if (yk) { yk[(s * k_sim + kk) * 2] = y0; yk[(s * k_sim + kk) * 2 + 1] = y1; }                             \
+        }                                                                                                             \
+        x0 = n0;                                                                                                      \
+        x1 = n1;                                                                                                      \
+        NTM_WSYNC();                                                                                                  \
+        obs_model(w, km, d0, d1);                                                                                     \
+    }
+
+// k_mpc_step_est with the dead time: u_queue (d per scenario, in/out; not read when
+// d == 0), x_plan (2 per scenario, may be null): the z the plan was made from, u_applied
+// (one per scenario, may be null)
+template <int P>
+__global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_step_dly(
+    Prob pb, int64_t B, const double* __restrict__ x_k, double* __restrict__ rho, double* __restrict__ U_old,
+    double* __restrict__ U, double* __restrict__ x_pred, double* __restrict__ x_next, int32_t* __restrict__ exitflag,
+    int32_t* __restrict__ inner_iters, int32_t* __restrict__ active_ws, double* __restrict__ d_hat,
+    double* __restrict__ x_hat, double* __restrict__ y, EstOpt eo, DlyOpt dl, double* __restrict__ u_queue,
+    double* __restrict__ x_plan, double* __restrict__ u_applied) {
+    const auto [g, l, s] = scn_lanes<P>();
+    const int N = pb.N;
+    if (s >= B) return;
+    WSObs w = ws_carve_obs(scn_lds<P, 0, false>(N, g, l), N);
+    const double x0 = x_k[2 * s], x1 = x_k[2 * s + 1];
+    const double h0 = x_hat[2 * s], h1 = x_hat[2 * s + 1];
+    double d0 = d_hat[2 * s], d1 = d_hat[2 * s + 1];
+    double q = dly_load(u_queue, s, dl.steps, l);
+    const int64_t gid = pb.g.first_id + s;
+    const Coef kp = plant_coef(pb, gid);
+    const Coef km = eo.nominal ? pb.k : kp;
+    obs_model(w, km, d0, d1);
+    start_from_state<P, false>(pb, w, B, s, rho, U_old, active_ws, l);
+    int its;
+    double z0 = h0, z1 = h1;
+    dly_plan<P>(pb, w, dl, q, z0, z1);
+    int flag = mpc_step_dev<P>(pb, w, z0, z1, l, &its, B, s);
+    store_record<P>(rho + s * (3 * N), w.rho(), 3 * N, l);
+    store_record<P>(U_old + s * N, w.Uold(), N, l);
+    store_record<P>(U + s * N, w.U(), N, l);
+    store_record<P>(x_pred + s * (2 * (N + 1)), w.xp(), 2 * (N + 1), l);
+    const double u0 = w.U()[0];
+    const double ua = dly_applied<P>(dl, q, u0);
+    double n0, n1, m0, m1, e0, e1;
+    plant_step<true>(pb, kp, x0, x1, ua, n0, n1, gid, pb.g.k0);
+    model_step(pb, km, h0, h1, ua, m0, m1);
+    const double y0 = est_measure(pb, eo.sy[0], n0, gid, pb.g.k0, 2);
+    const double y1 = est_measure(pb, eo.sy[1], n1, gid, pb.g.k0, 3);
+    est_update(eo.gain[0], eo.kappa[0], y0, m0, d0, e0);
+    est_update(eo.gain[1], eo.kappa[1], y1, m1, d1, e1);
+    q = dly_shift(dl, q, u0, l);
+    if (l < dl.steps) u_queue[s * dl.steps + l] = q;
+    if (l < 2) {
+        x_next[2 * s + l] = l ? n1 : n0;
+        d_hat[2 * s + l] = l ? d1 : d0;
+        x_hat[2 * s + l] = l ? e1 : e0;
+        if (y) y[2 * s + l] = l ? y1 : y0;
+        if (x_plan) x_plan[2 * s + l] = l ? z1 : z0;
+    }
+    if (l == 0) {
+        exitflag[s] = flag;
+        inner_iters[s] = its;
+        if (u_applied) u_applied[s] = ua;
+    }
+    if (active_ws)
+        for (int e = l; e < 2 * (N + 1); e += P) active_ws[s * (2 * (N + 1)) + e] = w.cand()[e];
+    NTM_STAMPS_FLUSH();
+}
+
+// k_mpc_run_est with the dead time, the queue carried in the lanes for the whole loop:
+// uq0 (d per scenario, null: zeros), uak (k_sim per scenario, may be null): the applied
+// input of step k, xpk (2 k_sim per scenario, may be null): the plan state of step k
+template <int P>
+__global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_run_dly(
+    Prob pb, int64_t B, int k_sim, const double* __restrict__ x0v, const double* __restrict__ d0v,
+    const double* __restrict__ h0v, const double* __restrict__ uq0, double* xk, double* uk, double* Uk, double* wpred,
+    double* dk, double* xhk, double* yk, double* uak, double* xpk, int32_t* exitflag, int32_t* inner_iters, EstOpt eo,
+    DlyOpt dl) {
+    const auto [g, l, s] = scn_lanes<P>();
+    const int N = pb.N;
+    if (s >= B) return;
+    WSObs w = ws_carve_obs(scn_lds<P, 0, false>(N, g, l), N);
+    double x0 = x0v[2 * s], x1 = x0v[2 * s + 1];
+    double h0 = h0v ? h0v[2 * s] : x0, h1 = h0v ? h0v[2 * s + 1] : x1;
+    double d0 = d0v ? d0v[2 * s] : 0.0, d1 = d0v ? d0v[2 * s + 1] : 0.0;
+    double q = dly_load(uq0, s, dl.steps, l);
+    const int64_t gid = pb.g.first_id + s;
+    const Coef kp = plant_coef(pb, gid);
+    const Coef km = eo.nominal ? pb.k : kp;
+    obs_model(w, km, d0, d1);
+    if (l < 2) w.cand()[l * (N + 1) + N] = -1;
+    NTM_START_FROM_X0(km, h0, h1)
+    NTM_RUN_DLY_LOOP
+    NTM_STAMPS_FLUSH();
+}
+
+// k_mpc_run_est_from with the dead time: u_queue (d per scenario) in/out with the rest of
+// the carried state, so a loop split into chunks carries the inputs still under way
+template <int P>
+__global__ __launch_bounds__(64, NTM_WAVES_PER_EU_P(P, 0, false)) void k_mpc_run_dly_from(
+    Prob pb, int64_t B, int k_sim, double* __restrict__ x, double* __restrict__ rho, double* __restrict__ U_old,
+    int32_t* __restrict__ active_ws, double* __restrict__ d_hat, double* __restrict__ x_hat,
+    double* __restrict__ u_queue, double* xk, double* uk, double* Uk, double* wpred, double* dk, double* xhk,
+    double* yk, double* uak, double* xpk, int32_t* exitflag, int32_t* inner_iters, EstOpt eo, DlyOpt dl) {
+    const auto [g, l, s] = scn_lanes<P>();
+    const int N = pb.N;
+    if (s >= B) return;
+    WSObs w = ws_carve_obs(scn_lds<P, 0, false>(N, g, l), N);
+    double x0 = x[2 * s], x1 = x[2 * s + 1];
+    double h0 = x_hat[2 * s], h1 = x_hat[2 * s + 1];
+    double d0 = d_hat[2 * s], d1 = d_hat[2 * s + 1];
+    double q = dly_load(u_queue, s, dl.steps, l);
+    const int64_t gid = pb.g.first_id + s;
+    const Coef kp = plant_coef(pb, gid);
+    const Coef km = eo.nominal ? pb.k : kp;
+    obs_model(w, km, d0, d1);
+    start_from_state<P, true>(pb, w, B, s, rho, U_old, active_ws, l);
+    NTM_RUN_DLY_LOOP
+    if (k_sim > 0) {
+        store_record<P>(rho + s * (3 * N), w.rho(), 3 * N, l);
+        store_record<P>(U_old + s * N, w.Uold(), N, l);
+        for (int e = l; e < 2 * (N + 1); e += P) active_ws[s * (2 * (N + 1)) + e] = w.cand()[e];
+        if (l < 2) {
+            x[2 * s + l] = l ? x1 : x0;
+            d_hat[2 * s + l] = l ? d1 : d0;
+            x_hat[2 * s + l] = l ? h1 : h0;
+        }
+        if (l < dl.steps) u_queue[s * dl.steps + l] = q;
+    }
+    NTM_STAMPS_FLUSH();
+}
 
 }  // namespace
 

@@ -59,6 +59,13 @@ class NtmEstimator(C.Structure):
                 ("kappa", C.c_double * 2), ("sigma_y", C.c_double * 2)]
 
 
+class NtmDelay(C.Structure):
+    """ntm_delay — actuator dead time and the delay-compensating plan (include/ntm_mpc.h)."""
+    _fields_ = [("steps", C.c_int32), ("predict", C.c_int32)]
+
+
+MAX_DELAY = 8            # include/ntm_mpc.h NTM_MAX_DELAY
+
 _DP = C.POINTER(C.c_double)
 _IP = C.POINTER(C.c_int32)
 _V = C.c_void_p
@@ -66,6 +73,7 @@ _PHY = C.POINTER(NtmPhysics)
 _CFG = C.POINTER(NtmConfig)
 _OBS = C.POINTER(NtmObserver)
 _EST = C.POINTER(NtmEstimator)
+_DLY = C.POINTER(NtmDelay)
 
 # name -> (restype, argtypes)
 EXPORTS = {
@@ -132,6 +140,13 @@ EXPORTS = {
                                        _DP, _DP, _DP, _DP, _DP, _DP, _DP, _IP, _IP]),
     "ntm_mpc_run_est_from_device": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, C.c_int64, C.c_int32, _V, _V, _V, _V, _V,
                                               _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+    "ntm_mpc_step_dly": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, _DLY, C.c_int64] + [_DP] * 12 + [_IP] * 3),
+    "ntm_mpc_step_dly_device": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, _DLY, C.c_int64] + [_V] * 16),
+    "ntm_mpc_run_dly": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, _DLY, C.c_int64, C.c_int32] + [_DP] * 13 + [_IP] * 2),
+    "ntm_mpc_run_dly_device": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, _DLY, C.c_int64, C.c_int32] + [_V] * 16),
+    "ntm_mpc_run_dly_from": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, _DLY, C.c_int64, C.c_int32] + [_DP] * 3 + [_IP]
+                             + [_DP] * 12 + [_IP] * 2),
+    "ntm_mpc_run_dly_from_device": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, _DLY, C.c_int64, C.c_int32] + [_V] * 19),
     "ntm_qp_kkt_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V]),
     "ntm_mpc_kkt_device": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, _V, _V, _V, _V, _V, _V]),
     "ntm_scenarios_x0": (None, [C.c_uint64, C.c_int64, C.c_int64, _DP]),
@@ -143,6 +158,9 @@ EXPORTS = {
 # additive entry points an older build of the library (one loaded through NTM_MPC_LIB, an
 # A/B against a parent commit) may lack: bound when present, see has_run_from()
 OPTIONAL = ("ntm_mpc_run_from", "ntm_mpc_run_from_device", "ntm_mpc_run_est_from", "ntm_mpc_run_est_from_device")
+# the actuator dead time's (NTM_MPC_HAS_INPUT_DELAY), a set of its own: see has_input_delay()
+OPTIONAL_DELAY = ("ntm_mpc_step_dly", "ntm_mpc_step_dly_device", "ntm_mpc_run_dly", "ntm_mpc_run_dly_device",
+                  "ntm_mpc_run_dly_from", "ntm_mpc_run_dly_from_device")
 
 _lib = None
 
@@ -161,7 +179,7 @@ def load(path: Path | str | None = None):
     except OSError as e:  # pragma: no cover - depends on the loader
         raise NtmLibraryError(f"cannot load {p}: {e}") from e
     for name, (res, args) in EXPORTS.items():
-        if name in OPTIONAL and not hasattr(lib, name):
+        if name in OPTIONAL + OPTIONAL_DELAY and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         fn.restype = res
@@ -178,6 +196,13 @@ def has_run_from(lib=None) -> bool:
     header): ntm_mpc_run_from* / ntm_mpc_run_est_from*, detected by symbol."""
     lib = lib or load()
     return all(hasattr(lib, n) for n in OPTIONAL)
+
+
+def has_input_delay(lib=None) -> bool:
+    """The loaded library has the actuator dead time (NTM_MPC_HAS_INPUT_DELAY in the
+    header): ntm_mpc_step_dly* / ntm_mpc_run_dly* / ntm_mpc_run_dly_from*, detected by symbol."""
+    lib = lib or load()
+    return all(hasattr(lib, n) for n in OPTIONAL_DELAY)
 
 
 def default_physics() -> NtmPhysics:

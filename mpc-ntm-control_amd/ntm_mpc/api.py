@@ -159,6 +159,20 @@ class Estimator:
                               d2(*_pair(self.sigma_y)))
 
 
+@dataclass
+class Delay:
+    """ntm_delay: actuator dead time.  The plant applies the input commanded ``steps``
+    sampling periods ago (0 .. MAX_DELAY = 8); the pending inputs travel in a queue
+    ``u_queue`` (steps, B), oldest first.  ``predict``: the controller plans from the
+    state its model predicts for the moment the command arrives (x_hat carried over the
+    queued inputs); False plans from x_hat, a controller that does not know the delay."""
+    steps: int = 0
+    predict: bool = True
+
+    def to_c(self) -> L.NtmDelay:
+        return L.NtmDelay(int(self.steps), 1 if self.predict else 0)
+
+
 def meas_sample(gen: ScenarioGen, B: int, k: int = 0) -> np.ndarray:
     """(B, 2) host-side unit samples of the measurement noise for scenarios
     gen.first_id + s at time index k: the generator's normal channels 2 (w) and 3
@@ -849,15 +863,19 @@ class NtmMpc:
         return out
 
     # ------------------------------------------------------------ resumable closed loops
-    def _run_out(self, k_sim, N, Bn, est=False, host=False):
+    def _run_out(self, k_sim, N, Bn, est=False, host=False, dly=False):
         if not L.has_run_from(self.lib):
             raise NtmLibraryError("this build of the library has no ntm_mpc_run_from (NTM_MPC_HAS_RUN_FROM)")
+        if dly and not L.has_input_delay(self.lib):
+            raise NtmLibraryError("this build of the library has no ntm_mpc_run_dly (NTM_MPC_HAS_INPUT_DELAY)")
         mk = _host_empty if host else self._empty
         i32 = np.int32 if host else torch.int32
         out = {"xk": mk(2 * (k_sim + 1), Bn), "uk": mk(k_sim, Bn), "Uk": mk(N * k_sim, Bn),
                "wpred": mk((N + 1) * k_sim, Bn)}
         if est:
             out.update(dk=mk(2 * (k_sim + 1), Bn), xhk=mk(2 * (k_sim + 1), Bn), yk=mk(2 * k_sim, Bn))
+        if dly:
+            out.update(uak=mk(k_sim, Bn), xpk=mk(2 * k_sim, Bn))
         out.update(exitflag=mk(k_sim, Bn, dtype=i32), inner_iters=mk(k_sim, Bn, dtype=i32))
         return out
 
@@ -944,6 +962,180 @@ class NtmMpc:
                                            *[hp(v) for v in out.values()])
         self._raise(rc, "ntm_mpc_run_est_from")
         for dst, (src, staged) in zip((x, rho, U_old, active_ws, d_hat, x_hat), state):
+            if staged:
+                dst[...] = src
+        return out
+
+    # ------------------------------------------------------------ actuator dead time
+    @staticmethod
+    def _queue_arg(arg, u_queue, dly: Delay, Bn, name="u_queue", **kw):
+        """The queue argument (steps, B) as (array, staged?); None where there is none."""
+        if u_queue is None:
+            return None, False
+        return arg(u_queue, (int(dly.steps), Bn), name=name, **kw)
+
+    def step_dly(self, x_k: torch.Tensor, rho: torch.Tensor, U_old: torch.Tensor, d_hat: torch.Tensor,
+                 x_hat: torch.Tensor, u_queue: torch.Tensor | None, est: Estimator, dly: Delay,
+                 cfg: Config | None = None, active_ws: torch.Tensor | None = None):
+        """step_est() with an actuator dead time (ntm_mpc_step_dly_device): the plant applies
+        ``u_queue[0]`` (the input commanded dly.steps steps ago) and the controller plans from
+        ``x_plan``, x_hat carried over the queued inputs by its model (dly.predict; else
+        x_hat).  ``u_queue`` (steps, B) is shifted in place and takes the new command
+        ``U[0]`` at its end (None is allowed when steps == 0).  Returns step_est()'s dict
+        plus ``x_plan`` (2, B), ``u_applied`` (B,) and ``u_queue``.  With steps == 0 it is
+        step_est() bit for bit."""
+        if not L.has_input_delay(self.lib):
+            raise NtmLibraryError("this build of the library has no ntm_mpc_step_dly (NTM_MPC_HAS_INPUT_DELAY)")
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x_k.shape[1]
+        xk, _ = _dev_arg(x_k, (2, Bn), name="x_k")
+        rh, rho_st = _dev_arg(rho, (3 * N, Bn), name="rho")
+        uo, uo_st = _dev_arg(U_old, (N, Bn), name="U_old")
+        dh, dh_st = _dev_arg(d_hat, (2, Bn), name="d_hat")
+        xh, xh_st = _dev_arg(x_hat, (2, Bn), name="x_hat")
+        uq, uq_st = self._queue_arg(_dev_arg, u_queue, dly, Bn)
+        ws, ws_st = (None, False) if active_ws is None else _dev_arg(active_ws, (2 * (N + 1), Bn), torch.int32,
+                                                                     "active_ws")
+        out = {"U": self._empty(N, Bn), "x_pred": self._empty(2 * (N + 1), Bn), "x_next": self._empty(2, Bn),
+               "y": self._empty(2, Bn), "x_plan": self._empty(2, Bn), "u_applied": self._empty(Bn),
+               "exitflag": self._empty(Bn, dtype=torch.int32), "inner_iters": self._empty(Bn, dtype=torch.int32)}
+        rc = self.lib.ntm_mpc_step_dly_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
+                                              C.byref(est.to_c()), C.byref(dly.to_c()), Bn, _ptr(xk), _ptr(rh),
+                                              _ptr(uo), _ptr(dh), _ptr(xh), _ptr(uq), _ptr(out["U"]),
+                                              _ptr(out["x_pred"]), _ptr(out["x_next"]), _ptr(out["y"]),
+                                              _ptr(out["x_plan"]), _ptr(out["u_applied"]), _ptr(out["exitflag"]),
+                                              _ptr(out["inner_iters"]), _ptr(ws), self._stream())
+        self._raise(rc, "ntm_mpc_step_dly_device")
+        for staged, dst, src in ((rho_st, rho, rh), (uo_st, U_old, uo), (dh_st, d_hat, dh), (xh_st, x_hat, xh),
+                                 (uq_st, u_queue, uq), (ws_st, active_ws, ws)):
+            if staged:
+                dst.copy_(src)
+        out["d_hat"], out["x_hat"], out["u_queue"] = d_hat, x_hat, u_queue
+        return out
+
+    def step_dly_host(self, x_k: np.ndarray, rho: np.ndarray, U_old: np.ndarray, d_hat: np.ndarray,
+                      x_hat: np.ndarray, u_queue: np.ndarray | None, est: Estimator, dly: Delay,
+                      cfg: Config | None = None, active_ws: np.ndarray | None = None):
+        """ntm_mpc_step_dly with host arrays (the MEX path): ``d_hat``, ``x_hat`` and
+        ``u_queue`` are updated in place and returned in the dict."""
+        if not L.has_input_delay(self.lib):
+            raise NtmLibraryError("this build of the library has no ntm_mpc_step_dly (NTM_MPC_HAS_INPUT_DELAY)")
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x_k.shape[1]
+        xk, _ = _host_arg(x_k, (2, Bn), name="x_k")
+        rh, rho_st = _host_arg(rho, (3 * N, Bn), name="rho")
+        uo, uo_st = _host_arg(U_old, (N, Bn), name="U_old")
+        dh, dh_st = _host_arg(d_hat, (2, Bn), name="d_hat")
+        xh, xh_st = _host_arg(x_hat, (2, Bn), name="x_hat")
+        uq, uq_st = self._queue_arg(_host_arg, u_queue, dly, Bn)
+        ws, ws_st = (None, False) if active_ws is None else _host_arg(active_ws, (2 * (N + 1), Bn), np.int32,
+                                                                      "active_ws")
+        out = {"U": _host_empty(N, Bn), "x_pred": _host_empty(2 * (N + 1), Bn), "x_next": _host_empty(2, Bn),
+               "y": _host_empty(2, Bn), "x_plan": _host_empty(2, Bn), "u_applied": np.empty(Bn),
+               "exitflag": np.empty(Bn, np.int32), "inner_iters": np.empty(Bn, np.int32)}
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))          # noqa: E731
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))           # noqa: E731
+        rc = self.lib.ntm_mpc_step_dly(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
+                                       C.byref(est.to_c()), C.byref(dly.to_c()), Bn, dp(xk), dp(rh), dp(uo), dp(dh),
+                                       dp(xh), None if uq is None else dp(uq), dp(out["U"]), dp(out["x_pred"]),
+                                       dp(out["x_next"]), dp(out["y"]), dp(out["x_plan"]), dp(out["u_applied"]),
+                                       ip(out["exitflag"]), ip(out["inner_iters"]), None if ws is None else ip(ws))
+        self._raise(rc, "ntm_mpc_step_dly")
+        for staged, dst, src in ((rho_st, rho, rh), (uo_st, U_old, uo), (dh_st, d_hat, dh), (xh_st, x_hat, xh),
+                                 (uq_st, u_queue, uq), (ws_st, active_ws, ws)):
+            if staged:
+                dst[...] = src
+        out["d_hat"], out["x_hat"], out["u_queue"] = d_hat, x_hat, u_queue
+        return out
+
+    def run_dly(self, x0: torch.Tensor, est: Estimator, dly: Delay, k_sim: int = 20, cfg: Config | None = None,
+                d0: torch.Tensor | None = None, xhat0: torch.Tensor | None = None, uq0: torch.Tensor | None = None):
+        """run_est() with an actuator dead time (ntm_mpc_run_dly_device): the queue of
+        pending inputs stays on chip with x, x_hat and d_hat.  ``uq0`` (steps, B) is the
+        initial queue (None: zeros, power off until the first command arrives).  Returns
+        run_est()'s dict plus ``uak`` (k_sim, B), the applied input (``uk`` stays the
+        commanded U[0]: uak[k + steps] == uk[k]), and ``xpk`` (2 k_sim, B), the plan state."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x0.shape[1]
+        x0, _ = _dev_arg(x0, (2, Bn), name="x0")
+        if d0 is not None:
+            d0, _ = _dev_arg(d0, (2, Bn), name="d0")
+        if xhat0 is not None:
+            xhat0, _ = _dev_arg(xhat0, (2, Bn), name="xhat0")
+        uq0, _ = self._queue_arg(_dev_arg, uq0, dly, Bn, name="uq0")
+        out = self._run_out(k_sim, N, Bn, est=True, dly=True)
+        rc = self.lib.ntm_mpc_run_dly_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
+                                             C.byref(est.to_c()), C.byref(dly.to_c()), Bn, k_sim, _ptr(x0), _ptr(d0),
+                                             _ptr(xhat0), _ptr(uq0), *[_ptr(v) for v in out.values()],
+                                             self._stream())
+        self._raise(rc, "ntm_mpc_run_dly_device")
+        return out
+
+    def run_dly_host(self, x0: np.ndarray, est: Estimator, dly: Delay, k_sim: int = 20, cfg: Config | None = None,
+                     d0: np.ndarray | None = None, xhat0: np.ndarray | None = None, uq0: np.ndarray | None = None):
+        """ntm_mpc_run_dly with host arrays: run_est_host with the dead time, plus ``uak``
+        and ``xpk``."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x0.shape[1]
+        x0, _ = _host_arg(x0, (2, Bn), name="x0")
+        if d0 is not None:
+            d0, _ = _host_arg(d0, (2, Bn), name="d0")
+        if xhat0 is not None:
+            xhat0, _ = _host_arg(xhat0, (2, Bn), name="xhat0")
+        uq0, _ = self._queue_arg(_host_arg, uq0, dly, Bn, name="uq0")
+        out = self._run_out(k_sim, N, Bn, est=True, host=True, dly=True)
+        hp = lambda a: None if a is None else a.ctypes.data_as(                                    # noqa: E731
+            C.POINTER(C.c_int32 if a.dtype == np.int32 else C.c_double))
+        rc = self.lib.ntm_mpc_run_dly(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
+                                      C.byref(est.to_c()), C.byref(dly.to_c()), Bn, k_sim, hp(x0), hp(d0), hp(xhat0),
+                                      hp(uq0), *[hp(v) for v in out.values()])
+        self._raise(rc, "ntm_mpc_run_dly")
+        return out
+
+    def run_dly_from(self, x: torch.Tensor, rho: torch.Tensor, U_old: torch.Tensor, active_ws: torch.Tensor,
+                     d_hat: torch.Tensor, x_hat: torch.Tensor, u_queue: torch.Tensor | None, est: Estimator,
+                     dly: Delay, k_sim: int = 20, cfg: Config | None = None):
+        """run_dly() from a carried state (ntm_mpc_run_dly_from_device): run_est_from() with
+        the queue ``u_queue`` (steps, B) carried too, all updated in place; one call of k
+        steps and any split of them give the same bits.  ``dly.steps`` must not change
+        between the chunks of one loop.  Returns run_dly()'s dict."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x.shape[1]
+        state = [_dev_arg(x, (2, Bn), name="x"), _dev_arg(rho, (3 * N, Bn), name="rho"),
+                 _dev_arg(U_old, (N, Bn), name="U_old"),
+                 _dev_arg(active_ws, (2 * (N + 1), Bn), torch.int32, "active_ws"),
+                 _dev_arg(d_hat, (2, Bn), name="d_hat"), _dev_arg(x_hat, (2, Bn), name="x_hat"),
+                 self._queue_arg(_dev_arg, u_queue, dly, Bn)]
+        out = self._run_out(k_sim, N, Bn, est=True, dly=True)
+        rc = self.lib.ntm_mpc_run_dly_from_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
+                                                  C.byref(est.to_c()), C.byref(dly.to_c()), Bn, k_sim,
+                                                  *[_ptr(a) for a, _ in state], *[_ptr(v) for v in out.values()],
+                                                  self._stream())
+        self._raise(rc, "ntm_mpc_run_dly_from_device")
+        for dst, (src, staged) in zip((x, rho, U_old, active_ws, d_hat, x_hat, u_queue), state):
+            if staged:
+                dst.copy_(src)
+        return out
+
+    def run_dly_from_host(self, x: np.ndarray, rho: np.ndarray, U_old: np.ndarray, active_ws: np.ndarray,
+                          d_hat: np.ndarray, x_hat: np.ndarray, u_queue: np.ndarray | None, est: Estimator,
+                          dly: Delay, k_sim: int = 20, cfg: Config | None = None):
+        """ntm_mpc_run_dly_from with host arrays; the state arrays are updated in place."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x.shape[1]
+        state = [_host_arg(x, (2, Bn), name="x"), _host_arg(rho, (3 * N, Bn), name="rho"),
+                 _host_arg(U_old, (N, Bn), name="U_old"),
+                 _host_arg(active_ws, (2 * (N + 1), Bn), np.int32, "active_ws"),
+                 _host_arg(d_hat, (2, Bn), name="d_hat"), _host_arg(x_hat, (2, Bn), name="x_hat"),
+                 self._queue_arg(_host_arg, u_queue, dly, Bn)]
+        out = self._run_out(k_sim, N, Bn, est=True, host=True, dly=True)
+        hp = lambda a: None if a is None else a.ctypes.data_as(                                    # noqa: E731
+            C.POINTER(C.c_int32 if a.dtype == np.int32 else C.c_double))
+        rc = self.lib.ntm_mpc_run_dly_from(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
+                                           C.byref(est.to_c()), C.byref(dly.to_c()), Bn, k_sim,
+                                           *[hp(a) for a, _ in state], *[hp(v) for v in out.values()])
+        self._raise(rc, "ntm_mpc_run_dly_from")
+        for dst, (src, staged) in zip((x, rho, U_old, active_ws, d_hat, x_hat, u_queue), state):
             if staged:
                 dst[...] = src
         return out
