@@ -170,6 +170,101 @@ static const double* in_matrix(const mxArray* a, size_t rows, size_t cols, const
     return mxGetDoubles(a);
 }
 
+#define D(a) mxGetDoubles(a)
+#define I(a) mxGetInt32s(a)
+
+/* an optional 2-by-B input: omitted or [] gives NULL */
+static const double* opt_matrix(int nrhs, const mxArray* prhs[], int i, size_t B, const char* name) {
+    if (nrhs <= i || (mxIsDouble(prhs[i]) && mxGetNumberOfElements(prhs[i]) == 0)) return NULL;
+    return in_matrix(prhs[i], 2, B, name);
+}
+
+/* the int32 2(N+1)-by-B warm-start workspace (the '*_from' commands require one) */
+static void in_ws(const mxArray* w, size_t N, size_t B) {
+    if (!mxIsInt32(w) || mxGetM(w) != 2 * (N + 1) || mxGetN(w) != B)
+        mexErrMsgIdAndTxt("ntm:arg", "ws must be an int32 %d-by-%d array", (int)(2 * (N + 1)), (int)B);
+}
+
+/* the workspace as an output (value semantics): a copy of the caller's, or, where the
+ * command was given none (w == NULL), an empty one, -1 everywhere */
+static mxArray* dup_ws(const mxArray* w, size_t N, size_t B) {
+    if (w) {
+        in_ws(w, N, B);
+        return mxDuplicateArray(w);
+    }
+    mxArray* ws = mxCreateNumericMatrix(2 * (N + 1), B, mxINT32_CLASS, mxREAL);
+    for (size_t i = 0; i < B * 2 * (N + 1); ++i) I(ws)[i] = -1;
+    return ws;
+}
+
+/* k_sim of the 'run*' commands (>= 1) and of the '*_from' commands (a scalar >= 0) */
+static int in_ksim_run(const mxArray* a) {
+    const int k = (int)mxGetScalar(a);
+    if (k < 1) mexErrMsgIdAndTxt("ntm:arg", "k_sim must be >= 1");
+    return k;
+}
+
+static int in_ksim(const mxArray* a) {
+    if (!mxIsDouble(a) || mxGetNumberOfElements(a) != 1 || !(mxGetScalar(a) >= 0))
+        mexErrMsgIdAndTxt("ntm:arg", "k_sim must be a scalar >= 0");
+    return (int)mxGetScalar(a);
+}
+
+/* The 'step*' commands' own outputs: U N-by-B, x_pred 2(N+1)-by-B, x_next 2-by-B, exitflag
+ * and iters 1-by-B are outputs 1 to 5 of each; y 2-by-B ('step_est', 'step_dly'), x_plan
+ * 2-by-B and u_app 1-by-B ('step_dly') follow the returned state, where each command says. */
+typedef struct {
+    mxArray *U, *xp, *xn, *fl, *it, *y, *z, *ua;
+} step_out;
+
+static step_out new_step_out(size_t N, size_t B, int est, int dly) {
+    step_out o = {mxCreateDoubleMatrix(N, B, mxREAL), mxCreateDoubleMatrix(2 * (N + 1), B, mxREAL),
+                  mxCreateDoubleMatrix(2, B, mxREAL), mxCreateNumericMatrix(1, B, mxINT32_CLASS, mxREAL),
+                  mxCreateNumericMatrix(1, B, mxINT32_CLASS, mxREAL), NULL, NULL, NULL};
+    if (est) o.y = mxCreateDoubleMatrix(2, B, mxREAL);
+    if (dly) {
+        o.z = mxCreateDoubleMatrix(2, B, mxREAL);
+        o.ua = mxCreateDoubleMatrix(1, B, mxREAL);
+    }
+    return o;
+}
+
+/* The closed-loop histories of the 'run*' commands for k steps.  The fields stand in the
+ * MEX output order, which every 'run*' command shares: xk, uk, Uk, wpred, exitflag, iters
+ * (outputs 1 to 6), then dk (observer), xhk and yk (estimator), uak and xpk (dead time); a
+ * '*_from' command appends its carried state.  It is not the C-ABI's order: there exitflag
+ * and iters come last, after the extras. */
+typedef struct {
+    mxArray *xk, *uk, *Uk, *wp, *fl, *it, *dk, *xhk, *yk, *uak, *xpk;
+} loop_out;
+
+static loop_out new_loop_out(int k_sim, size_t N, size_t B, int obs, int est, int dly) {
+    const size_t k = (size_t)k_sim;
+    loop_out o = {mxCreateDoubleMatrix(2 * (k + 1), B, mxREAL), mxCreateDoubleMatrix(k, B, mxREAL),
+                  mxCreateDoubleMatrix(N * k, B, mxREAL), mxCreateDoubleMatrix((N + 1) * k, B, mxREAL),
+                  mxCreateNumericMatrix(k, B, mxINT32_CLASS, mxREAL),
+                  mxCreateNumericMatrix(k, B, mxINT32_CLASS, mxREAL), NULL, NULL, NULL, NULL, NULL};
+    if (obs) o.dk = mxCreateDoubleMatrix(2 * (k + 1), B, mxREAL);
+    if (est) {
+        o.xhk = mxCreateDoubleMatrix(2 * (k + 1), B, mxREAL);
+        o.yk = mxCreateDoubleMatrix(2 * k, B, mxREAL);
+    }
+    if (dly) {
+        o.uak = mxCreateDoubleMatrix(k, B, mxREAL);
+        o.xpk = mxCreateDoubleMatrix(2 * k, B, mxREAL);
+    }
+    return o;
+}
+
+/* hand a command's n outputs to plhs: as many as the caller asked for (one at least), the
+ * rest destroyed */
+static void put_outs(int nlhs, mxArray* plhs[], mxArray** outs, int n) {
+    for (int i = 0; i < n; ++i) {
+        if (i < (nlhs > 0 ? nlhs : 1)) plhs[i] = outs[i];
+        else mxDestroyArray(outs[i]);
+    }
+}
+
 static void do_step(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (nrhs < 4) mexErrMsgIdAndTxt("ntm:arg", "usage: ntm_mpc_mex('step', x_k, rho, Uold[, cfg[, ws]])");
     const ntm_config c = read_cfg(nrhs > 4 ? prhs[4] : NULL);
@@ -182,22 +277,8 @@ static void do_step(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
     /* value semantics: rho / Uold are updated in copies returned as outputs 6-7 */
     mxArray* rho = mxDuplicateArray(prhs[2]);
     mxArray* uold = mxDuplicateArray(prhs[3]);
-    mxArray* U = mxCreateDoubleMatrix(N, B, mxREAL);
-    mxArray* xp = mxCreateDoubleMatrix(2 * (N + 1), B, mxREAL);
-    mxArray* xn = mxCreateDoubleMatrix(2, B, mxREAL);
-    mxArray* fl = mxCreateNumericMatrix(1, B, mxINT32_CLASS, mxREAL);
-    mxArray* it = mxCreateNumericMatrix(1, B, mxINT32_CLASS, mxREAL);
-    mxArray* ws = NULL;
-    if (nrhs > 5) {
-        const mxArray* w = prhs[5];
-        if (!mxIsInt32(w) || mxGetM(w) != 2 * (N + 1) || mxGetN(w) != B)
-            mexErrMsgIdAndTxt("ntm:arg", "ws must be an int32 %d-by-%d array", (int)(2 * (N + 1)), (int)B);
-        ws = mxDuplicateArray(w);
-    } else {
-        ws = mxCreateNumericMatrix(2 * (N + 1), B, mxINT32_CLASS, mxREAL);
-        int32_t* wp = mxGetInt32s(ws);
-        for (size_t i = 0; i < B * 2 * (N + 1); ++i) wp[i] = -1;
-    }
+    const step_out o = new_step_out(N, B, 0, 0);
+    mxArray* ws = dup_ws(nrhs > 5 ? prhs[5] : NULL, N, B);
     mxArray* lam = NULL;
     mxArray* rq = NULL;
     if (nlhs > 8) {
@@ -206,20 +287,16 @@ static void do_step(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
                          : c.mode == NTM_MODE_FULL_DU ? 8 * N + 2 : 6 * N + 4;
         lam = mxCreateDoubleMatrix(m, B, mxREAL);
         rq = mxCreateDoubleMatrix(3 * N, B, mxREAL);
-        check(ntm_mpc_step_dual(ctx(), &p, &c, (int64_t)B, x, mxGetDoubles(rho), mxGetDoubles(uold), mxGetDoubles(U),
-                                mxGetDoubles(xp), mxGetDoubles(xn), mxGetInt32s(fl), mxGetInt32s(it), mxGetInt32s(ws),
-                                m ? mxGetDoubles(lam) : NULL, mxGetDoubles(rq)),
+        check(ntm_mpc_step_dual(ctx(), &p, &c, (int64_t)B, x, D(rho), D(uold), D(o.U), D(o.xp), D(o.xn), I(o.fl),
+                                I(o.it), I(ws), m ? D(lam) : NULL, D(rq)),
               "ntm_mpc_step_dual");
     } else {
-        check(ntm_mpc_step_ws(ctx(), &p, &c, (int64_t)B, x, mxGetDoubles(rho), mxGetDoubles(uold), mxGetDoubles(U),
-                              mxGetDoubles(xp), mxGetDoubles(xn), mxGetInt32s(fl), mxGetInt32s(it), mxGetInt32s(ws)),
+        check(ntm_mpc_step_ws(ctx(), &p, &c, (int64_t)B, x, D(rho), D(uold), D(o.U), D(o.xp), D(o.xn), I(o.fl),
+                              I(o.it), I(ws)),
               "ntm_mpc_step_ws");
     }
-    mxArray* outs[10] = {U, xp, xn, fl, it, rho, uold, ws, lam, rq};
-    for (int i = 0; i < (lam ? 10 : 8); ++i) {
-        if (i < (nlhs > 0 ? nlhs : 1)) plhs[i] = outs[i];
-        else mxDestroyArray(outs[i]);
-    }
+    mxArray* outs[10] = {o.U, o.xp, o.xn, o.fl, o.it, rho, uold, ws, lam, rq};
+    put_outs(nlhs, plhs, outs, lam ? 10 : 8);
 }
 
 static void do_init(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -231,7 +308,7 @@ static void do_init(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
     const double* x0 = in_matrix(prhs[1], 2, B, "x0");
     mxArray* rho = mxCreateDoubleMatrix(3 * N, B, mxREAL);
     mxArray* uold = mxCreateDoubleMatrix(N, B, mxREAL);
-    check(ntm_mpc_init(ctx(), &p, &c, (int64_t)B, x0, mxGetDoubles(rho), mxGetDoubles(uold)), "ntm_mpc_init");
+    check(ntm_mpc_init(ctx(), &p, &c, (int64_t)B, x0, D(rho), D(uold)), "ntm_mpc_init");
     plhs[0] = rho;
     if (nlhs > 1) plhs[1] = uold;
     else mxDestroyArray(uold);
@@ -244,22 +321,12 @@ static void do_run(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     ntm_physics_default(&p);
     const size_t B = mxGetN(prhs[1]), N = (size_t)c.N;
     const double* x0 = in_matrix(prhs[1], 2, B, "x0");
-    const int k = (int)mxGetScalar(prhs[2]);
-    if (k < 1) mexErrMsgIdAndTxt("ntm:arg", "k_sim must be >= 1");
-    mxArray* xk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
-    mxArray* uk = mxCreateDoubleMatrix((size_t)k, B, mxREAL);
-    mxArray* Uk = mxCreateDoubleMatrix(N * (size_t)k, B, mxREAL);
-    mxArray* wp = mxCreateDoubleMatrix((N + 1) * (size_t)k, B, mxREAL);
-    mxArray* fl = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
-    mxArray* it = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
-    check(ntm_mpc_run(ctx(), &p, &c, (int64_t)B, k, x0, mxGetDoubles(xk), mxGetDoubles(uk), mxGetDoubles(Uk),
-                      mxGetDoubles(wp), mxGetInt32s(fl), mxGetInt32s(it)),
+    const int k = in_ksim_run(prhs[2]);
+    const loop_out o = new_loop_out(k, N, B, 0, 0, 0);
+    check(ntm_mpc_run(ctx(), &p, &c, (int64_t)B, k, x0, D(o.xk), D(o.uk), D(o.Uk), D(o.wp), I(o.fl), I(o.it)),
           "ntm_mpc_run");
-    mxArray* outs[6] = {xk, uk, Uk, wp, fl, it};
-    for (int i = 0; i < 6; ++i) {
-        if (i < (nlhs > 0 ? nlhs : 1)) plhs[i] = outs[i];
-        else mxDestroyArray(outs[i]);
-    }
+    mxArray* outs[6] = {o.xk, o.uk, o.Uk, o.wp, o.fl, o.it};
+    put_outs(nlhs, plhs, outs, 6);
 }
 
 /* obs struct with any of nominal_model, gain (ntm_observer); missing fields are 0 */
@@ -276,7 +343,7 @@ static ntm_observer read_obs(const mxArray* s) {
  * back, updated, as output 9 */
 static void do_step_obs(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (nrhs < 6) mexErrMsgIdAndTxt("ntm:arg", "usage: ntm_mpc_mex('step_obs', x_k, rho, Uold, d_hat, obs[, cfg[, ws]])");
-    const ntm_observer o = read_obs(prhs[5]);
+    const ntm_observer ob = read_obs(prhs[5]);
     const ntm_config c = read_cfg(nrhs > 6 ? prhs[6] : NULL);
     ntm_physics p;
     ntm_physics_default(&p);
@@ -288,60 +355,32 @@ static void do_step_obs(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs
     mxArray* rho = mxDuplicateArray(prhs[2]);
     mxArray* uold = mxDuplicateArray(prhs[3]);
     mxArray* dh = mxDuplicateArray(prhs[4]);
-    mxArray* U = mxCreateDoubleMatrix(N, B, mxREAL);
-    mxArray* xp = mxCreateDoubleMatrix(2 * (N + 1), B, mxREAL);
-    mxArray* xn = mxCreateDoubleMatrix(2, B, mxREAL);
-    mxArray* fl = mxCreateNumericMatrix(1, B, mxINT32_CLASS, mxREAL);
-    mxArray* it = mxCreateNumericMatrix(1, B, mxINT32_CLASS, mxREAL);
-    mxArray* ws = NULL;
-    if (nrhs > 7) {
-        const mxArray* w = prhs[7];
-        if (!mxIsInt32(w) || mxGetM(w) != 2 * (N + 1) || mxGetN(w) != B)
-            mexErrMsgIdAndTxt("ntm:arg", "ws must be an int32 %d-by-%d array", (int)(2 * (N + 1)), (int)B);
-        ws = mxDuplicateArray(w);
-    } else {
-        ws = mxCreateNumericMatrix(2 * (N + 1), B, mxINT32_CLASS, mxREAL);
-        int32_t* wp = mxGetInt32s(ws);
-        for (size_t i = 0; i < B * 2 * (N + 1); ++i) wp[i] = -1;
-    }
-    check(ntm_mpc_step_obs(ctx(), &p, &c, &o, (int64_t)B, x, mxGetDoubles(rho), mxGetDoubles(uold), mxGetDoubles(dh),
-                           mxGetDoubles(U), mxGetDoubles(xp), mxGetDoubles(xn), mxGetInt32s(fl), mxGetInt32s(it),
-                           mxGetInt32s(ws)),
+    const step_out o = new_step_out(N, B, 0, 0);
+    mxArray* ws = dup_ws(nrhs > 7 ? prhs[7] : NULL, N, B);
+    check(ntm_mpc_step_obs(ctx(), &p, &c, &ob, (int64_t)B, x, D(rho), D(uold), D(dh), D(o.U), D(o.xp), D(o.xn), I(o.fl),
+                           I(o.it), I(ws)),
           "ntm_mpc_step_obs");
-    mxArray* outs[9] = {U, xp, xn, fl, it, rho, uold, ws, dh};
-    for (int i = 0; i < 9; ++i) {
-        if (i < (nlhs > 0 ? nlhs : 1)) plhs[i] = outs[i];
-        else mxDestroyArray(outs[i]);
-    }
+    mxArray* outs[9] = {o.U, o.xp, o.xn, o.fl, o.it, rho, uold, ws, dh};
+    put_outs(nlhs, plhs, outs, 9);
 }
 
 /* 'run' with the observer (ntm_mpc_run_obs): dk is output 7 */
 static void do_run_obs(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (nrhs < 4) mexErrMsgIdAndTxt("ntm:arg", "usage: ntm_mpc_mex('run_obs', x0, k_sim, obs[, cfg[, d0]])");
-    const ntm_observer o = read_obs(prhs[3]);
+    const ntm_observer ob = read_obs(prhs[3]);
     const ntm_config c = read_cfg(nrhs > 4 ? prhs[4] : NULL);
     ntm_physics p;
     ntm_physics_default(&p);
     const size_t B = mxGetN(prhs[1]), N = (size_t)c.N;
     const double* x0 = in_matrix(prhs[1], 2, B, "x0");
     const double* d0 = nrhs > 5 ? in_matrix(prhs[5], 2, B, "d0") : NULL;
-    const int k = (int)mxGetScalar(prhs[2]);
-    if (k < 1) mexErrMsgIdAndTxt("ntm:arg", "k_sim must be >= 1");
-    mxArray* xk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
-    mxArray* uk = mxCreateDoubleMatrix((size_t)k, B, mxREAL);
-    mxArray* Uk = mxCreateDoubleMatrix(N * (size_t)k, B, mxREAL);
-    mxArray* wp = mxCreateDoubleMatrix((N + 1) * (size_t)k, B, mxREAL);
-    mxArray* fl = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
-    mxArray* it = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
-    mxArray* dk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
-    check(ntm_mpc_run_obs(ctx(), &p, &c, &o, (int64_t)B, k, x0, d0, mxGetDoubles(xk), mxGetDoubles(uk),
-                          mxGetDoubles(Uk), mxGetDoubles(wp), mxGetDoubles(dk), mxGetInt32s(fl), mxGetInt32s(it)),
+    const int k = in_ksim_run(prhs[2]);
+    const loop_out o = new_loop_out(k, N, B, 1, 0, 0);
+    check(ntm_mpc_run_obs(ctx(), &p, &c, &ob, (int64_t)B, k, x0, d0, D(o.xk), D(o.uk), D(o.Uk), D(o.wp), D(o.dk),
+                          I(o.fl), I(o.it)),
           "ntm_mpc_run_obs");
-    mxArray* outs[7] = {xk, uk, Uk, wp, fl, it, dk};
-    for (int i = 0; i < 7; ++i) {
-        if (i < (nlhs > 0 ? nlhs : 1)) plhs[i] = outs[i];
-        else mxDestroyArray(outs[i]);
-    }
+    mxArray* outs[7] = {o.xk, o.uk, o.Uk, o.wp, o.fl, o.it, o.dk};
+    put_outs(nlhs, plhs, outs, 7);
 }
 
 /* est struct with any of nominal_model, gain, kappa, sigma_y (ntm_estimator); the last
@@ -387,38 +426,13 @@ static void do_step_est(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs
     mxArray* uold = mxDuplicateArray(prhs[3]);
     mxArray* dh = mxDuplicateArray(prhs[4]);
     mxArray* xh = mxDuplicateArray(prhs[5]);
-    mxArray* U = mxCreateDoubleMatrix(N, B, mxREAL);
-    mxArray* xp = mxCreateDoubleMatrix(2 * (N + 1), B, mxREAL);
-    mxArray* xn = mxCreateDoubleMatrix(2, B, mxREAL);
-    mxArray* y = mxCreateDoubleMatrix(2, B, mxREAL);
-    mxArray* fl = mxCreateNumericMatrix(1, B, mxINT32_CLASS, mxREAL);
-    mxArray* it = mxCreateNumericMatrix(1, B, mxINT32_CLASS, mxREAL);
-    mxArray* ws = NULL;
-    if (nrhs > 8) {
-        const mxArray* w = prhs[8];
-        if (!mxIsInt32(w) || mxGetM(w) != 2 * (N + 1) || mxGetN(w) != B)
-            mexErrMsgIdAndTxt("ntm:arg", "ws must be an int32 %d-by-%d array", (int)(2 * (N + 1)), (int)B);
-        ws = mxDuplicateArray(w);
-    } else {
-        ws = mxCreateNumericMatrix(2 * (N + 1), B, mxINT32_CLASS, mxREAL);
-        int32_t* wp = mxGetInt32s(ws);
-        for (size_t i = 0; i < B * 2 * (N + 1); ++i) wp[i] = -1;
-    }
-    check(ntm_mpc_step_est(ctx(), &p, &c, &e, (int64_t)B, x, mxGetDoubles(rho), mxGetDoubles(uold), mxGetDoubles(dh),
-                           mxGetDoubles(xh), mxGetDoubles(U), mxGetDoubles(xp), mxGetDoubles(xn), mxGetDoubles(y),
-                           mxGetInt32s(fl), mxGetInt32s(it), mxGetInt32s(ws)),
+    const step_out o = new_step_out(N, B, 1, 0);
+    mxArray* ws = dup_ws(nrhs > 8 ? prhs[8] : NULL, N, B);
+    check(ntm_mpc_step_est(ctx(), &p, &c, &e, (int64_t)B, x, D(rho), D(uold), D(dh), D(xh), D(o.U), D(o.xp), D(o.xn),
+                           D(o.y), I(o.fl), I(o.it), I(ws)),
           "ntm_mpc_step_est");
-    mxArray* outs[11] = {U, xp, xn, fl, it, rho, uold, ws, dh, xh, y};
-    for (int i = 0; i < 11; ++i) {
-        if (i < (nlhs > 0 ? nlhs : 1)) plhs[i] = outs[i];
-        else mxDestroyArray(outs[i]);
-    }
-}
-
-/* an optional 2-by-B input: omitted or [] gives NULL */
-static const double* opt_matrix(int nrhs, const mxArray* prhs[], int i, size_t B, const char* name) {
-    if (nrhs <= i || (mxIsDouble(prhs[i]) && mxGetNumberOfElements(prhs[i]) == 0)) return NULL;
-    return in_matrix(prhs[i], 2, B, name);
+    mxArray* outs[11] = {o.U, o.xp, o.xn, o.fl, o.it, rho, uold, ws, dh, xh, o.y};
+    put_outs(nlhs, plhs, outs, 11);
 }
 
 /* 'run_obs' with the estimator (ntm_mpc_run_est): dk, xhk and yk are outputs 7 to 9 */
@@ -432,38 +446,13 @@ static void do_run_est(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[
     const double* x0 = in_matrix(prhs[1], 2, B, "x0");
     const double* d0 = opt_matrix(nrhs, prhs, 5, B, "d0");
     const double* h0 = opt_matrix(nrhs, prhs, 6, B, "xhat0");
-    const int k = (int)mxGetScalar(prhs[2]);
-    if (k < 1) mexErrMsgIdAndTxt("ntm:arg", "k_sim must be >= 1");
-    mxArray* xk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
-    mxArray* uk = mxCreateDoubleMatrix((size_t)k, B, mxREAL);
-    mxArray* Uk = mxCreateDoubleMatrix(N * (size_t)k, B, mxREAL);
-    mxArray* wp = mxCreateDoubleMatrix((N + 1) * (size_t)k, B, mxREAL);
-    mxArray* fl = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
-    mxArray* it = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
-    mxArray* dk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
-    mxArray* xhk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
-    mxArray* yk = mxCreateDoubleMatrix(2 * (size_t)k, B, mxREAL);
-    check(ntm_mpc_run_est(ctx(), &p, &c, &e, (int64_t)B, k, x0, d0, h0, mxGetDoubles(xk), mxGetDoubles(uk),
-                          mxGetDoubles(Uk), mxGetDoubles(wp), mxGetDoubles(dk), mxGetDoubles(xhk), mxGetDoubles(yk),
-                          mxGetInt32s(fl), mxGetInt32s(it)),
+    const int k = in_ksim_run(prhs[2]);
+    const loop_out o = new_loop_out(k, N, B, 1, 1, 0);
+    check(ntm_mpc_run_est(ctx(), &p, &c, &e, (int64_t)B, k, x0, d0, h0, D(o.xk), D(o.uk), D(o.Uk), D(o.wp), D(o.dk),
+                          D(o.xhk), D(o.yk), I(o.fl), I(o.it)),
           "ntm_mpc_run_est");
-    mxArray* outs[9] = {xk, uk, Uk, wp, fl, it, dk, xhk, yk};
-    for (int i = 0; i < 9; ++i) {
-        if (i < (nlhs > 0 ? nlhs : 1)) plhs[i] = outs[i];
-        else mxDestroyArray(outs[i]);
-    }
-}
-
-/* the int32 2(N+1)-by-B warm-start workspace of the resumable loops (required there) */
-static void in_ws(const mxArray* w, size_t N, size_t B) {
-    if (!mxIsInt32(w) || mxGetM(w) != 2 * (N + 1) || mxGetN(w) != B)
-        mexErrMsgIdAndTxt("ntm:arg", "ws must be an int32 %d-by-%d array", (int)(2 * (N + 1)), (int)B);
-}
-
-static int in_ksim(const mxArray* a) {
-    if (!mxIsDouble(a) || mxGetNumberOfElements(a) != 1 || !(mxGetScalar(a) >= 0))
-        mexErrMsgIdAndTxt("ntm:arg", "k_sim must be a scalar >= 0");
-    return (int)mxGetScalar(a);
+    mxArray* outs[9] = {o.xk, o.uk, o.Uk, o.wp, o.fl, o.it, o.dk, o.xhk, o.yk};
+    put_outs(nlhs, plhs, outs, 9);
 }
 
 /* 'run' from a carried state (ntm_mpc_run_from): the state is outputs 7 to 10 */
@@ -482,21 +471,12 @@ static void do_run_from(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs
     mxArray* rho = mxDuplicateArray(prhs[2]);
     mxArray* uold = mxDuplicateArray(prhs[3]);
     mxArray* ws = mxDuplicateArray(prhs[4]);
-    mxArray* xk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
-    mxArray* uk = mxCreateDoubleMatrix((size_t)k, B, mxREAL);
-    mxArray* Uk = mxCreateDoubleMatrix(N * (size_t)k, B, mxREAL);
-    mxArray* wp = mxCreateDoubleMatrix((N + 1) * (size_t)k, B, mxREAL);
-    mxArray* fl = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
-    mxArray* it = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
-    check(ntm_mpc_run_from(ctx(), &p, &c, (int64_t)B, k, mxGetDoubles(x), mxGetDoubles(rho), mxGetDoubles(uold),
-                           mxGetInt32s(ws), mxGetDoubles(xk), mxGetDoubles(uk), mxGetDoubles(Uk), mxGetDoubles(wp),
-                           mxGetInt32s(fl), mxGetInt32s(it)),
+    const loop_out o = new_loop_out(k, N, B, 0, 0, 0);
+    check(ntm_mpc_run_from(ctx(), &p, &c, (int64_t)B, k, D(x), D(rho), D(uold), I(ws), D(o.xk), D(o.uk), D(o.Uk),
+                           D(o.wp), I(o.fl), I(o.it)),
           "ntm_mpc_run_from");
-    mxArray* outs[10] = {xk, uk, Uk, wp, fl, it, x, rho, uold, ws};
-    for (int i = 0; i < 10; ++i) {
-        if (i < (nlhs > 0 ? nlhs : 1)) plhs[i] = outs[i];
-        else mxDestroyArray(outs[i]);
-    }
+    mxArray* outs[10] = {o.xk, o.uk, o.Uk, o.wp, o.fl, o.it, x, rho, uold, ws};
+    put_outs(nlhs, plhs, outs, 10);
 }
 
 /* 'run_est' from a carried state (ntm_mpc_run_est_from): the state is outputs 10 to 15 */
@@ -522,25 +502,12 @@ static void do_run_est_from(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     mxArray* ws = mxDuplicateArray(prhs[4]);
     mxArray* dh = mxDuplicateArray(prhs[5]);
     mxArray* xh = mxDuplicateArray(prhs[6]);
-    mxArray* xk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
-    mxArray* uk = mxCreateDoubleMatrix((size_t)k, B, mxREAL);
-    mxArray* Uk = mxCreateDoubleMatrix(N * (size_t)k, B, mxREAL);
-    mxArray* wp = mxCreateDoubleMatrix((N + 1) * (size_t)k, B, mxREAL);
-    mxArray* fl = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
-    mxArray* it = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
-    mxArray* dk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
-    mxArray* xhk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
-    mxArray* yk = mxCreateDoubleMatrix(2 * (size_t)k, B, mxREAL);
-    check(ntm_mpc_run_est_from(ctx(), &p, &c, &e, (int64_t)B, k, mxGetDoubles(x), mxGetDoubles(rho), mxGetDoubles(uold),
-                               mxGetInt32s(ws), mxGetDoubles(dh), mxGetDoubles(xh), mxGetDoubles(xk), mxGetDoubles(uk),
-                               mxGetDoubles(Uk), mxGetDoubles(wp), mxGetDoubles(dk), mxGetDoubles(xhk),
-                               mxGetDoubles(yk), mxGetInt32s(fl), mxGetInt32s(it)),
+    const loop_out o = new_loop_out(k, N, B, 1, 1, 0);
+    check(ntm_mpc_run_est_from(ctx(), &p, &c, &e, (int64_t)B, k, D(x), D(rho), D(uold), I(ws), D(dh), D(xh), D(o.xk),
+                               D(o.uk), D(o.Uk), D(o.wp), D(o.dk), D(o.xhk), D(o.yk), I(o.fl), I(o.it)),
           "ntm_mpc_run_est_from");
-    mxArray* outs[15] = {xk, uk, Uk, wp, fl, it, dk, xhk, yk, x, rho, uold, ws, dh, xh};
-    for (int i = 0; i < 15; ++i) {
-        if (i < (nlhs > 0 ? nlhs : 1)) plhs[i] = outs[i];
-        else mxDestroyArray(outs[i]);
-    }
+    mxArray* outs[15] = {o.xk, o.uk, o.Uk, o.wp, o.fl, o.it, o.dk, o.xhk, o.yk, x, rho, uold, ws, dh, xh};
+    put_outs(nlhs, plhs, outs, 15);
 }
 
 /* dly struct with steps (0 .. NTM_MAX_DELAY) and predict (missing: 1) (ntm_delay) */
@@ -558,13 +525,6 @@ static ntm_delay read_dly(const mxArray* s) {
 static void in_queue(const mxArray* a, size_t steps, size_t B, const char* name) {
     if (steps == 0 && mxIsDouble(a) && mxGetNumberOfElements(a) == 0) return;
     in_matrix(a, steps, B, name);
-}
-
-static void put_outs(int nlhs, mxArray* plhs[], mxArray** outs, int n) {
-    for (int i = 0; i < n; ++i) {
-        if (i < (nlhs > 0 ? nlhs : 1)) plhs[i] = outs[i];
-        else mxDestroyArray(outs[i]);
-    }
 }
 
 /* 'step_est' with the dead time (ntm_mpc_step_dly): u_queue goes in after x_hat, dly after
@@ -590,29 +550,12 @@ static void do_step_dly(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs
     mxArray* dh = mxDuplicateArray(prhs[4]);
     mxArray* xh = mxDuplicateArray(prhs[5]);
     mxArray* uq = d.steps ? mxDuplicateArray(prhs[6]) : mxCreateDoubleMatrix(0, B, mxREAL);
-    mxArray* U = mxCreateDoubleMatrix(N, B, mxREAL);
-    mxArray* xp = mxCreateDoubleMatrix(2 * (N + 1), B, mxREAL);
-    mxArray* xn = mxCreateDoubleMatrix(2, B, mxREAL);
-    mxArray* y = mxCreateDoubleMatrix(2, B, mxREAL);
-    mxArray* z = mxCreateDoubleMatrix(2, B, mxREAL);
-    mxArray* ua = mxCreateDoubleMatrix(1, B, mxREAL);
-    mxArray* fl = mxCreateNumericMatrix(1, B, mxINT32_CLASS, mxREAL);
-    mxArray* it = mxCreateNumericMatrix(1, B, mxINT32_CLASS, mxREAL);
-    mxArray* ws = NULL;
-    if (nrhs > 10) {
-        in_ws(prhs[10], N, B);
-        ws = mxDuplicateArray(prhs[10]);
-    } else {
-        ws = mxCreateNumericMatrix(2 * (N + 1), B, mxINT32_CLASS, mxREAL);
-        int32_t* wp = mxGetInt32s(ws);
-        for (size_t i = 0; i < B * 2 * (N + 1); ++i) wp[i] = -1;
-    }
-    check(ntm_mpc_step_dly(ctx(), &p, &c, &e, &d, (int64_t)B, x, mxGetDoubles(rho), mxGetDoubles(uold), mxGetDoubles(dh),
-                           mxGetDoubles(xh), d.steps ? mxGetDoubles(uq) : NULL, mxGetDoubles(U), mxGetDoubles(xp),
-                           mxGetDoubles(xn), mxGetDoubles(y), mxGetDoubles(z), mxGetDoubles(ua), mxGetInt32s(fl),
-                           mxGetInt32s(it), mxGetInt32s(ws)),
+    const step_out o = new_step_out(N, B, 1, 1);
+    mxArray* ws = dup_ws(nrhs > 10 ? prhs[10] : NULL, N, B);
+    check(ntm_mpc_step_dly(ctx(), &p, &c, &e, &d, (int64_t)B, x, D(rho), D(uold), D(dh), D(xh), d.steps ? D(uq) : NULL,
+                           D(o.U), D(o.xp), D(o.xn), D(o.y), D(o.z), D(o.ua), I(o.fl), I(o.it), I(ws)),
           "ntm_mpc_step_dly");
-    mxArray* outs[14] = {U, xp, xn, fl, it, rho, uold, ws, dh, xh, y, uq, z, ua};
+    mxArray* outs[14] = {o.U, o.xp, o.xn, o.fl, o.it, rho, uold, ws, dh, xh, o.y, uq, o.z, o.ua};
     put_outs(nlhs, plhs, outs, 14);
 }
 
@@ -632,24 +575,12 @@ static void do_run_dly(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[
     const double* q0 = NULL;
     if (nrhs > 8 && !(mxIsDouble(prhs[8]) && mxGetNumberOfElements(prhs[8]) == 0))
         q0 = in_matrix(prhs[8], (size_t)d.steps, B, "uq0");
-    const int k = (int)mxGetScalar(prhs[2]);
-    if (k < 1) mexErrMsgIdAndTxt("ntm:arg", "k_sim must be >= 1");
-    mxArray* xk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
-    mxArray* uk = mxCreateDoubleMatrix((size_t)k, B, mxREAL);
-    mxArray* Uk = mxCreateDoubleMatrix(N * (size_t)k, B, mxREAL);
-    mxArray* wp = mxCreateDoubleMatrix((N + 1) * (size_t)k, B, mxREAL);
-    mxArray* fl = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
-    mxArray* it = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
-    mxArray* dk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
-    mxArray* xhk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
-    mxArray* yk = mxCreateDoubleMatrix(2 * (size_t)k, B, mxREAL);
-    mxArray* uak = mxCreateDoubleMatrix((size_t)k, B, mxREAL);
-    mxArray* xpk = mxCreateDoubleMatrix(2 * (size_t)k, B, mxREAL);
-    check(ntm_mpc_run_dly(ctx(), &p, &c, &e, &d, (int64_t)B, k, x0, d0, h0, q0, mxGetDoubles(xk), mxGetDoubles(uk),
-                          mxGetDoubles(Uk), mxGetDoubles(wp), mxGetDoubles(dk), mxGetDoubles(xhk), mxGetDoubles(yk),
-                          mxGetDoubles(uak), mxGetDoubles(xpk), mxGetInt32s(fl), mxGetInt32s(it)),
+    const int k = in_ksim_run(prhs[2]);
+    const loop_out o = new_loop_out(k, N, B, 1, 1, 1);
+    check(ntm_mpc_run_dly(ctx(), &p, &c, &e, &d, (int64_t)B, k, x0, d0, h0, q0, D(o.xk), D(o.uk), D(o.Uk), D(o.wp),
+                          D(o.dk), D(o.xhk), D(o.yk), D(o.uak), D(o.xpk), I(o.fl), I(o.it)),
           "ntm_mpc_run_dly");
-    mxArray* outs[11] = {xk, uk, Uk, wp, fl, it, dk, xhk, yk, uak, xpk};
+    mxArray* outs[11] = {o.xk, o.uk, o.Uk, o.wp, o.fl, o.it, o.dk, o.xhk, o.yk, o.uak, o.xpk};
     put_outs(nlhs, plhs, outs, 11);
 }
 
@@ -680,24 +611,13 @@ static void do_run_dly_from(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     mxArray* dh = mxDuplicateArray(prhs[5]);
     mxArray* xh = mxDuplicateArray(prhs[6]);
     mxArray* uq = d.steps ? mxDuplicateArray(prhs[7]) : mxCreateDoubleMatrix(0, B, mxREAL);
-    mxArray* xk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
-    mxArray* uk = mxCreateDoubleMatrix((size_t)k, B, mxREAL);
-    mxArray* Uk = mxCreateDoubleMatrix(N * (size_t)k, B, mxREAL);
-    mxArray* wp = mxCreateDoubleMatrix((N + 1) * (size_t)k, B, mxREAL);
-    mxArray* fl = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
-    mxArray* it = mxCreateNumericMatrix((size_t)k, B, mxINT32_CLASS, mxREAL);
-    mxArray* dk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
-    mxArray* xhk = mxCreateDoubleMatrix(2 * (size_t)(k + 1), B, mxREAL);
-    mxArray* yk = mxCreateDoubleMatrix(2 * (size_t)k, B, mxREAL);
-    mxArray* uak = mxCreateDoubleMatrix((size_t)k, B, mxREAL);
-    mxArray* xpk = mxCreateDoubleMatrix(2 * (size_t)k, B, mxREAL);
-    check(ntm_mpc_run_dly_from(ctx(), &p, &c, &e, &d, (int64_t)B, k, mxGetDoubles(x), mxGetDoubles(rho),
-                               mxGetDoubles(uold), mxGetInt32s(ws), mxGetDoubles(dh), mxGetDoubles(xh),
-                               d.steps ? mxGetDoubles(uq) : NULL, mxGetDoubles(xk), mxGetDoubles(uk), mxGetDoubles(Uk),
-                               mxGetDoubles(wp), mxGetDoubles(dk), mxGetDoubles(xhk), mxGetDoubles(yk),
-                               mxGetDoubles(uak), mxGetDoubles(xpk), mxGetInt32s(fl), mxGetInt32s(it)),
+    const loop_out o = new_loop_out(k, N, B, 1, 1, 1);
+    check(ntm_mpc_run_dly_from(ctx(), &p, &c, &e, &d, (int64_t)B, k, D(x), D(rho), D(uold), I(ws), D(dh), D(xh),
+                               d.steps ? D(uq) : NULL, D(o.xk), D(o.uk), D(o.Uk), D(o.wp), D(o.dk), D(o.xhk), D(o.yk),
+                               D(o.uak), D(o.xpk), I(o.fl), I(o.it)),
           "ntm_mpc_run_dly_from");
-    mxArray* outs[18] = {xk, uk, Uk, wp, fl, it, dk, xhk, yk, uak, xpk, x, rho, uold, ws, dh, xh, uq};
+    mxArray* outs[18] = {o.xk, o.uk,  o.Uk, o.wp, o.fl,  o.it, o.dk, o.xhk, o.yk,
+                         o.uak, o.xpk, x,   rho,  uold, ws,   dh,   xh,    uq};
     put_outs(nlhs, plhs, outs, 18);
 }
 

@@ -75,7 +75,20 @@ _OBS = C.POINTER(NtmObserver)
 _EST = C.POINTER(NtmEstimator)
 _DLY = C.POINTER(NtmDelay)
 
-# name -> (restype, argtypes)
+
+def _both(name, head, arrays):
+    """The host entry point ``name`` and its ``_device`` twin, both returning int: context,
+    physics and ``head`` (config, option structs, dimensions), then ``arrays``, a string of
+    "d" (double*) and "i" (int32_t*).  The device form takes every array as void* (device
+    memory) and a trailing void*, the stream."""
+    lead = [C.c_void_p, _PHY] + head
+    return {name: (C.c_int, lead + [_DP if a == "d" else _IP for a in arrays]),
+            name + "_device": (C.c_int, lead + [_V] * (len(arrays) + 1))}
+
+
+_B, _K = C.c_int64, C.c_int32          # the batch size; the number of closed-loop steps
+
+# name -> (restype, argtypes); tests/test_host_signatures.py checks every entry against the header's prototype
 EXPORTS = {
     "ntm_physics_default": (None, [_PHY]),
     "ntm_config_default": (None, [_CFG, C.c_int32]),
@@ -92,16 +105,10 @@ EXPORTS = {
                                           C.POINTER(C.c_int32)]),
     "ntm_debug_stamps": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
     "ntm_step_launch_info": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-    "ntm_mpc_init": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, _DP, _DP, _DP]),
-    "ntm_mpc_init_device": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, _V, _V, _V, _V]),
-    "ntm_mpc_step": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, _DP, _DP, _DP, _DP, _DP, _DP, _IP, _IP]),
-    "ntm_mpc_step_device": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
-    "ntm_mpc_step_ws": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, _DP, _DP, _DP, _DP, _DP, _DP, _IP, _IP, _IP]),
-    "ntm_mpc_step_ws_device": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, _V, _V, _V, _V, _V, _V, _V, _V, _V,
-                                         _V]),
-    "ntm_mpc_run": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, C.c_int32, _DP, _DP, _DP, _DP, _DP, _IP, _IP]),
-    "ntm_mpc_run_device": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, C.c_int32, _V, _V, _V, _V, _V, _V,
-                                     _V, _V]),
+    **_both("ntm_mpc_init", [_CFG, _B], "ddd"),
+    **_both("ntm_mpc_step", [_CFG, _B], "dddddd" "ii"),
+    **_both("ntm_mpc_step_ws", [_CFG, _B], "dddddd" "iii"),
+    **_both("ntm_mpc_run", [_CFG, _B, _K], "ddddd" "ii"),
     "ntm_rho_device": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, _V, _V, _V]),
     "ntm_AB_device": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, _V, _V, _V, _V]),
     "ntm_lift_device": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, _V, _V, _V, _V, _V]),
@@ -112,41 +119,16 @@ EXPORTS = {
                                       _V, _V, _V]),
     "ntm_qp_dual_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V, _V,
                                      _V]),
-    "ntm_mpc_step_dual": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, _DP, _DP, _DP, _DP, _DP, _DP, _IP, _IP, _IP,
-                                    _DP, _DP]),
-    "ntm_mpc_step_dual_device": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, _V, _V, _V, _V, _V, _V, _V, _V, _V,
-                                           _V, _V, _V]),
-    "ntm_mpc_step_obs": (C.c_int, [C.c_void_p, _PHY, _CFG, _OBS, C.c_int64, _DP, _DP, _DP, _DP, _DP, _DP, _DP, _IP, _IP,
-                                   _IP]),
-    "ntm_mpc_step_obs_device": (C.c_int, [C.c_void_p, _PHY, _CFG, _OBS, C.c_int64, _V, _V, _V, _V, _V, _V, _V, _V, _V,
-                                          _V, _V]),
-    "ntm_mpc_run_obs": (C.c_int, [C.c_void_p, _PHY, _CFG, _OBS, C.c_int64, C.c_int32, _DP, _DP, _DP, _DP, _DP, _DP, _DP,
-                                  _IP, _IP]),
-    "ntm_mpc_run_obs_device": (C.c_int, [C.c_void_p, _PHY, _CFG, _OBS, C.c_int64, C.c_int32, _V, _V, _V, _V, _V, _V,
-                                         _V, _V, _V, _V]),
-    "ntm_mpc_step_est": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, C.c_int64, _DP, _DP, _DP, _DP, _DP, _DP, _DP, _DP, _DP,
-                                   _IP, _IP, _IP]),
-    "ntm_mpc_step_est_device": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, C.c_int64, _V, _V, _V, _V, _V, _V, _V, _V, _V,
-                                          _V, _V, _V, _V]),
-    "ntm_mpc_run_est": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, C.c_int64, C.c_int32, _DP, _DP, _DP, _DP, _DP, _DP, _DP,
-                                  _DP, _DP, _DP, _IP, _IP]),
-    "ntm_mpc_run_est_device": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, C.c_int64, C.c_int32, _V, _V, _V, _V, _V, _V,
-                                         _V, _V, _V, _V, _V, _V, _V]),
-    "ntm_mpc_run_from": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, C.c_int32, _DP, _DP, _DP, _IP, _DP, _DP, _DP, _DP,
-                                   _IP, _IP]),
-    "ntm_mpc_run_from_device": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V,
-                                          _V, _V, _V]),
-    "ntm_mpc_run_est_from": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, C.c_int64, C.c_int32, _DP, _DP, _DP, _IP, _DP, _DP,
-                                       _DP, _DP, _DP, _DP, _DP, _DP, _DP, _IP, _IP]),
-    "ntm_mpc_run_est_from_device": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, C.c_int64, C.c_int32, _V, _V, _V, _V, _V,
-                                              _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
-    "ntm_mpc_step_dly": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, _DLY, C.c_int64] + [_DP] * 12 + [_IP] * 3),
-    "ntm_mpc_step_dly_device": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, _DLY, C.c_int64] + [_V] * 16),
-    "ntm_mpc_run_dly": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, _DLY, C.c_int64, C.c_int32] + [_DP] * 13 + [_IP] * 2),
-    "ntm_mpc_run_dly_device": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, _DLY, C.c_int64, C.c_int32] + [_V] * 16),
-    "ntm_mpc_run_dly_from": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, _DLY, C.c_int64, C.c_int32] + [_DP] * 3 + [_IP]
-                             + [_DP] * 12 + [_IP] * 2),
-    "ntm_mpc_run_dly_from_device": (C.c_int, [C.c_void_p, _PHY, _CFG, _EST, _DLY, C.c_int64, C.c_int32] + [_V] * 19),
+    **_both("ntm_mpc_step_dual", [_CFG, _B], "dddddd" "iii" "dd"),
+    **_both("ntm_mpc_step_obs", [_CFG, _OBS, _B], "ddddddd" "iii"),
+    **_both("ntm_mpc_run_obs", [_CFG, _OBS, _B, _K], "ddddddd" "ii"),
+    **_both("ntm_mpc_step_est", [_CFG, _EST, _B], "ddddddddd" "iii"),
+    **_both("ntm_mpc_run_est", [_CFG, _EST, _B, _K], "dddddddddd" "ii"),
+    **_both("ntm_mpc_run_from", [_CFG, _B, _K], "ddd" "i" "dddd" "ii"),
+    **_both("ntm_mpc_run_est_from", [_CFG, _EST, _B, _K], "ddd" "i" "ddddddddd" "ii"),
+    **_both("ntm_mpc_step_dly", [_CFG, _EST, _DLY, _B], "d" * 12 + "iii"),
+    **_both("ntm_mpc_run_dly", [_CFG, _EST, _DLY, _B, _K], "d" * 13 + "ii"),
+    **_both("ntm_mpc_run_dly_from", [_CFG, _EST, _DLY, _B, _K], "ddd" "i" + "d" * 12 + "ii"),
     "ntm_qp_kkt_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V]),
     "ntm_mpc_kkt_device": (C.c_int, [C.c_void_p, _PHY, _CFG, C.c_int64, _V, _V, _V, _V, _V, _V]),
     "ntm_scenarios_x0": (None, [C.c_uint64, C.c_int64, C.c_int64, _DP]),

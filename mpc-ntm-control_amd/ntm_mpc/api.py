@@ -196,14 +196,25 @@ def _ptr(t: torch.Tensor | None):
     return C.c_void_p(t.data_ptr())
 
 
-def _check_dev(t: torch.Tensor, shape, dtype=torch.float64, name="tensor"):
-    """Plain contiguous CUDA array (instrumentation counters, SoA)."""
+def _host_ptr(a: np.ndarray | None):
+    """Host pointer typed by the array's dtype (int32 or double); None stays None."""
+    if a is None:
+        return None
+    return a.ctypes.data_as(L._IP if a.dtype == np.int32 else L._DP)
+
+
+def _dev_checked(t, shape, dtype, name):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise ValueError(f"{name} must be a CUDA tensor")
     if t.dtype != dtype:
         raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
     if tuple(t.shape) != tuple(shape):
         raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def _check_dev(t: torch.Tensor, shape, dtype=torch.float64, name="tensor"):
+    """Plain contiguous CUDA array (instrumentation counters, SoA)."""
+    _dev_checked(t, shape, dtype, name)
     if not t.is_contiguous():
         raise ValueError(f"{name} must be contiguous")
 
@@ -217,12 +228,7 @@ def is_scenario_major(a) -> bool:
 
 def _dev_arg(t, shape, dtype=torch.float64, name="tensor"):
     """Validate an (E, B) CUDA argument; return (array in the ABI layout, staged?)."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise ValueError(f"{name} must be a CUDA tensor")
-    if t.dtype != dtype:
-        raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    _dev_checked(t, shape, dtype, name)
     if is_scenario_major(t):
         return t, False
     return t.T.contiguous().T, True
@@ -250,6 +256,66 @@ def device_tensor(a, device=None, dtype=torch.float64) -> torch.Tensor:
     return torch.tensor(np.ascontiguousarray(a.T), dtype=dtype, device=dev).T
 
 
+class _Device:
+    """What the ``_device`` form of an entry point needs: CUDA tensors in and out, the
+    launch on the controller's current stream.  ``arg`` validates an argument into the ABI
+    layout, ``empty`` allocates, ``ptr`` makes a pointer (None: NULL), ``copy_back`` returns
+    a staged in/out argument; ``suffix`` ends the symbol, ``tail`` the argument list."""
+    suffix, i32 = "_device", torch.int32
+    arg, ptr = staticmethod(_dev_arg), staticmethod(_ptr)
+
+    def __init__(self, device: int):
+        self.device = device
+
+    def empty(self, *shape, dtype=torch.float64):
+        """(E, B) output in the ABI's scenario-major layout (1-D: plain)."""
+        dev = f"cuda:{self.device}"
+        if len(shape) == 2:
+            return torch.empty(shape[1], shape[0], dtype=dtype, device=dev).T
+        return torch.empty(*shape, dtype=dtype, device=dev)
+
+    def stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def tail(self):
+        return (self.stream(),)
+
+    @staticmethod
+    def copy_back(dst, src):
+        dst.copy_(src)
+
+
+class _Host:
+    """The host form (the MEX path): NumPy arrays, which the library stages itself."""
+    suffix, i32 = "", np.int32
+    arg, empty, ptr = staticmethod(_host_arg), staticmethod(_host_empty), staticmethod(_host_ptr)
+
+    @staticmethod
+    def tail():
+        return ()
+
+    @staticmethod
+    def copy_back(dst, src):
+        dst[...] = src
+
+
+_HOST = _Host()
+_NONE = {}          # no carried arrays (a default argument; never written to)
+
+
+def _optional(arg, a, *spec, **kw):
+    """``arg`` for an argument that may be None: (None, False) then."""
+    return (None, False) if a is None else arg(a, *spec, **kw)
+
+
+def _queue_arg(be, q, opts, Bn, name):
+    """The dead time's queue (steps, B) as (array, staged?); None where there is none.  The
+    delay is the last of the option structs."""
+    if q is None:
+        return None, False
+    return be.arg(q, (int(opts[-1].steps), Bn), name=name)
+
+
 class NtmMpc:
     """Batched LPV-MPC controller on one MI355X (one ``ntm_ctx`` per device)."""
 
@@ -261,6 +327,7 @@ class NtmMpc:
         self.physics = physics or Physics()
         self.config = config or Config()
         self.gen = None
+        self._dev = _Device(self.device)
         self._ctx = C.c_void_p()
         rc = self.lib.ntm_ctx_create(C.byref(self._ctx), self.device)
         if rc != L.NTM_OK:
@@ -282,7 +349,7 @@ class NtmMpc:
         return (cfg or self.config).to_c()
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return self._dev.stream()
 
     def _raise(self, rc, what):
         if rc != L.NTM_OK:
@@ -290,10 +357,7 @@ class NtmMpc:
 
     def _empty(self, *shape, dtype=torch.float64):
         """(E, B) output in the ABI's scenario-major layout (1-D: plain)."""
-        dev = f"cuda:{self.device}"
-        if len(shape) == 2:
-            return torch.empty(shape[1], shape[0], dtype=dtype, device=dev).T
-        return torch.empty(*shape, dtype=dtype, device=dev)
+        return self._dev.empty(*shape, dtype=dtype)
 
     def tensor(self, a, dtype=torch.float64) -> torch.Tensor:
         """(E, B) host data -> device tensor in the ABI layout on this controller's GPU."""
@@ -358,28 +422,136 @@ class NtmMpc:
         build = self.step_build(B, cfg)
         return f"k_mpc_step<P={lanes},NN={nn},{layout}>" + (" (one-wave budget)" if build == "lds1" else "")
 
+    # ------------------------------------------------------------ closed-loop entry points: one body per family
+    # Every public method below forwards here with its backend (self._dev or _HOST); the
+    # argument list of each entry point is marshalled in one place, in the ABI's order.
+    def _call(self, be, entry, cfg, opts, dims, arrays):
+        """ntm_mpc_<entry> in the backend's form: context, physics, cfg, the option structs,
+        the dimensions, every array (None: NULL), then the backend's trailing arguments."""
+        what = "ntm_mpc_" + entry + be.suffix
+        rc = getattr(self.lib, what)(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
+                                     *[C.byref(o.to_c()) for o in opts], *dims, *[be.ptr(a) for a in arrays],
+                                     *be.tail())
+        self._raise(rc, what)
+
+    def _need_run_from(self):
+        if not L.has_run_from(self.lib):
+            raise NtmLibraryError("this build of the library has no ntm_mpc_run_from (NTM_MPC_HAS_RUN_FROM)")
+
+    def _need_input_delay(self, entry):
+        if not L.has_input_delay(self.lib):
+            raise NtmLibraryError(f"this build of the library has no {entry} (NTM_MPC_HAS_INPUT_DELAY)")
+
+    @staticmethod
+    def _carried_args(be, carried, opts, Bn):
+        """The estimator's carried d_hat / x_hat (2, B) and the dead time's u_queue (steps, B;
+        None where there is none), by name and in the ABI's order, as [(array, staged?)]."""
+        return [_queue_arg(be, a, opts, Bn, n) if n == "u_queue" else be.arg(a, (2, Bn), name=n)
+                for n, a in carried.items()]
+
+    def _initial_state(self, be, x0, cfg):
+        cfg = cfg or self.config
+        Bn = x0.shape[1]
+        x0, _ = be.arg(x0, (2, Bn), name="x0")
+        rho, U_old = be.empty(3 * cfg.N, Bn), be.empty(cfg.N, Bn)
+        self._call(be, "init", cfg, (), (Bn,), (x0, rho, U_old))
+        return rho, U_old
+
+    def _step(self, be, entry, x_k, rho, U_old, cfg, active_ws, opts=(), carried=_NONE, dual=False, out=None):
+        """The step* family.  ABI order: x_k, the in/out state (rho, U_old, then ``carried``),
+        the outputs (U, x_pred, x_next, y with x_hat, x_plan and u_applied with u_queue,
+        exitflag, inner_iters), active_ws, and step_dual's lambda and rho_qp.  In/out arguments
+        not in the ABI layout are staged and copied back; ``carried`` is echoed into the dict."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x_k.shape[1]
+        xk, _ = be.arg(x_k, (2, Bn), name="x_k")
+        state = [be.arg(rho, (3 * N, Bn), name="rho"), be.arg(U_old, (N, Bn), name="U_old")]
+        if carried:
+            state += self._carried_args(be, carried, opts, Bn)
+        state.append(_optional(be.arg, active_ws, (2 * (N + 1), Bn), be.i32, "active_ws"))
+        spec = [("U", (N, Bn)), ("x_pred", (2 * (N + 1), Bn)), ("x_next", (2, Bn))]
+        if "x_hat" in carried:
+            spec.append(("y", (2, Bn)))
+        if "u_queue" in carried:
+            spec += [("x_plan", (2, Bn)), ("u_applied", (Bn,))]
+        if out is None:
+            out = {k: be.empty(*shp) for k, shp in spec}
+            out["exitflag"], out["inner_iters"] = be.empty(Bn, dtype=be.i32), be.empty(Bn, dtype=be.i32)
+            if dual:
+                out["lambda"], out["rho_qp"] = be.empty(cfg.m, Bn), be.empty(3 * N, Bn)
+        else:
+            for k, shp in spec:
+                if tuple(out[k].shape) != shp or not is_scenario_major(out[k]):
+                    raise ValueError(f"out[{k!r}] must be a {shp} array from an earlier step()")
+        arrays = [xk, *[a for a, _ in state[:-1]], *[out[k] for k, _ in spec], out["exitflag"], out["inner_iters"],
+                  state[-1][0]]
+        if dual:
+            arrays += [out["lambda"] if cfg.m else None, out["rho_qp"]]
+        self._call(be, entry, cfg, opts, (Bn,), arrays)
+        for dst, (src, staged) in zip((rho, U_old, *carried.values(), active_ws), state):
+            if staged:
+                be.copy_back(dst, src)
+        if carried:
+            out.update(carried)
+        return out
+
+    def _run_out(self, be, k_sim, N, Bn, dk=False, est=False, dly=False):
+        """The closed loops' histories in the ABI's order (which is the dict's): xk, uk, Uk,
+        wpred, the observer's dk, the estimator's xhk and yk, the dead time's uak and xpk,
+        exitflag, inner_iters."""
+        mk = be.empty
+        out = {"xk": mk(2 * (k_sim + 1), Bn), "uk": mk(k_sim, Bn), "Uk": mk(N * k_sim, Bn),
+               "wpred": mk((N + 1) * k_sim, Bn)}
+        if dk:
+            out["dk"] = mk(2 * (k_sim + 1), Bn)
+        if est:
+            out.update(xhk=mk(2 * (k_sim + 1), Bn), yk=mk(2 * k_sim, Bn))
+        if dly:
+            out.update(uak=mk(k_sim, Bn), xpk=mk(2 * k_sim, Bn))
+        out.update(exitflag=mk(k_sim, Bn, dtype=be.i32), inner_iters=mk(k_sim, Bn, dtype=be.i32))
+        return out
+
+    def _run(self, be, entry, x0, k_sim, cfg, opts=(), init=_NONE):
+        """The run* family from x0.  ``init``: the optional initial d0, xhat0 (2, B) and uq0
+        (steps, B) by name, in the ABI's order; each brings its histories."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x0.shape[1]
+        ins = [be.arg(x0, (2, Bn), name="x0")[0]]
+        for n, a in init.items():
+            ins.append((_queue_arg(be, a, opts, Bn, n) if n == "uq0" else _optional(be.arg, a, (2, Bn), name=n))[0])
+        if "uq0" in init:
+            self._need_run_from()
+            self._need_input_delay("ntm_mpc_run_dly")
+        out = self._run_out(be, k_sim, N, Bn, dk="d0" in init, est="xhat0" in init, dly="uq0" in init)
+        self._call(be, entry, cfg, opts, (Bn, k_sim), (*ins, *out.values()))
+        return out
+
+    def _run_from(self, be, entry, x, rho, U_old, active_ws, k_sim, cfg, opts=(), carried=_NONE):
+        """The run*_from family: the carried state (x, rho, U_old, active_ws, then ``carried``)
+        goes in and out, staged and copied back where it is not in the ABI layout."""
+        cfg = cfg or self.config
+        N, Bn = cfg.N, x.shape[1]
+        state = [be.arg(x, (2, Bn), name="x"), be.arg(rho, (3 * N, Bn), name="rho"),
+                 be.arg(U_old, (N, Bn), name="U_old"), be.arg(active_ws, (2 * (N + 1), Bn), be.i32, "active_ws")]
+        state += self._carried_args(be, carried, opts, Bn)
+        self._need_run_from()
+        if "u_queue" in carried:
+            self._need_input_delay("ntm_mpc_run_dly")
+        out = self._run_out(be, k_sim, N, Bn, dk="d_hat" in carried, est="x_hat" in carried, dly="u_queue" in carried)
+        self._call(be, entry, cfg, opts, (Bn, k_sim), (*[a for a, _ in state], *out.values()))
+        for dst, (src, staged) in zip((x, rho, U_old, active_ws, *carried.values()), state):
+            if staged:
+                be.copy_back(dst, src)
+        return out
+
     # ------------------------------------------------------------ hot path
     def initial_state(self, x0: torch.Tensor, cfg: Config | None = None):
         """Rho = repmat(rho(x0), 1, N) (NTM_MPC_Sim.m:63-65); U_old = +inf (D14)."""
-        cfg = cfg or self.config
-        Bn = x0.shape[1]
-        x0, _ = _dev_arg(x0, (2, Bn), name="x0")
-        rho, U_old = self._empty(3 * cfg.N, Bn), self._empty(cfg.N, Bn)
-        self._raise(self.lib.ntm_mpc_init_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()), Bn,
-                                                 _ptr(x0), _ptr(rho), _ptr(U_old), self._stream()),
-                    "ntm_mpc_init_device")
-        return rho, U_old
+        return self._initial_state(self._dev, x0, cfg)
 
     def initial_state_host(self, x0: np.ndarray, cfg: Config | None = None):
         """ntm_mpc_init with host arrays (the MEX path)."""
-        cfg = cfg or self.config
-        Bn = x0.shape[1]
-        x0, _ = _host_arg(x0, (2, Bn), name="x0")
-        rho, U_old = _host_empty(3 * cfg.N, Bn), _host_empty(cfg.N, Bn)
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))          # noqa: E731
-        self._raise(self.lib.ntm_mpc_init(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()), Bn,
-                                          dp(x0), dp(rho), dp(U_old)), "ntm_mpc_init")
-        return rho, U_old
+        return self._initial_state(_HOST, x0, cfg)
 
     def new_active_ws(self, B: int, cfg: Config | None = None) -> torch.Tensor:
         """Empty warm-start workspace for step(..., active_ws=): (2(N+1), B) int32 of -1."""
@@ -394,46 +566,13 @@ class NtmMpc:
         starts (ntm_mpc_step_ws_device).  Returns dict U, x_pred, x_next,
         exitflag, inner_iters (all CUDA tensors); ``out`` (a dict this method
         returned earlier) is reused."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x_k.shape[1]
-        xk, _ = _dev_arg(x_k, (2, Bn), name="x_k")
-        rh, rho_st = _dev_arg(rho, (3 * N, Bn), name="rho")
-        uo, uo_st = _dev_arg(U_old, (N, Bn), name="U_old")
-        ws, ws_st = (None, False) if active_ws is None else _dev_arg(active_ws, (2 * (N + 1), Bn), torch.int32,
-                                                                     "active_ws")
-        if out is None:
-            out = {"U": self._empty(N, Bn), "x_pred": self._empty(2 * (N + 1), Bn), "x_next": self._empty(2, Bn),
-                   "exitflag": self._empty(Bn, dtype=torch.int32), "inner_iters": self._empty(Bn, dtype=torch.int32)}
-        else:
-            for k, shp in (("U", (N, Bn)), ("x_pred", (2 * (N + 1), Bn)), ("x_next", (2, Bn))):
-                if tuple(out[k].shape) != shp or not is_scenario_major(out[k]):
-                    raise ValueError(f"out[{k!r}] must be a {shp} array from an earlier step()")
-        rc = self.lib.ntm_mpc_step_ws_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()), Bn,
-                                             _ptr(xk), _ptr(rh), _ptr(uo), _ptr(out["U"]), _ptr(out["x_pred"]),
-                                             _ptr(out["x_next"]), _ptr(out["exitflag"]), _ptr(out["inner_iters"]),
-                                             _ptr(ws), self._stream())
-        self._raise(rc, "ntm_mpc_step_ws_device")
-        for staged, dst, src in ((rho_st, rho, rh), (uo_st, U_old, uo), (ws_st, active_ws, ws)):
-            if staged:
-                dst.copy_(src)
-        return out
+        return self._step(self._dev, "step_ws", x_k, rho, U_old, cfg, active_ws, out=out)
 
     def run(self, x0: torch.Tensor, k_sim: int = 20, cfg: Config | None = None):
         """Closed loop NTM_MPC_Sim.m:80-131 on device.  Returns the workspace
         variables xk (2(k_sim+1), B), uk (k_sim, B), Uk (N k_sim, B), wpred
         ((N+1) k_sim, B), exitflag / inner_iters (k_sim, B)."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x0.shape[1]
-        x0, _ = _dev_arg(x0, (2, Bn), name="x0")
-        out = {"xk": self._empty(2 * (k_sim + 1), Bn), "uk": self._empty(k_sim, Bn), "Uk": self._empty(N * k_sim, Bn),
-               "wpred": self._empty((N + 1) * k_sim, Bn), "exitflag": self._empty(k_sim, Bn, dtype=torch.int32),
-               "inner_iters": self._empty(k_sim, Bn, dtype=torch.int32)}
-        rc = self.lib.ntm_mpc_run_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()), Bn, k_sim,
-                                         _ptr(x0), _ptr(out["xk"]), _ptr(out["uk"]), _ptr(out["Uk"]),
-                                         _ptr(out["wpred"]), _ptr(out["exitflag"]), _ptr(out["inner_iters"]),
-                                         self._stream())
-        self._raise(rc, "ntm_mpc_run_device")
-        return out
+        return self._run(self._dev, "run", x0, k_sim, cfg)
 
     # ------------------------------------------------------------ host-buffer entry points (the MEX path)
     def step_host(self, x_k: np.ndarray, rho: np.ndarray, U_old: np.ndarray, cfg: Config | None = None,
@@ -441,41 +580,11 @@ class NtmMpc:
         """ntm_mpc_step with host (NumPy fp64) arrays, as a MEX gateway calls it:
         the library stages through its own device buffers.  ``rho`` and
         ``U_old`` (and ``active_ws``) are updated in place."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x_k.shape[1]
-        xk, _ = _host_arg(x_k, (2, Bn), name="x_k")
-        rh, rho_st = _host_arg(rho, (3 * N, Bn), name="rho")
-        uo, uo_st = _host_arg(U_old, (N, Bn), name="U_old")
-        ws, ws_st = (None, False) if active_ws is None else _host_arg(active_ws, (2 * (N + 1), Bn), np.int32,
-                                                                      "active_ws")
-        out = {"U": _host_empty(N, Bn), "x_pred": _host_empty(2 * (N + 1), Bn), "x_next": _host_empty(2, Bn),
-               "exitflag": np.empty(Bn, np.int32), "inner_iters": np.empty(Bn, np.int32)}
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))          # noqa: E731
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))           # noqa: E731
-        rc = self.lib.ntm_mpc_step_ws(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()), Bn, dp(xk),
-                                      dp(rh), dp(uo), dp(out["U"]), dp(out["x_pred"]), dp(out["x_next"]),
-                                      ip(out["exitflag"]), ip(out["inner_iters"]), None if ws is None else ip(ws))
-        self._raise(rc, "ntm_mpc_step_ws")
-        for staged, dst, src in ((rho_st, rho, rh), (uo_st, U_old, uo), (ws_st, active_ws, ws)):
-            if staged:
-                dst[...] = src
-        return out
+        return self._step(_HOST, "step_ws", x_k, rho, U_old, cfg, active_ws)
 
     def run_host(self, x0: np.ndarray, k_sim: int = 20, cfg: Config | None = None):
         """ntm_mpc_run with host arrays (NTM_MPC_Sim.m:80-131 for a batch)."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x0.shape[1]
-        x0, _ = _host_arg(x0, (2, Bn), name="x0")
-        out = {"xk": _host_empty(2 * (k_sim + 1), Bn), "uk": _host_empty(k_sim, Bn),
-               "Uk": _host_empty(N * k_sim, Bn), "wpred": _host_empty((N + 1) * k_sim, Bn),
-               "exitflag": _host_empty(k_sim, Bn, dtype=np.int32), "inner_iters": _host_empty(k_sim, Bn, dtype=np.int32)}
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))          # noqa: E731
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))           # noqa: E731
-        rc = self.lib.ntm_mpc_run(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()), Bn, k_sim, dp(x0),
-                                  dp(out["xk"]), dp(out["uk"]), dp(out["Uk"]), dp(out["wpred"]),
-                                  ip(out["exitflag"]), ip(out["inner_iters"]))
-        self._raise(rc, "ntm_mpc_run")
-        return out
+        return self._run(_HOST, "run", x0, k_sim, cfg)
 
     # ------------------------------------------------------------ function level
     def rho(self, x: torch.Tensor, cfg: Config | None = None, physics: Physics | None = None):
@@ -532,27 +641,6 @@ class NtmMpc:
                     "ntm_getwlc_device")
         return W, Lm, c
 
-    def quadprog(self, H: torch.Tensor, f: torch.Tensor, Lin: torch.Tensor | None, b: torch.Tensor | None):
-        """quadprog(H, f, A, b) for a batch: min 1/2 U'HU + f'U s.t. Lin U <= b.
-        H (N*N, B), f (N, B), Lin (m*N, B) column-major per scenario, b (m, B).
-        Returns (U (N, B), exitflag (B,), iterations (B,)); exitflag as quadprog
-        (1 optimal, 0 max iterations, -2 infeasible -> U = 0, -7 non-finite)."""
-        N, Bn = f.shape
-        m = 0 if Lin is None else b.shape[0]
-        H, _ = _dev_arg(H, (N * N, Bn), name="H")
-        f, _ = _dev_arg(f, (N, Bn), name="f")
-        if m:
-            Lin, _ = _dev_arg(Lin, (m * N, Bn), name="A")
-            b, _ = _dev_arg(b, (m, Bn), name="b")
-        U = self._empty(N, Bn)
-        flag = self._empty(Bn, dtype=torch.int32)
-        its = self._empty(Bn, dtype=torch.int32)
-        self._raise(self.lib.ntm_qp_device(self._ctx, Bn, N, m, _ptr(H), _ptr(f), _ptr(Lin) if m else None,
-                                           _ptr(b) if m else None, _ptr(U), _ptr(flag), _ptr(its), self._stream()),
-                    "ntm_qp_device")
-        return U, flag, its
-
-    # ------------------------------------------------------------ multipliers and the KKT audit
     def _qp_args(self, H, f, Lin, b):
         N, Bn = f.shape
         m = 0 if Lin is None else b.shape[0]
@@ -563,6 +651,34 @@ class NtmMpc:
             b, _ = _dev_arg(b, (m, Bn), name="b")
         return N, Bn, m, H, f, (Lin if m else None), (b if m else None)
 
+    def quadprog(self, H: torch.Tensor, f: torch.Tensor, Lin: torch.Tensor | None, b: torch.Tensor | None):
+        """quadprog(H, f, A, b) for a batch: min 1/2 U'HU + f'U s.t. Lin U <= b.
+        H (N*N, B), f (N, B), Lin (m*N, B) column-major per scenario, b (m, B).
+        Returns (U (N, B), exitflag (B,), iterations (B,)); exitflag as quadprog
+        (1 optimal, 0 max iterations, -2 infeasible -> U = 0, -7 non-finite)."""
+        N, Bn, m, H, f, Lin, b = self._qp_args(H, f, Lin, b)
+        U = self._empty(N, Bn)
+        flag = self._empty(Bn, dtype=torch.int32)
+        its = self._empty(Bn, dtype=torch.int32)
+        self._raise(self.lib.ntm_qp_device(self._ctx, Bn, N, m, _ptr(H), _ptr(f), _ptr(Lin), _ptr(b), _ptr(U),
+                                           _ptr(flag), _ptr(its), self._stream()), "ntm_qp_device")
+        return U, flag, its
+
+    def quadprog_mixed(self, H: torch.Tensor, f: torch.Tensor, Lin: torch.Tensor | None, b: torch.Tensor | None):
+        """Config 5's fp32 leg (ntm_qp_mixed_device; not the fp64 product path): the QP
+        solved in fp32 on fp32-rounded data, its active set then re-solved exactly in
+        fp64 and certified (fp64 fallback otherwise).  Returns (U refined (N, B),
+        U32 fp32 solution (N, B), exitflag (B,), info (B,) bit 0 certified / bit 1
+        fp64 fallback / bit 2 fp32 not optimal, fp32 GI iterations (B,))."""
+        N, Bn, m, H, f, Lin, b = self._qp_args(H, f, Lin, b)
+        U, U32 = self._empty(N, Bn), self._empty(N, Bn)
+        flag, info, its = (self._empty(Bn, dtype=torch.int32) for _ in range(3))
+        self._raise(self.lib.ntm_qp_mixed_device(self._ctx, Bn, N, m, _ptr(H), _ptr(f), _ptr(Lin), _ptr(b), _ptr(U),
+                                                 _ptr(U32), _ptr(flag), _ptr(info), _ptr(its), self._stream()),
+                    "ntm_qp_mixed_device")
+        return U, U32, flag, info, its
+
+    # ------------------------------------------------------------ multipliers and the KKT audit
     def quadprog_dual(self, H: torch.Tensor, f: torch.Tensor, Lin: torch.Tensor | None, b: torch.Tensor | None):
         """[x, fval, exitflag, output, lambda] = quadprog(H, f, A, b) for a batch
         (ntm_qp_dual_device).  Returns (U (N, B), fval (B,), exitflag (B,),
@@ -601,52 +717,13 @@ class NtmMpc:
         ``rho_qp`` (3N, B): the scheduling rho that QP was built from
         (ntm_mpc_step_dual_device).  Every horizon runs on the runtime-N kernels
         here, so U agrees with step() to the parity tolerances, not bit for bit."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x_k.shape[1]
-        xk, _ = _dev_arg(x_k, (2, Bn), name="x_k")
-        rh, rho_st = _dev_arg(rho, (3 * N, Bn), name="rho")
-        uo, uo_st = _dev_arg(U_old, (N, Bn), name="U_old")
-        ws, ws_st = (None, False) if active_ws is None else _dev_arg(active_ws, (2 * (N + 1), Bn), torch.int32,
-                                                                     "active_ws")
-        out = {"U": self._empty(N, Bn), "x_pred": self._empty(2 * (N + 1), Bn), "x_next": self._empty(2, Bn),
-               "exitflag": self._empty(Bn, dtype=torch.int32), "inner_iters": self._empty(Bn, dtype=torch.int32),
-               "lambda": self._empty(cfg.m, Bn), "rho_qp": self._empty(3 * N, Bn)}
-        rc = self.lib.ntm_mpc_step_dual_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()), Bn,
-                                               _ptr(xk), _ptr(rh), _ptr(uo), _ptr(out["U"]), _ptr(out["x_pred"]),
-                                               _ptr(out["x_next"]), _ptr(out["exitflag"]), _ptr(out["inner_iters"]),
-                                               _ptr(ws), _ptr(out["lambda"]) if cfg.m else None, _ptr(out["rho_qp"]),
-                                               self._stream())
-        self._raise(rc, "ntm_mpc_step_dual_device")
-        for staged, dst, src in ((rho_st, rho, rh), (uo_st, U_old, uo), (ws_st, active_ws, ws)):
-            if staged:
-                dst.copy_(src)
-        return out
+        return self._step(self._dev, "step_dual", x_k, rho, U_old, cfg, active_ws, dual=True)
 
     def step_dual_host(self, x_k: np.ndarray, rho: np.ndarray, U_old: np.ndarray, cfg: Config | None = None,
                        active_ws: np.ndarray | None = None):
         """ntm_mpc_step_dual with host arrays (the MEX path): step_host plus ``lambda``
         and ``rho_qp``."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x_k.shape[1]
-        xk, _ = _host_arg(x_k, (2, Bn), name="x_k")
-        rh, rho_st = _host_arg(rho, (3 * N, Bn), name="rho")
-        uo, uo_st = _host_arg(U_old, (N, Bn), name="U_old")
-        ws, ws_st = (None, False) if active_ws is None else _host_arg(active_ws, (2 * (N + 1), Bn), np.int32,
-                                                                      "active_ws")
-        out = {"U": _host_empty(N, Bn), "x_pred": _host_empty(2 * (N + 1), Bn), "x_next": _host_empty(2, Bn),
-               "exitflag": np.empty(Bn, np.int32), "inner_iters": np.empty(Bn, np.int32),
-               "lambda": _host_empty(cfg.m, Bn), "rho_qp": _host_empty(3 * N, Bn)}
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))          # noqa: E731
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))           # noqa: E731
-        rc = self.lib.ntm_mpc_step_dual(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()), Bn, dp(xk),
-                                        dp(rh), dp(uo), dp(out["U"]), dp(out["x_pred"]), dp(out["x_next"]),
-                                        ip(out["exitflag"]), ip(out["inner_iters"]), None if ws is None else ip(ws),
-                                        dp(out["lambda"]) if cfg.m else None, dp(out["rho_qp"]))
-        self._raise(rc, "ntm_mpc_step_dual")
-        for staged, dst, src in ((rho_st, rho, rh), (uo_st, U_old, uo), (ws_st, active_ws, ws)):
-            if staged:
-                dst[...] = src
-        return out
+        return self._step(_HOST, "step_dual", x_k, rho, U_old, cfg, active_ws, dual=True)
 
     # ------------------------------------------------------------ plant-model mismatch, disturbance estimate
     def step_obs(self, x_k: torch.Tensor, rho: torch.Tensor, U_old: torch.Tensor, d_hat: torch.Tensor,
@@ -656,96 +733,25 @@ class NtmMpc:
         ``d_hat`` (2, B), which is updated in place like ``rho`` and ``U_old`` and
         also returned as ``d_hat`` in the dict.  Every horizon runs on the runtime-N
         kernels here, as for step_dual."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x_k.shape[1]
-        xk, _ = _dev_arg(x_k, (2, Bn), name="x_k")
-        rh, rho_st = _dev_arg(rho, (3 * N, Bn), name="rho")
-        uo, uo_st = _dev_arg(U_old, (N, Bn), name="U_old")
-        dh, dh_st = _dev_arg(d_hat, (2, Bn), name="d_hat")
-        ws, ws_st = (None, False) if active_ws is None else _dev_arg(active_ws, (2 * (N + 1), Bn), torch.int32,
-                                                                     "active_ws")
-        out = {"U": self._empty(N, Bn), "x_pred": self._empty(2 * (N + 1), Bn), "x_next": self._empty(2, Bn),
-               "exitflag": self._empty(Bn, dtype=torch.int32), "inner_iters": self._empty(Bn, dtype=torch.int32)}
-        rc = self.lib.ntm_mpc_step_obs_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
-                                              C.byref(obs.to_c()), Bn, _ptr(xk), _ptr(rh), _ptr(uo), _ptr(dh),
-                                              _ptr(out["U"]), _ptr(out["x_pred"]), _ptr(out["x_next"]),
-                                              _ptr(out["exitflag"]), _ptr(out["inner_iters"]), _ptr(ws),
-                                              self._stream())
-        self._raise(rc, "ntm_mpc_step_obs_device")
-        for staged, dst, src in ((rho_st, rho, rh), (uo_st, U_old, uo), (dh_st, d_hat, dh), (ws_st, active_ws, ws)):
-            if staged:
-                dst.copy_(src)
-        out["d_hat"] = d_hat
-        return out
+        return self._step(self._dev, "step_obs", x_k, rho, U_old, cfg, active_ws, (obs,), {"d_hat": d_hat})
 
     def step_obs_host(self, x_k: np.ndarray, rho: np.ndarray, U_old: np.ndarray, d_hat: np.ndarray, obs: Observer,
                       cfg: Config | None = None, active_ws: np.ndarray | None = None):
         """ntm_mpc_step_obs with host arrays (the MEX path): step_host with the observer;
         ``d_hat`` (2, B) is updated in place and returned as ``d_hat``."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x_k.shape[1]
-        xk, _ = _host_arg(x_k, (2, Bn), name="x_k")
-        rh, rho_st = _host_arg(rho, (3 * N, Bn), name="rho")
-        uo, uo_st = _host_arg(U_old, (N, Bn), name="U_old")
-        dh, dh_st = _host_arg(d_hat, (2, Bn), name="d_hat")
-        ws, ws_st = (None, False) if active_ws is None else _host_arg(active_ws, (2 * (N + 1), Bn), np.int32,
-                                                                      "active_ws")
-        out = {"U": _host_empty(N, Bn), "x_pred": _host_empty(2 * (N + 1), Bn), "x_next": _host_empty(2, Bn),
-               "exitflag": np.empty(Bn, np.int32), "inner_iters": np.empty(Bn, np.int32)}
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))          # noqa: E731
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))           # noqa: E731
-        rc = self.lib.ntm_mpc_step_obs(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
-                                       C.byref(obs.to_c()), Bn, dp(xk), dp(rh), dp(uo), dp(dh), dp(out["U"]),
-                                       dp(out["x_pred"]), dp(out["x_next"]), ip(out["exitflag"]),
-                                       ip(out["inner_iters"]), None if ws is None else ip(ws))
-        self._raise(rc, "ntm_mpc_step_obs")
-        for staged, dst, src in ((rho_st, rho, rh), (uo_st, U_old, uo), (dh_st, d_hat, dh), (ws_st, active_ws, ws)):
-            if staged:
-                dst[...] = src
-        out["d_hat"] = d_hat
-        return out
+        return self._step(_HOST, "step_obs", x_k, rho, U_old, cfg, active_ws, (obs,), {"d_hat": d_hat})
 
     def run_obs(self, x0: torch.Tensor, obs: Observer, k_sim: int = 20, cfg: Config | None = None,
                 d0: torch.Tensor | None = None):
         """run() with the observer (ntm_mpc_run_obs_device), d_hat kept on chip.  ``d0``
         (2, B) is the initial estimate (None: zeros).  Returns run()'s dict plus ``dk``
         (2(k_sim+1), B): column 0 is d0, column k+1 the estimate after step k."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x0.shape[1]
-        x0, _ = _dev_arg(x0, (2, Bn), name="x0")
-        if d0 is not None:
-            d0, _ = _dev_arg(d0, (2, Bn), name="d0")
-        out = {"xk": self._empty(2 * (k_sim + 1), Bn), "uk": self._empty(k_sim, Bn), "Uk": self._empty(N * k_sim, Bn),
-               "wpred": self._empty((N + 1) * k_sim, Bn), "dk": self._empty(2 * (k_sim + 1), Bn),
-               "exitflag": self._empty(k_sim, Bn, dtype=torch.int32),
-               "inner_iters": self._empty(k_sim, Bn, dtype=torch.int32)}
-        rc = self.lib.ntm_mpc_run_obs_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
-                                             C.byref(obs.to_c()), Bn, k_sim, _ptr(x0), _ptr(d0), _ptr(out["xk"]),
-                                             _ptr(out["uk"]), _ptr(out["Uk"]), _ptr(out["wpred"]), _ptr(out["dk"]),
-                                             _ptr(out["exitflag"]), _ptr(out["inner_iters"]), self._stream())
-        self._raise(rc, "ntm_mpc_run_obs_device")
-        return out
+        return self._run(self._dev, "run_obs", x0, k_sim, cfg, (obs,), {"d0": d0})
 
     def run_obs_host(self, x0: np.ndarray, obs: Observer, k_sim: int = 20, cfg: Config | None = None,
                      d0: np.ndarray | None = None):
         """ntm_mpc_run_obs with host arrays: run_host with the observer, plus ``dk``."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x0.shape[1]
-        x0, _ = _host_arg(x0, (2, Bn), name="x0")
-        if d0 is not None:
-            d0, _ = _host_arg(d0, (2, Bn), name="d0")
-        out = {"xk": _host_empty(2 * (k_sim + 1), Bn), "uk": _host_empty(k_sim, Bn),
-               "Uk": _host_empty(N * k_sim, Bn), "wpred": _host_empty((N + 1) * k_sim, Bn),
-               "dk": _host_empty(2 * (k_sim + 1), Bn),
-               "exitflag": _host_empty(k_sim, Bn, dtype=np.int32), "inner_iters": _host_empty(k_sim, Bn, dtype=np.int32)}
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))          # noqa: E731
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))           # noqa: E731
-        rc = self.lib.ntm_mpc_run_obs(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
-                                      C.byref(obs.to_c()), Bn, k_sim, dp(x0), None if d0 is None else dp(d0),
-                                      dp(out["xk"]), dp(out["uk"]), dp(out["Uk"]), dp(out["wpred"]), dp(out["dk"]),
-                                      ip(out["exitflag"]), ip(out["inner_iters"]))
-        self._raise(rc, "ntm_mpc_run_obs")
-        return out
+        return self._run(_HOST, "run_obs", x0, k_sim, cfg, (obs,), {"d0": d0})
 
     # ------------------------------------------------------------ measurement noise, filtered state estimate
     def step_est(self, x_k: torch.Tensor, rho: torch.Tensor, U_old: torch.Tensor, d_hat: torch.Tensor,
@@ -755,60 +761,16 @@ class NtmMpc:
         from the estimate ``x_hat`` (2, B) while the plant steps from its true state
         ``x_k``; ``x_hat`` and ``d_hat`` are updated in place from the noisy measurement
         ``y`` of ``x_next`` and are also returned in the dict, with ``y``."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x_k.shape[1]
-        xk, _ = _dev_arg(x_k, (2, Bn), name="x_k")
-        rh, rho_st = _dev_arg(rho, (3 * N, Bn), name="rho")
-        uo, uo_st = _dev_arg(U_old, (N, Bn), name="U_old")
-        dh, dh_st = _dev_arg(d_hat, (2, Bn), name="d_hat")
-        xh, xh_st = _dev_arg(x_hat, (2, Bn), name="x_hat")
-        ws, ws_st = (None, False) if active_ws is None else _dev_arg(active_ws, (2 * (N + 1), Bn), torch.int32,
-                                                                     "active_ws")
-        out = {"U": self._empty(N, Bn), "x_pred": self._empty(2 * (N + 1), Bn), "x_next": self._empty(2, Bn),
-               "y": self._empty(2, Bn), "exitflag": self._empty(Bn, dtype=torch.int32),
-               "inner_iters": self._empty(Bn, dtype=torch.int32)}
-        rc = self.lib.ntm_mpc_step_est_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
-                                              C.byref(est.to_c()), Bn, _ptr(xk), _ptr(rh), _ptr(uo), _ptr(dh),
-                                              _ptr(xh), _ptr(out["U"]), _ptr(out["x_pred"]), _ptr(out["x_next"]),
-                                              _ptr(out["y"]), _ptr(out["exitflag"]), _ptr(out["inner_iters"]),
-                                              _ptr(ws), self._stream())
-        self._raise(rc, "ntm_mpc_step_est_device")
-        for staged, dst, src in ((rho_st, rho, rh), (uo_st, U_old, uo), (dh_st, d_hat, dh), (xh_st, x_hat, xh),
-                                 (ws_st, active_ws, ws)):
-            if staged:
-                dst.copy_(src)
-        out["d_hat"], out["x_hat"] = d_hat, x_hat
-        return out
+        return self._step(self._dev, "step_est", x_k, rho, U_old, cfg, active_ws, (est,),
+                          {"d_hat": d_hat, "x_hat": x_hat})
 
     def step_est_host(self, x_k: np.ndarray, rho: np.ndarray, U_old: np.ndarray, d_hat: np.ndarray,
                       x_hat: np.ndarray, est: Estimator, cfg: Config | None = None,
                       active_ws: np.ndarray | None = None):
         """ntm_mpc_step_est with host arrays (the MEX path): ``d_hat`` and ``x_hat`` (2, B)
         are updated in place and returned in the dict, with the measurement ``y``."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x_k.shape[1]
-        xk, _ = _host_arg(x_k, (2, Bn), name="x_k")
-        rh, rho_st = _host_arg(rho, (3 * N, Bn), name="rho")
-        uo, uo_st = _host_arg(U_old, (N, Bn), name="U_old")
-        dh, dh_st = _host_arg(d_hat, (2, Bn), name="d_hat")
-        xh, xh_st = _host_arg(x_hat, (2, Bn), name="x_hat")
-        ws, ws_st = (None, False) if active_ws is None else _host_arg(active_ws, (2 * (N + 1), Bn), np.int32,
-                                                                      "active_ws")
-        out = {"U": _host_empty(N, Bn), "x_pred": _host_empty(2 * (N + 1), Bn), "x_next": _host_empty(2, Bn),
-               "y": _host_empty(2, Bn), "exitflag": np.empty(Bn, np.int32), "inner_iters": np.empty(Bn, np.int32)}
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))          # noqa: E731
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))           # noqa: E731
-        rc = self.lib.ntm_mpc_step_est(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
-                                       C.byref(est.to_c()), Bn, dp(xk), dp(rh), dp(uo), dp(dh), dp(xh), dp(out["U"]),
-                                       dp(out["x_pred"]), dp(out["x_next"]), dp(out["y"]), ip(out["exitflag"]),
-                                       ip(out["inner_iters"]), None if ws is None else ip(ws))
-        self._raise(rc, "ntm_mpc_step_est")
-        for staged, dst, src in ((rho_st, rho, rh), (uo_st, U_old, uo), (dh_st, d_hat, dh), (xh_st, x_hat, xh),
-                                 (ws_st, active_ws, ws)):
-            if staged:
-                dst[...] = src
-        out["d_hat"], out["x_hat"] = d_hat, x_hat
-        return out
+        return self._step(_HOST, "step_est", x_k, rho, U_old, cfg, active_ws, (est,),
+                          {"d_hat": d_hat, "x_hat": x_hat})
 
     def run_est(self, x0: torch.Tensor, est: Estimator, k_sim: int = 20, cfg: Config | None = None,
                 d0: torch.Tensor | None = None, xhat0: torch.Tensor | None = None):
@@ -816,69 +778,15 @@ class NtmMpc:
         on chip.  ``xhat0`` (2, B) is the initial estimate (None: x0).  Returns run_obs()'s
         dict plus ``xhk`` (2(k_sim+1), B), column 0 the initial estimate, and ``yk``
         (2 k_sim, B), the measurements."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x0.shape[1]
-        x0, _ = _dev_arg(x0, (2, Bn), name="x0")
-        if d0 is not None:
-            d0, _ = _dev_arg(d0, (2, Bn), name="d0")
-        if xhat0 is not None:
-            xhat0, _ = _dev_arg(xhat0, (2, Bn), name="xhat0")
-        out = {"xk": self._empty(2 * (k_sim + 1), Bn), "uk": self._empty(k_sim, Bn), "Uk": self._empty(N * k_sim, Bn),
-               "wpred": self._empty((N + 1) * k_sim, Bn), "dk": self._empty(2 * (k_sim + 1), Bn),
-               "xhk": self._empty(2 * (k_sim + 1), Bn), "yk": self._empty(2 * k_sim, Bn),
-               "exitflag": self._empty(k_sim, Bn, dtype=torch.int32),
-               "inner_iters": self._empty(k_sim, Bn, dtype=torch.int32)}
-        rc = self.lib.ntm_mpc_run_est_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
-                                             C.byref(est.to_c()), Bn, k_sim, _ptr(x0), _ptr(d0), _ptr(xhat0),
-                                             _ptr(out["xk"]), _ptr(out["uk"]), _ptr(out["Uk"]), _ptr(out["wpred"]),
-                                             _ptr(out["dk"]), _ptr(out["xhk"]), _ptr(out["yk"]),
-                                             _ptr(out["exitflag"]), _ptr(out["inner_iters"]), self._stream())
-        self._raise(rc, "ntm_mpc_run_est_device")
-        return out
+        return self._run(self._dev, "run_est", x0, k_sim, cfg, (est,), {"d0": d0, "xhat0": xhat0})
 
     def run_est_host(self, x0: np.ndarray, est: Estimator, k_sim: int = 20, cfg: Config | None = None,
                      d0: np.ndarray | None = None, xhat0: np.ndarray | None = None):
         """ntm_mpc_run_est with host arrays: run_obs_host with the estimator, plus ``xhk``
         and ``yk``."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x0.shape[1]
-        x0, _ = _host_arg(x0, (2, Bn), name="x0")
-        if d0 is not None:
-            d0, _ = _host_arg(d0, (2, Bn), name="d0")
-        if xhat0 is not None:
-            xhat0, _ = _host_arg(xhat0, (2, Bn), name="xhat0")
-        out = {"xk": _host_empty(2 * (k_sim + 1), Bn), "uk": _host_empty(k_sim, Bn),
-               "Uk": _host_empty(N * k_sim, Bn), "wpred": _host_empty((N + 1) * k_sim, Bn),
-               "dk": _host_empty(2 * (k_sim + 1), Bn), "xhk": _host_empty(2 * (k_sim + 1), Bn),
-               "yk": _host_empty(2 * k_sim, Bn),
-               "exitflag": _host_empty(k_sim, Bn, dtype=np.int32), "inner_iters": _host_empty(k_sim, Bn, dtype=np.int32)}
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))          # noqa: E731
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))           # noqa: E731
-        nul = lambda a: None if a is None else dp(a)                    # noqa: E731
-        rc = self.lib.ntm_mpc_run_est(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
-                                      C.byref(est.to_c()), Bn, k_sim, dp(x0), nul(d0), nul(xhat0), dp(out["xk"]),
-                                      dp(out["uk"]), dp(out["Uk"]), dp(out["wpred"]), dp(out["dk"]), dp(out["xhk"]),
-                                      dp(out["yk"]), ip(out["exitflag"]), ip(out["inner_iters"]))
-        self._raise(rc, "ntm_mpc_run_est")
-        return out
+        return self._run(_HOST, "run_est", x0, k_sim, cfg, (est,), {"d0": d0, "xhat0": xhat0})
 
     # ------------------------------------------------------------ resumable closed loops
-    def _run_out(self, k_sim, N, Bn, est=False, host=False, dly=False):
-        if not L.has_run_from(self.lib):
-            raise NtmLibraryError("this build of the library has no ntm_mpc_run_from (NTM_MPC_HAS_RUN_FROM)")
-        if dly and not L.has_input_delay(self.lib):
-            raise NtmLibraryError("this build of the library has no ntm_mpc_run_dly (NTM_MPC_HAS_INPUT_DELAY)")
-        mk = _host_empty if host else self._empty
-        i32 = np.int32 if host else torch.int32
-        out = {"xk": mk(2 * (k_sim + 1), Bn), "uk": mk(k_sim, Bn), "Uk": mk(N * k_sim, Bn),
-               "wpred": mk((N + 1) * k_sim, Bn)}
-        if est:
-            out.update(dk=mk(2 * (k_sim + 1), Bn), xhk=mk(2 * (k_sim + 1), Bn), yk=mk(2 * k_sim, Bn))
-        if dly:
-            out.update(uak=mk(k_sim, Bn), xpk=mk(2 * k_sim, Bn))
-        out.update(exitflag=mk(k_sim, Bn, dtype=i32), inner_iters=mk(k_sim, Bn, dtype=i32))
-        return out
-
     def run_from(self, x: torch.Tensor, rho: torch.Tensor, U_old: torch.Tensor, active_ws: torch.Tensor,
                  k_sim: int = 20, cfg: Config | None = None):
         """run() from a carried state (ntm_mpc_run_from_device): ``x`` (2, B), ``rho``
@@ -888,39 +796,13 @@ class NtmMpc:
         first call takes initial_state() and new_active_ws().  An attached generator's
         ``k0`` is the caller's to advance between calls.  Returns run()'s dict; xk's
         column 0 is the input ``x``."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x.shape[1]
-        state = [_dev_arg(x, (2, Bn), name="x"), _dev_arg(rho, (3 * N, Bn), name="rho"),
-                 _dev_arg(U_old, (N, Bn), name="U_old"),
-                 _dev_arg(active_ws, (2 * (N + 1), Bn), torch.int32, "active_ws")]
-        out = self._run_out(k_sim, N, Bn)
-        rc = self.lib.ntm_mpc_run_from_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()), Bn, k_sim,
-                                              *[_ptr(a) for a, _ in state], *[_ptr(v) for v in out.values()],
-                                              self._stream())
-        self._raise(rc, "ntm_mpc_run_from_device")
-        for dst, (src, staged) in zip((x, rho, U_old, active_ws), state):
-            if staged:
-                dst.copy_(src)
-        return out
+        return self._run_from(self._dev, "run_from", x, rho, U_old, active_ws, k_sim, cfg)
 
     def run_from_host(self, x: np.ndarray, rho: np.ndarray, U_old: np.ndarray, active_ws: np.ndarray,
                       k_sim: int = 20, cfg: Config | None = None):
         """ntm_mpc_run_from with host arrays (the MEX path); the state arrays are
         updated in place."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x.shape[1]
-        state = [_host_arg(x, (2, Bn), name="x"), _host_arg(rho, (3 * N, Bn), name="rho"),
-                 _host_arg(U_old, (N, Bn), name="U_old"),
-                 _host_arg(active_ws, (2 * (N + 1), Bn), np.int32, "active_ws")]
-        out = self._run_out(k_sim, N, Bn, host=True)
-        hp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32 if a.dtype == np.int32 else C.c_double))  # noqa: E731
-        rc = self.lib.ntm_mpc_run_from(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()), Bn, k_sim,
-                                       *[hp(a) for a, _ in state], *[hp(v) for v in out.values()])
-        self._raise(rc, "ntm_mpc_run_from")
-        for dst, (src, staged) in zip((x, rho, U_old, active_ws), state):
-            if staged:
-                dst[...] = src
-        return out
+        return self._run_from(_HOST, "run_from", x, rho, U_old, active_ws, k_sim, cfg)
 
     def run_est_from(self, x: torch.Tensor, rho: torch.Tensor, U_old: torch.Tensor, active_ws: torch.Tensor,
                      d_hat: torch.Tensor, x_hat: torch.Tensor, est: Estimator, k_sim: int = 20,
@@ -929,51 +811,17 @@ class NtmMpc:
         the estimator's ``d_hat`` and ``x_hat`` (2, B) carried too, all updated in place.
         With sigma_y = 0, kappa = 0, equal gains and x_hat == x it continues run_obs()
         bit for bit.  Returns run_est()'s dict."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x.shape[1]
-        state = [_dev_arg(x, (2, Bn), name="x"), _dev_arg(rho, (3 * N, Bn), name="rho"),
-                 _dev_arg(U_old, (N, Bn), name="U_old"),
-                 _dev_arg(active_ws, (2 * (N + 1), Bn), torch.int32, "active_ws"),
-                 _dev_arg(d_hat, (2, Bn), name="d_hat"), _dev_arg(x_hat, (2, Bn), name="x_hat")]
-        out = self._run_out(k_sim, N, Bn, est=True)
-        rc = self.lib.ntm_mpc_run_est_from_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
-                                                  C.byref(est.to_c()), Bn, k_sim, *[_ptr(a) for a, _ in state],
-                                                  *[_ptr(v) for v in out.values()], self._stream())
-        self._raise(rc, "ntm_mpc_run_est_from_device")
-        for dst, (src, staged) in zip((x, rho, U_old, active_ws, d_hat, x_hat), state):
-            if staged:
-                dst.copy_(src)
-        return out
+        return self._run_from(self._dev, "run_est_from", x, rho, U_old, active_ws, k_sim, cfg, (est,),
+                              {"d_hat": d_hat, "x_hat": x_hat})
 
     def run_est_from_host(self, x: np.ndarray, rho: np.ndarray, U_old: np.ndarray, active_ws: np.ndarray,
                           d_hat: np.ndarray, x_hat: np.ndarray, est: Estimator, k_sim: int = 20,
                           cfg: Config | None = None):
         """ntm_mpc_run_est_from with host arrays; the state arrays are updated in place."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x.shape[1]
-        state = [_host_arg(x, (2, Bn), name="x"), _host_arg(rho, (3 * N, Bn), name="rho"),
-                 _host_arg(U_old, (N, Bn), name="U_old"),
-                 _host_arg(active_ws, (2 * (N + 1), Bn), np.int32, "active_ws"),
-                 _host_arg(d_hat, (2, Bn), name="d_hat"), _host_arg(x_hat, (2, Bn), name="x_hat")]
-        out = self._run_out(k_sim, N, Bn, est=True, host=True)
-        hp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32 if a.dtype == np.int32 else C.c_double))  # noqa: E731
-        rc = self.lib.ntm_mpc_run_est_from(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
-                                           C.byref(est.to_c()), Bn, k_sim, *[hp(a) for a, _ in state],
-                                           *[hp(v) for v in out.values()])
-        self._raise(rc, "ntm_mpc_run_est_from")
-        for dst, (src, staged) in zip((x, rho, U_old, active_ws, d_hat, x_hat), state):
-            if staged:
-                dst[...] = src
-        return out
+        return self._run_from(_HOST, "run_est_from", x, rho, U_old, active_ws, k_sim, cfg, (est,),
+                              {"d_hat": d_hat, "x_hat": x_hat})
 
     # ------------------------------------------------------------ actuator dead time
-    @staticmethod
-    def _queue_arg(arg, u_queue, dly: Delay, Bn, name="u_queue", **kw):
-        """The queue argument (steps, B) as (array, staged?); None where there is none."""
-        if u_queue is None:
-            return None, False
-        return arg(u_queue, (int(dly.steps), Bn), name=name, **kw)
-
     def step_dly(self, x_k: torch.Tensor, rho: torch.Tensor, U_old: torch.Tensor, d_hat: torch.Tensor,
                  x_hat: torch.Tensor, u_queue: torch.Tensor | None, est: Estimator, dly: Delay,
                  cfg: Config | None = None, active_ws: torch.Tensor | None = None):
@@ -984,69 +832,18 @@ class NtmMpc:
         ``U[0]`` at its end (None is allowed when steps == 0).  Returns step_est()'s dict
         plus ``x_plan`` (2, B), ``u_applied`` (B,) and ``u_queue``.  With steps == 0 it is
         step_est() bit for bit."""
-        if not L.has_input_delay(self.lib):
-            raise NtmLibraryError("this build of the library has no ntm_mpc_step_dly (NTM_MPC_HAS_INPUT_DELAY)")
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x_k.shape[1]
-        xk, _ = _dev_arg(x_k, (2, Bn), name="x_k")
-        rh, rho_st = _dev_arg(rho, (3 * N, Bn), name="rho")
-        uo, uo_st = _dev_arg(U_old, (N, Bn), name="U_old")
-        dh, dh_st = _dev_arg(d_hat, (2, Bn), name="d_hat")
-        xh, xh_st = _dev_arg(x_hat, (2, Bn), name="x_hat")
-        uq, uq_st = self._queue_arg(_dev_arg, u_queue, dly, Bn)
-        ws, ws_st = (None, False) if active_ws is None else _dev_arg(active_ws, (2 * (N + 1), Bn), torch.int32,
-                                                                     "active_ws")
-        out = {"U": self._empty(N, Bn), "x_pred": self._empty(2 * (N + 1), Bn), "x_next": self._empty(2, Bn),
-               "y": self._empty(2, Bn), "x_plan": self._empty(2, Bn), "u_applied": self._empty(Bn),
-               "exitflag": self._empty(Bn, dtype=torch.int32), "inner_iters": self._empty(Bn, dtype=torch.int32)}
-        rc = self.lib.ntm_mpc_step_dly_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
-                                              C.byref(est.to_c()), C.byref(dly.to_c()), Bn, _ptr(xk), _ptr(rh),
-                                              _ptr(uo), _ptr(dh), _ptr(xh), _ptr(uq), _ptr(out["U"]),
-                                              _ptr(out["x_pred"]), _ptr(out["x_next"]), _ptr(out["y"]),
-                                              _ptr(out["x_plan"]), _ptr(out["u_applied"]), _ptr(out["exitflag"]),
-                                              _ptr(out["inner_iters"]), _ptr(ws), self._stream())
-        self._raise(rc, "ntm_mpc_step_dly_device")
-        for staged, dst, src in ((rho_st, rho, rh), (uo_st, U_old, uo), (dh_st, d_hat, dh), (xh_st, x_hat, xh),
-                                 (uq_st, u_queue, uq), (ws_st, active_ws, ws)):
-            if staged:
-                dst.copy_(src)
-        out["d_hat"], out["x_hat"], out["u_queue"] = d_hat, x_hat, u_queue
-        return out
+        self._need_input_delay("ntm_mpc_step_dly")
+        return self._step(self._dev, "step_dly", x_k, rho, U_old, cfg, active_ws, (est, dly),
+                          {"d_hat": d_hat, "x_hat": x_hat, "u_queue": u_queue})
 
     def step_dly_host(self, x_k: np.ndarray, rho: np.ndarray, U_old: np.ndarray, d_hat: np.ndarray,
                       x_hat: np.ndarray, u_queue: np.ndarray | None, est: Estimator, dly: Delay,
                       cfg: Config | None = None, active_ws: np.ndarray | None = None):
         """ntm_mpc_step_dly with host arrays (the MEX path): ``d_hat``, ``x_hat`` and
         ``u_queue`` are updated in place and returned in the dict."""
-        if not L.has_input_delay(self.lib):
-            raise NtmLibraryError("this build of the library has no ntm_mpc_step_dly (NTM_MPC_HAS_INPUT_DELAY)")
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x_k.shape[1]
-        xk, _ = _host_arg(x_k, (2, Bn), name="x_k")
-        rh, rho_st = _host_arg(rho, (3 * N, Bn), name="rho")
-        uo, uo_st = _host_arg(U_old, (N, Bn), name="U_old")
-        dh, dh_st = _host_arg(d_hat, (2, Bn), name="d_hat")
-        xh, xh_st = _host_arg(x_hat, (2, Bn), name="x_hat")
-        uq, uq_st = self._queue_arg(_host_arg, u_queue, dly, Bn)
-        ws, ws_st = (None, False) if active_ws is None else _host_arg(active_ws, (2 * (N + 1), Bn), np.int32,
-                                                                      "active_ws")
-        out = {"U": _host_empty(N, Bn), "x_pred": _host_empty(2 * (N + 1), Bn), "x_next": _host_empty(2, Bn),
-               "y": _host_empty(2, Bn), "x_plan": _host_empty(2, Bn), "u_applied": np.empty(Bn),
-               "exitflag": np.empty(Bn, np.int32), "inner_iters": np.empty(Bn, np.int32)}
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))          # noqa: E731
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))           # noqa: E731
-        rc = self.lib.ntm_mpc_step_dly(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
-                                       C.byref(est.to_c()), C.byref(dly.to_c()), Bn, dp(xk), dp(rh), dp(uo), dp(dh),
-                                       dp(xh), None if uq is None else dp(uq), dp(out["U"]), dp(out["x_pred"]),
-                                       dp(out["x_next"]), dp(out["y"]), dp(out["x_plan"]), dp(out["u_applied"]),
-                                       ip(out["exitflag"]), ip(out["inner_iters"]), None if ws is None else ip(ws))
-        self._raise(rc, "ntm_mpc_step_dly")
-        for staged, dst, src in ((rho_st, rho, rh), (uo_st, U_old, uo), (dh_st, d_hat, dh), (xh_st, x_hat, xh),
-                                 (uq_st, u_queue, uq), (ws_st, active_ws, ws)):
-            if staged:
-                dst[...] = src
-        out["d_hat"], out["x_hat"], out["u_queue"] = d_hat, x_hat, u_queue
-        return out
+        self._need_input_delay("ntm_mpc_step_dly")
+        return self._step(_HOST, "step_dly", x_k, rho, U_old, cfg, active_ws, (est, dly),
+                          {"d_hat": d_hat, "x_hat": x_hat, "u_queue": u_queue})
 
     def run_dly(self, x0: torch.Tensor, est: Estimator, dly: Delay, k_sim: int = 20, cfg: Config | None = None,
                 d0: torch.Tensor | None = None, xhat0: torch.Tensor | None = None, uq0: torch.Tensor | None = None):
@@ -1055,42 +852,13 @@ class NtmMpc:
         initial queue (None: zeros, power off until the first command arrives).  Returns
         run_est()'s dict plus ``uak`` (k_sim, B), the applied input (``uk`` stays the
         commanded U[0]: uak[k + steps] == uk[k]), and ``xpk`` (2 k_sim, B), the plan state."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x0.shape[1]
-        x0, _ = _dev_arg(x0, (2, Bn), name="x0")
-        if d0 is not None:
-            d0, _ = _dev_arg(d0, (2, Bn), name="d0")
-        if xhat0 is not None:
-            xhat0, _ = _dev_arg(xhat0, (2, Bn), name="xhat0")
-        uq0, _ = self._queue_arg(_dev_arg, uq0, dly, Bn, name="uq0")
-        out = self._run_out(k_sim, N, Bn, est=True, dly=True)
-        rc = self.lib.ntm_mpc_run_dly_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
-                                             C.byref(est.to_c()), C.byref(dly.to_c()), Bn, k_sim, _ptr(x0), _ptr(d0),
-                                             _ptr(xhat0), _ptr(uq0), *[_ptr(v) for v in out.values()],
-                                             self._stream())
-        self._raise(rc, "ntm_mpc_run_dly_device")
-        return out
+        return self._run(self._dev, "run_dly", x0, k_sim, cfg, (est, dly), {"d0": d0, "xhat0": xhat0, "uq0": uq0})
 
     def run_dly_host(self, x0: np.ndarray, est: Estimator, dly: Delay, k_sim: int = 20, cfg: Config | None = None,
                      d0: np.ndarray | None = None, xhat0: np.ndarray | None = None, uq0: np.ndarray | None = None):
         """ntm_mpc_run_dly with host arrays: run_est_host with the dead time, plus ``uak``
         and ``xpk``."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x0.shape[1]
-        x0, _ = _host_arg(x0, (2, Bn), name="x0")
-        if d0 is not None:
-            d0, _ = _host_arg(d0, (2, Bn), name="d0")
-        if xhat0 is not None:
-            xhat0, _ = _host_arg(xhat0, (2, Bn), name="xhat0")
-        uq0, _ = self._queue_arg(_host_arg, uq0, dly, Bn, name="uq0")
-        out = self._run_out(k_sim, N, Bn, est=True, host=True, dly=True)
-        hp = lambda a: None if a is None else a.ctypes.data_as(                                    # noqa: E731
-            C.POINTER(C.c_int32 if a.dtype == np.int32 else C.c_double))
-        rc = self.lib.ntm_mpc_run_dly(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
-                                      C.byref(est.to_c()), C.byref(dly.to_c()), Bn, k_sim, hp(x0), hp(d0), hp(xhat0),
-                                      hp(uq0), *[hp(v) for v in out.values()])
-        self._raise(rc, "ntm_mpc_run_dly")
-        return out
+        return self._run(_HOST, "run_dly", x0, k_sim, cfg, (est, dly), {"d0": d0, "xhat0": xhat0, "uq0": uq0})
 
     def run_dly_from(self, x: torch.Tensor, rho: torch.Tensor, U_old: torch.Tensor, active_ws: torch.Tensor,
                      d_hat: torch.Tensor, x_hat: torch.Tensor, u_queue: torch.Tensor | None, est: Estimator,
@@ -1099,46 +867,15 @@ class NtmMpc:
         the queue ``u_queue`` (steps, B) carried too, all updated in place; one call of k
         steps and any split of them give the same bits.  ``dly.steps`` must not change
         between the chunks of one loop.  Returns run_dly()'s dict."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x.shape[1]
-        state = [_dev_arg(x, (2, Bn), name="x"), _dev_arg(rho, (3 * N, Bn), name="rho"),
-                 _dev_arg(U_old, (N, Bn), name="U_old"),
-                 _dev_arg(active_ws, (2 * (N + 1), Bn), torch.int32, "active_ws"),
-                 _dev_arg(d_hat, (2, Bn), name="d_hat"), _dev_arg(x_hat, (2, Bn), name="x_hat"),
-                 self._queue_arg(_dev_arg, u_queue, dly, Bn)]
-        out = self._run_out(k_sim, N, Bn, est=True, dly=True)
-        rc = self.lib.ntm_mpc_run_dly_from_device(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
-                                                  C.byref(est.to_c()), C.byref(dly.to_c()), Bn, k_sim,
-                                                  *[_ptr(a) for a, _ in state], *[_ptr(v) for v in out.values()],
-                                                  self._stream())
-        self._raise(rc, "ntm_mpc_run_dly_from_device")
-        for dst, (src, staged) in zip((x, rho, U_old, active_ws, d_hat, x_hat, u_queue), state):
-            if staged:
-                dst.copy_(src)
-        return out
+        return self._run_from(self._dev, "run_dly_from", x, rho, U_old, active_ws, k_sim, cfg, (est, dly),
+                              {"d_hat": d_hat, "x_hat": x_hat, "u_queue": u_queue})
 
     def run_dly_from_host(self, x: np.ndarray, rho: np.ndarray, U_old: np.ndarray, active_ws: np.ndarray,
                           d_hat: np.ndarray, x_hat: np.ndarray, u_queue: np.ndarray | None, est: Estimator,
                           dly: Delay, k_sim: int = 20, cfg: Config | None = None):
         """ntm_mpc_run_dly_from with host arrays; the state arrays are updated in place."""
-        cfg = cfg or self.config
-        N, Bn = cfg.N, x.shape[1]
-        state = [_host_arg(x, (2, Bn), name="x"), _host_arg(rho, (3 * N, Bn), name="rho"),
-                 _host_arg(U_old, (N, Bn), name="U_old"),
-                 _host_arg(active_ws, (2 * (N + 1), Bn), np.int32, "active_ws"),
-                 _host_arg(d_hat, (2, Bn), name="d_hat"), _host_arg(x_hat, (2, Bn), name="x_hat"),
-                 self._queue_arg(_host_arg, u_queue, dly, Bn)]
-        out = self._run_out(k_sim, N, Bn, est=True, host=True, dly=True)
-        hp = lambda a: None if a is None else a.ctypes.data_as(                                    # noqa: E731
-            C.POINTER(C.c_int32 if a.dtype == np.int32 else C.c_double))
-        rc = self.lib.ntm_mpc_run_dly_from(self._ctx, C.byref(self.physics.to_c()), C.byref(cfg.to_c()),
-                                           C.byref(est.to_c()), C.byref(dly.to_c()), Bn, k_sim,
-                                           *[hp(a) for a, _ in state], *[hp(v) for v in out.values()])
-        self._raise(rc, "ntm_mpc_run_dly_from")
-        for dst, (src, staged) in zip((x, rho, U_old, active_ws, d_hat, x_hat, u_queue), state):
-            if staged:
-                dst[...] = src
-        return out
+        return self._run_from(_HOST, "run_dly_from", x, rho, U_old, active_ws, k_sim, cfg, (est, dly),
+                              {"d_hat": d_hat, "x_hat": x_hat, "u_queue": u_queue})
 
     def step_kkt(self, x_k: torch.Tensor, rho_qp: torch.Tensor, U: torch.Tensor, lam: torch.Tensor | None,
                  cfg: Config | None = None):
@@ -1157,30 +894,6 @@ class NtmMpc:
                                                 _ptr(xk), _ptr(rq), _ptr(U), _ptr(lam) if cfg.m else None, _ptr(out),
                                                 self._stream()), "ntm_mpc_kkt_device")
         return out
-
-
-def _quadprog_mixed(self, H: torch.Tensor, f: torch.Tensor, Lin: torch.Tensor | None, b: torch.Tensor | None):
-    """Config 5's fp32 leg (ntm_qp_mixed_device; not the fp64 product path): the QP
-    solved in fp32 on fp32-rounded data, its active set then re-solved exactly in
-    fp64 and certified (fp64 fallback otherwise).  Returns (U refined (N, B),
-    U32 fp32 solution (N, B), exitflag (B,), info (B,) bit 0 certified / bit 1
-    fp64 fallback / bit 2 fp32 not optimal, fp32 GI iterations (B,))."""
-    N, Bn = f.shape
-    m = 0 if Lin is None else b.shape[0]
-    H, _ = _dev_arg(H, (N * N, Bn), name="H")
-    f, _ = _dev_arg(f, (N, Bn), name="f")
-    if m:
-        Lin, _ = _dev_arg(Lin, (m * N, Bn), name="A")
-        b, _ = _dev_arg(b, (m, Bn), name="b")
-    U, U32 = self._empty(N, Bn), self._empty(N, Bn)
-    flag, info, its = (self._empty(Bn, dtype=torch.int32) for _ in range(3))
-    self._raise(self.lib.ntm_qp_mixed_device(self._ctx, Bn, N, m, _ptr(H), _ptr(f), _ptr(Lin) if m else None,
-                                             _ptr(b) if m else None, _ptr(U), _ptr(U32), _ptr(flag), _ptr(info),
-                                             _ptr(its), self._stream()), "ntm_qp_mixed_device")
-    return U, U32, flag, info, its
-
-
-NtmMpc.quadprog_mixed = _quadprog_mixed
 
 
 def scenarios_x0(first_id: int, B: int, seed: int = 20241220):

@@ -7,16 +7,19 @@ its parent commit).
     python tools/dump_entrypoints.py dump change.npz
     python tools/dump_entrypoints.py compare parent.npz change.npz [--out RECORD.txt]
 
-`dump` calls step_ws, step_dual, step_obs, run_obs, step_est, run_est, run, run_from and
-run_est_from through ntm_mpc.api (the library is the one NTM_MPC_LIB names, as for every
+`dump` calls step_ws, step_dual, step_obs, run_obs, step_est, run_est, run, run_from,
+run_est_from, step_dly, run_dly and run_dly_from through ntm_mpc.api (the library is the one NTM_MPC_LIB names, as for every
 tool here) and writes each output array under "<case>/<entry>/<dev|host>/<name>".  Cases:
 k_sim = 5; a partial last block (B no multiple of 64 / lanes); lanes 16 (N = 10) and 64
 (N = 33, the runtime-N kernels), 32 when the process runs under NTM_LANES=32 (N = 24: run
 `dump` once more under it, into a file of its own); N = 20 steered onto the far, the
 all-LDS and the one-wave build; N = 50 in modes 2 and 3; modes 0, 2 and 3; a generator
 with a plasma spread and a disturbance; the observer nominal and per scenario; the
-estimator with sigma_y != 0; active_ws from the previous step, then with one slot made
-invalid (an id out of range); the stats counters attached; k_sim = 0 for the _from forms.
+estimator with sigma_y != 0; a dead time of 2 steps with and without the delay-compensating
+plan; active_ws from the previous step, then with one slot made invalid (an id out of range);
+the stats counters attached; k_sim = 0 for the _from forms.  One small case runs a second
+time ("<case>_c") with every array argument handed over C-contiguous, not in the ABI's
+layout, which drives the binding's staged copies and copy-backs.
 `compare` compares every array and writes one line per case (its entries, array and byte
 counts), then ALL IDENTICAL, or the arrays that differ (exit 1).
 """
@@ -38,6 +41,7 @@ CASES = [("n10_m0", 10, 7, 0, None), ("n10_m2", 10, 7, 2, None), ("n10_m3", 10, 
          ("n20_far", 20, 70, 2, (0, 0)), ("n20_near", 20, 70, 2, (1000, 0)), ("n20_near1w", 20, 70, 2, (1000, 1000)),
          ("n20_m3", 20, 5, 3, None), ("n50_m2", 50, 5, 2, None), ("n50_m3", 50, 5, 3, None)]
 CASES32 = [("n24_p32_m2", 24, 3, 2, None), ("n24_p32_m3", 24, 3, 3, None)]      # under NTM_LANES=32
+CASE_C = ("n10_m2", 10, 7, 2, None)                                              # once more, C-contiguous arguments
 
 
 def host(t):
@@ -46,9 +50,9 @@ def host(t):
     return t if not isinstance(t, torch.Tensor) else np.asfortranarray(t.cpu().numpy())
 
 
-def dump_case(ctl, name, N, B, mode, steer, dev, out):
+def dump_case(ctl, name, N, B, mode, steer, dev, out, abi=True):
     import torch
-    from ntm_mpc import Config, Estimator, Observer, ScenarioGen, scenarios_x0
+    from ntm_mpc import Config, Delay, Estimator, Observer, ScenarioGen, scenarios_x0
     cfg = Config(N=N, mode=mode)
     ctl.set_small_batch(*([steer[0]] if steer else []))
     ctl.set_one_wave_batch(*([steer[1]] if steer else []))
@@ -57,8 +61,15 @@ def dump_case(ctl, name, N, B, mode, steer, dev, out):
     stats = torch.zeros(6, B, dtype=torch.int32, device=f"cuda:{ctl.device}")
     ctl.set_stats(stats)
     form = "dev" if dev else "host"
-    arr = (lambda a: ctl.tensor(a)) if dev else (lambda a: np.asfortranarray(np.asarray(a, dtype=float)))
+    # an (E, B) array in the layout under test: the ABI's (a no-op for what the API returns) or C-contiguous
+    if dev:
+        lay = (lambda t: t) if abi else (lambda t: t.contiguous())
+    else:
+        lay = np.asfortranarray if abi else np.ascontiguousarray
+    arr = (lambda a: lay(ctl.tensor(a))) if dev else (lambda a: lay(np.asarray(a, dtype=float)))
     sfx = "" if dev else "_host"
+    if not abi:
+        name += "_c"
 
     def put(entry, d):
         for k, v in d.items():
@@ -69,7 +80,7 @@ def dump_case(ctl, name, N, B, mode, steer, dev, out):
         rho, Uo = ctl.initial_state(x, cfg)
         ws = ctl.new_active_ws(B, cfg)
         s = [x, rho, Uo, ws]
-        return s if dev else [host(t) for t in s]
+        return [lay(t) for t in (s if dev else [host(t) for t in s])]
 
     def steps(entry, call, extra):
         # three steps: no candidates, the previous step's, then scenario 1's first slot made invalid
@@ -79,7 +90,7 @@ def dump_case(ctl, name, N, B, mode, steer, dev, out):
                 ws[0, 1], ws[N, 1] = 10 ** 6, 1
             o = call(x, rho, Uo, *extra, cfg=cfg, active_ws=ws)
             put(f"{entry}{i}", dict(o, rho=rho, U_old=Uo, active_ws=ws))
-            x = o["x_next"] if dev else np.asfortranarray(o["x_next"])
+            x = lay(o["x_next"])
 
     d2 = lambda v: arr(np.full((2, B), v))                                       # noqa: E731
     est = Estimator(True, (0.5, 0.25), (0.3, 0.6), (1e-4, 2.0))
@@ -89,14 +100,21 @@ def dump_case(ctl, name, N, B, mode, steer, dev, out):
         steps(f"step_obs_{tag}", getattr(ctl, "step_obs" + sfx), (d2(1e-4), obs))
         put(f"run_obs_{tag}", getattr(ctl, "run_obs" + sfx)(state()[0], obs, K, cfg, d0=d2(-1e-4)))
     x0 = state()[0]
-    steps("step_est", getattr(ctl, "step_est" + sfx), (d2(1e-4), x0 * 1.01, est))
-    put("run_est", getattr(ctl, "run_est" + sfx)(x0, est, K, cfg, d0=d2(-1e-4), xhat0=x0 * 0.99))
+    uq = lambda: arr(2e5 + 1.1e5 * np.arange(2)[:, None] + 7e3 * np.arange(B)[None, :])   # noqa: E731
+    steps("step_est", getattr(ctl, "step_est" + sfx), (d2(1e-4), lay(x0 * 1.01), est))
+    put("run_est", getattr(ctl, "run_est" + sfx)(x0, est, K, cfg, d0=d2(-1e-4), xhat0=lay(x0 * 0.99)))
     put("run", getattr(ctl, "run" + sfx)(x0, K, cfg))
-    for entry, extra in (("run_from", ()), ("run_est_from", (d2(1e-4), x0 * 1.01, est))):
-        s = state() + list(extra[:2])
+    froms = [("run_from", "run_from", (), ()), ("run_est_from", "run_est_from", (d2(1e-4), lay(x0 * 1.01)), (est,))]
+    for tag, dly in (("p", Delay(2, True)), ("n", Delay(2, False))):
+        steps(f"step_dly_{tag}", getattr(ctl, "step_dly" + sfx), (d2(1e-4), lay(x0 * 1.01), uq(), est, dly))
+        put(f"run_dly_{tag}", getattr(ctl, "run_dly" + sfx)(x0, est, dly, K, cfg, d0=d2(-1e-4), xhat0=lay(x0 * 0.99),
+                                                            uq0=uq()))
+        froms.append(("run_dly_from", f"run_dly_from_{tag}", (d2(1e-4), lay(x0 * 1.01), uq()), (est, dly)))
+    for entry, tag, carried, opts in froms:
+        s = state() + list(carried)
         for i, k in enumerate((2, 0, K - 2)):                                    # chunks, k_sim = 0 among them
-            o = getattr(ctl, entry + sfx)(*s, *extra[2:], k, cfg)
-            put(f"{entry}{i}", dict(o, **{f"state{j}": t for j, t in enumerate(s)}))
+            o = getattr(ctl, entry + sfx)(*s, *opts, k, cfg)
+            put(f"{tag}{i}", dict(o, **{f"state{j}": t for j, t in enumerate(s)}))
     torch.cuda.synchronize()
     out[f"{name}/stats/{form}"] = stats.cpu().numpy()
     ctl.set_stats(None)
@@ -113,6 +131,10 @@ def dump(path):
         for dev in (True, False):
             dump_case(ctl, *case, dev, out)
         print(case[0], "done", flush=True)
+    if lanes.value != 32:
+        for dev in (True, False):
+            dump_case(ctl, *CASE_C, dev, out, abi=False)
+        print(CASE_C[0] + "_c", "done", flush=True)
     ctl.close()
     Path(path).parent.mkdir(parents=True, exist_ok=True)
     np.savez(path, **out)
